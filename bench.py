@@ -19,7 +19,12 @@ the GPU) and prints rank 0's line; under torch.distributed.run it is a rank.
 KNN355_REHEARSE_ONE_GPU=1 puts every rank on GPU 0 with gloo as the collective backend:
 a functional rehearsal of the N-rank path on a one-GPU box, not a measurement.
 
-Also on the same JSON line (N=1 only, outside the timed region):
+A plain run sets up, warms up, times the K steps, checks the last step's result and prints the
+headline.  --dump-outputs DIR also writes that result (D, I of the last timed step) to DIR as .npy
+files; the inputs are seeded, so two builds can be compared output for output.
+
+With --full, also on the same JSON line (N=1 only, outside the timed region; --no-cpu, --no-batch,
+--no-extras leave legs out):
   roofline      the scan kernel against the HBM roofline (each step reads the shard once); box_read_rate: a plain read
                 kernel over the same rows on this box, for scale
   cpu_baseline  the reference's CPU path (faiss IndexFlat.search) on this box's host cores, on a
@@ -70,13 +75,25 @@ def parse():
     ap.add_argument("--in-flight", type=int, default=0, choices=(0, 1, 2),
                     help="searches in flight: 2 = steps alternate between the index's two lanes (the all-gather and the small "
                          "launches of one search hide behind the other's scan), 1 = one after the other, 0 = 2 on several GPUs, 1 on one")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-batch", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the nq sweep, the host-buffer step and the HNSW run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, comparison with the shard sweep, CPU baseline, "
+                         "batch, all-vs-all, nq sweep, host-buffer step, HNSW (the --no-* options below thin that out)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-batch", action="store_true", help="with --full: skip the batch and all-vs-all legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the nq sweep, the host-buffer step and the HNSW run")
     ap.add_argument("--cpu-sample-rows", type=int, default=2_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result (distances.npy float32, labels.npy float64) to DIR")
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the N ranks up (gloo, CPU) and tear them down: exercises the bounded waits and the failure report")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if not args.full:  # a plain run: set up, warm up, time the steps, nothing else
+        args.no_cpu = args.no_batch = args.no_extras = True
+    return args
 
 
 # ---- bring-up of the N-rank run: bounded, and loud when it fails -------------------------------------------------
@@ -462,8 +479,10 @@ def run(args):
                             "digests of all ranks must agree (checked on the last timed step, outside the timed region)"}
     if not (planted_ok and sorted_ok and verification["identical_on_all_ranks"]):
         raise RuntimeError(f"bench.py: the timed search returned a wrong result: {json.dumps(verification)}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Dh, Ih)
 
-    # ---- scan kernel durations of the timed steps (hipEvents on the launch stream) --
+    # ---- scan kernel durations of the timed steps (hipEvents on the launch stream; quoted by the --full roofline) --
     buf = (ctypes.c_float * 64)()
     n = L.knn_scan_times(index.local._h, buf, min(64, args.steps))
     scan_ms = [buf[i] for i in range(n) if buf[i] > 0]
@@ -532,7 +551,7 @@ def run(args):
         out["scan_ms_per_rank"] = {"min": min(ok) if ok else None, "max": max(ok) if ok else None, "all": scan_ms_ranks,
                                    "note": "mean HIP-event duration of each rank's scan launches (with two searches in flight a launch's "
                                            "events span the other lane's work too)"}
-    sweep_ref = None if rehearse else shard_sweep_reference(nb_local, in_flight)  # (a rehearsal's times mean nothing: N ranks share one GPU over gloo)
+    sweep_ref = None if rehearse or not args.full else shard_sweep_reference(nb_local, in_flight)  # (a rehearsal's times mean nothing: N ranks share one GPU over gloo)
     if sweep_ref is not None:
         # what ONE GPU needs for a shard of this size with no collective at all (builder-run sweep, committed): the part of a
         # multi-GPU step that is not the scan shows up as efficiency < 1
@@ -549,7 +568,7 @@ def run(args):
         # denominator there: one scan's bytes per step.
         avg_scan_ms = 1e3 * elapsed / args.steps
         basis = "ms_per_step (two searches in flight: per-launch event durations overlap)"
-    if avg_scan_ms:
+    if args.full and avg_scan_ms:
         achieved = alg_bytes / (avg_scan_ms * 1e-3) / 1e9
         traffic, traffic_source = None, None
         tfile = ROOT / "profiles" / "pmc_traffic.json"
@@ -618,6 +637,28 @@ def run(args):
     if use_pg:
         dist.destroy_process_group()
     return json.dumps(out)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, D, I):
+    """--dump-outputs: what the caller of the timed search receives from its last step, (D, I) of shape [nq, k], as
+    DIR/distances.npy (float32) and DIR/labels.npy (float64: every id < 2**53 is exact).  Above 64 MB in all, a fixed
+    seeded sample of query rows is written instead, and their row numbers as DIR/query_rows.npy (float64)."""
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    nq = D.shape[0]
+    per_row = D.shape[1] * (4 + 8)
+    if nq * per_row > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - 4096 - 8 * nq) // per_row)  # (4096: the three .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(nq, size=keep, replace=False))
+        D, I = D[rows], I[rows]
+        np.save(out / "query_rows.npy", rows.astype(np.float64))
+    else:
+        (out / "query_rows.npy").unlink(missing_ok=True)
+    np.save(out / "distances.npy", np.ascontiguousarray(D, dtype=np.float32))
+    np.save(out / "labels.npy", np.ascontiguousarray(I, dtype=np.float64))
 
 
 def real_data():

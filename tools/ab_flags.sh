@@ -2,7 +2,7 @@
 # A/B of tuning flags (KNN355_FLAGS) on the bench's batch legs and the streaming step: tools/ab_flags.sh 0 2048 0 2048 (needs the developer build: make -C knn-for-homology_amd/csrc trace, KNN355_LIB=.../libknn355_trace.so -- the shipped library ignores KNN355_FLAGS)
 for fl in "$@"; do
   echo "== KNN355_FLAGS=$fl"
-  KNN355_FLAGS=$fl timeout -k 10 300 python bench.py --no-extras --no-cpu --steps 30 --warmup 5 2>/dev/null | python -c "
+  KNN355_FLAGS=$fl timeout -k 10 300 python bench.py --full --no-extras --no-cpu --steps 30 --warmup 5 2>/dev/null | python -c "
 import sys, json
 o = json.loads(sys.stdin.read().strip().splitlines()[-1])
 b = o['batch']; a = o['all_vs_all_query_sharded']

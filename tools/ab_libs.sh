@@ -2,7 +2,7 @@
 # A/B of library builds on the bench's batch legs and the streaming step: tools/ab_libs.sh lib1.so lib2.so ...
 for lib in "$@"; do
   echo "== $lib"
-  KNN355_LIB=$PWD/$lib timeout -k 10 300 python bench.py --no-extras --no-cpu --steps 30 --warmup 5 2>/dev/null | python -c "
+  KNN355_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --no-extras --no-cpu --steps 30 --warmup 5 2>/dev/null | python -c "
 import sys, json
 o = json.loads(sys.stdin.read().strip().splitlines()[-1])
 b = o['batch']; a = o['all_vs_all_query_sharded']

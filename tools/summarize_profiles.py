@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns the rocprofv3 output of tools/collect_profiles.sh (gpurun_out/) into the
+"""Turns the rocprofv3 output of tools/collect_profiles.sh ($KNN355_MEASURE_OUT, default measure_out/) into the
 committed summaries under profiles/: kernel stats CSV, per-kernel HBM traffic from the
 PMC passes (FETCH_SIZE doubled for wide streaming reads on gfx950 as
 MI355X_MICROARCH.md section HBM prescribes; units are KiB), and pmc_traffic.json which
@@ -7,6 +7,7 @@ bench.py reads for roofline.traffic.  usage: summarize_profiles.py <round-tag>""
 import collections
 import csv
 import json
+import os
 import shutil
 import sys
 from pathlib import Path
@@ -15,7 +16,7 @@ ROOT = Path(__file__).resolve().parent.parent
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 out = ROOT / "profiles"
 out.mkdir(exist_ok=True)
-go = ROOT / "gpurun_out"
+go = ROOT / os.environ.get("KNN355_MEASURE_OUT", "measure_out")
 
 stats = go / f"prof_{tag}" / f"{tag}_kernel_stats.csv"
 shutil.copyfile(stats, out / f"{tag}_bench_kernel_stats.csv")
