@@ -128,6 +128,29 @@ int knn_flat_search_keys_dev(knn_handle h, const float *q_dev, int64_t nq, int64
  * streams cannot interfere */
 int knn_merge_keys_dev(knn_handle h, const uint64_t *keys_dev, int32_t nlists, int64_t nq, int64_t k,
                        float *D_dev, int64_t *I_dev, void *stream);
+/* ---- index.range_search(x, radius) (FAISS's other flat-index query) ----------
+ * Every row whose score beats the radius.  FAISS is not part of the reference tree: the
+ * rules below are restated from FAISS 1.7.2's utils/distances.cpp (range_search_inner_product,
+ * range_search_L2sqr) and python/class_wrappers.py.
+ *   - inner product keeps score > radius; squared L2 (no sqrt) keeps score < radius.  Both are
+ *     strict: a score equal to the radius is excluded.  A NaN radius keeps nothing; -inf (IP) /
+ *     +inf (L2) keeps every row with a finite score.
+ *   - scores are the bits knn_flat_search returns for the same (query, row), including the
+ *     small-batch squared-L2 rule (fewer than 20 queries in the batch -- or in the batch announced
+ *     by knn_flat_set_batch -- sum (x - y)^2, otherwise max(0, |x|^2 + |y|^2 - 2<x,y>)).
+ *   - the results of query i are entries lims[i] .. lims[i+1] - 1, in ascending row id (the order
+ *     FAISS's exhaustive scan appends in); no cap per query other than memory.
+ * knn_flat_range_search runs the search, writes lims_host[nq + 1] (size_t in FAISS's wrapper) and
+ * keeps the lims[nq] results in host memory of the handle; knn_flat_range_fetch copies them to
+ * D_host (float32) / I_host (int64) and releases them -- call it once behind every search (the next
+ * range search on the handle replaces results not fetched).  ntotal = 0 or nq = 0: all lims 0.
+ * knn_flat_range_search_self: the same search with rows [row0, row0 + nrows) of the index as the
+ * queries (no upload; identical results to knn_flat_range_search on those rows).
+ * Hot path: range_scan_kernel (range.inc), the flat scan's MFMA tile with a threshold-and-compact
+ * epilogue; the host reads the per-(query, chunk) counts, then copies the runs into place. */
+int knn_flat_range_search(knn_handle h, const float *q_host, int64_t nq, float radius, uint64_t *lims_host);
+int knn_flat_range_search_self(knn_handle h, int64_t row0, int64_t nrows, float radius, uint64_t *lims_host);
+int knn_flat_range_fetch(knn_handle h, float *D_host, int64_t *I_host);
 /* pre-sizes the device storage for nrows rows (faiss has no equivalent; avoids
  * regrowth copies when a shard is filled by several add calls) */
 int knn_flat_reserve(knn_handle h, int64_t nrows);
@@ -287,6 +310,11 @@ int knn_gather_distances(knn_handle h, const float *q_host, int64_t nq, const in
  * geometry; used by bench.py for the roofline line */
 int knn_last_scan_info(knn_handle h, char *name, int32_t name_len, int32_t *query_tile,
                        int32_t *db_tile, int32_t *nchunks, int32_t *grid);
+/* how the last range search on this handle ran: query_blocks = blocks of queries it was split
+ * into (each one scan launch), redos = rescans of queries whose per-chunk staging segment
+ * overflowed (at most one per query), redo_queries = queries rescanned.  knn_last_scan_info
+ * names the range kernel and its geometry. */
+int knn_last_range_info(knn_handle h, int64_t *query_blocks, int64_t *redos, int64_t *redo_queries);
 /* device time (ms) of the scan kernel launches of the last search, measured
  * with hipEvents on the launch stream */
 float knn_last_scan_ms(knn_handle h);

@@ -97,6 +97,10 @@ def _declare(L):
         "knn_scan_times": (c_int32, [H, c_void_p, c_int32]),
         "knn_last_seed_info": (c_int32, [H, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)]),
         "knn_flat_reserve": (c_int32, [H, c_int64]),
+        "knn_flat_range_search": (c_int32, [H, c_void_p, c_int64, c_float, c_void_p]),
+        "knn_flat_range_search_self": (c_int32, [H, c_int64, c_int64, c_float, c_void_p]),
+        "knn_flat_range_fetch": (c_int32, [H, c_void_p, c_void_p]),
+        "knn_last_range_info": (c_int32, [H, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export the ABI

@@ -3199,6 +3199,11 @@ struct knn_index_s {
     int pub_rounds_force = 0; // tile-minimum seed: rounds of publications (0: the host's choice)
     std::string last_kernel;
     int last_qt = 0, last_dt = 0, last_chunks = 0, last_grid = 0;
+    // range search (range.inc): scratch, and the results of the last search until knn_flat_range_fetch takes them
+    DevBuf ws_rq, ws_rqn, ws_rcnt, ws_rsegD, ws_rsegI, ws_roff, ws_routD, ws_routI, ws_rsel, ws_rq2, ws_rexp;
+    std::vector<float> range_D;
+    std::vector<int64_t> range_I;
+    int64_t range_qblocks = 0, range_redos = 0, range_redo_queries = 0; // query blocks, overflow rescans, queries rescanned
     float last_ms = 0.f;
 };
 
@@ -3414,7 +3419,8 @@ extern "C" void knn_free(knn_handle h)
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         if (!h->is_view && h->xb) (void)hipDeviceSynchronize(); // a view's stream may still be scanning these rows
         free_index_buffers(h);
-        DevBuf *bufs[] = {&h->xb16, &h->ws_q16, &h->ws_sym, &h->ws_qdiff, &h->ws_defer, &h->ws_turn, &h->ws_flag, &h->ws_q, &h->ws_qn, &h->ws_lists, &h->ws_D, &h->ws_I, &h->ws_tmp, &h->ws_tmp2, &h->ws_D1, &h->ws_I1, &h->ws_tmp3};
+        DevBuf *bufs[] = {&h->xb16, &h->ws_q16, &h->ws_sym, &h->ws_qdiff, &h->ws_defer, &h->ws_turn, &h->ws_flag, &h->ws_q, &h->ws_qn, &h->ws_lists, &h->ws_D, &h->ws_I, &h->ws_tmp, &h->ws_tmp2, &h->ws_D1, &h->ws_I1, &h->ws_tmp3,
+                          &h->ws_rq, &h->ws_rqn, &h->ws_rcnt, &h->ws_rsegD, &h->ws_rsegI, &h->ws_roff, &h->ws_routD, &h->ws_routI, &h->ws_rsel, &h->ws_rq2, &h->ws_rexp};
         for (DevBuf *b : bufs) b->release();
         for (LevelBufs &b : h->ws_level) {
             b.qlist.release();
@@ -5517,3 +5523,4 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "hnsw.inc"
 #include "lsh.inc"
 #include "eval.inc"
+#include "range.inc"

@@ -15,9 +15,11 @@ Reference call sites (konstin/knn-for-homology):
 Semantics kept: float32 C-contiguous 2-D inputs only (anything else raises, as the
 faiss SWIG wrapper does); ``search`` returns freshly allocated ``(D float32 [nq,k],
 I int64 [nq,k])`` best first; unfilled slots are id -1 with -FLT_MAX (IP) / +FLT_MAX
-(L2); ``normalize_L2`` works in place on the caller's array.
+(L2); ``range_search`` returns ``(lims uint64 [nq+1], D float32, I int64)`` (see
+IndexFlat.range_search); ``normalize_L2`` works in place on the caller's array.
 """
 import ctypes
+import threading
 
 import numpy as np
 
@@ -98,6 +100,21 @@ class IndexFlat(Index):
         _lib.check(_lib.lib().knn_flat_search(self._h, x.ctypes.data, x.shape[0], k, D.ctypes.data, I.ctypes.data))
         return D, I
 
+    def range_search(self, x, radius):
+        """faiss.IndexFlat.range_search: every row whose score beats ``radius``.
+
+        Returns ``(lims, D, I)`` as FAISS's Python wrapper does: ``lims`` uint64 [nq + 1] (size_t in
+        FAISS), the results of query i are ``D[lims[i]:lims[i+1]]`` (float32) and ``I[lims[i]:lims[i+1]]``
+        (int64), in ascending row id, with no cap per query.  Inner product keeps score > radius,
+        METRIC_L2 keeps squared distance < radius; both are strict, a NaN radius keeps nothing and
+        -inf (IP) / +inf (L2) keeps every row.  Scores are the bits ``search`` returns for the same
+        (query, row), including FAISS's small-batch L2 rule (fewer than 20 queries: the sum of squared
+        differences).  FAISS is not part of the reference tree: strictness, order and the lims dtype
+        are restated from FAISS 1.7.2's utils/distances.cpp and python/class_wrappers.py."""
+        _check_matrix(x, self._d)
+        return self._range(lambda L, r, lims: L.knn_flat_range_search(self._h, x.ctypes.data, x.shape[0], r, lims),
+                           x.shape[0], radius)
+
     def reset(self):
         _lib.check(_lib.lib().knn_reset(self._h))
 
@@ -109,6 +126,19 @@ class IndexFlat(Index):
 
     def reconstruct(self, i):
         return self.reconstruct_n(int(i), 1)[0]
+
+    def _range(self, run, nq, radius):
+        L = _lib.lib()
+        r = ctypes.c_float(np.float32(radius))
+        lims = np.zeros(nq + 1, np.uint64)
+        # (the library keeps a handle's last range result until it is fetched: search and fetch go together)
+        with self.__dict__.setdefault("_range_lock", threading.Lock()):
+            _lib.check(run(L, r, lims.ctypes.data))
+            n = int(lims[-1])
+            D = np.empty(n, np.float32)
+            I = np.empty(n, np.int64)
+            _lib.check(L.knn_flat_range_fetch(self._h, D.ctypes.data, I.ctypes.data))
+        return lims, D, I
 
     # -- knn355 extras (not in faiss) --
     def reconstruct_into(self, out, i0=0):
@@ -129,6 +159,13 @@ class IndexFlat(Index):
         I = _lib.result_array((nrows, k), np.int64)
         _lib.check(_lib.lib().knn_flat_search_self(self._h, int(row0), nrows, k, D.ctypes.data, I.ctypes.data))
         return D, I
+
+    def range_search_self(self, radius, row0=0, nrows=None):
+        """``index.range_search(x, radius)`` for x = the index's own rows [row0, row0+nrows), without
+        uploading them again; the same results as ``range_search(index.reconstruct_n(row0, nrows), radius)``."""
+        row0 = int(row0)
+        nrows = self.ntotal - row0 if nrows is None else int(nrows)
+        return self._range(lambda L, r, lims: L.knn_flat_range_search_self(self._h, row0, nrows, r, lims), nrows, radius)
 
     def view(self):
         """A read-only second handle on the same device rows with its own stream and scratch
@@ -160,6 +197,13 @@ class IndexFlat(Index):
         _lib.check(L.knn_last_scan_info(self._h, name, 64, ctypes.byref(qt), ctypes.byref(dt), ctypes.byref(nc), ctypes.byref(grid)))
         return {"kernel": name.value.decode(), "query_tile": qt.value, "db_tile": dt.value, "nchunks": nc.value,
                 "grid": grid.value, "ms": float(L.knn_last_scan_ms(self._h))}
+
+    def last_range(self):
+        """{"query_blocks": blocks of queries the last range search ran in, "redos": rescans of queries whose
+        staging segment overflowed, "redo_queries": queries rescanned}; last_scan() names the range kernel"""
+        qb, redo, rq = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.lib().knn_last_range_info(self._h, ctypes.byref(qb), ctypes.byref(redo), ctypes.byref(rq)))
+        return {"query_blocks": qb.value, "redos": redo.value, "redo_queries": rq.value}
 
     def last_seed(self):
         """{"stride": seed-sample stride of the last search (0: none), "stat_rank": j of a statistical seed
