@@ -258,7 +258,7 @@ int knn_lsh_search(knn_lsh_handle h, const float *q_host, int64_t nq, int64_t k,
                    int64_t *I_host);
 int64_t knn_lsh_ntotal(knn_lsh_handle h);
 int32_t knn_lsh_code_words(knn_lsh_handle h);
-/* codes in FAISS byte order ([ntotal][bytes_per_vec], bit i -> byte i>>3, bit i&7) */
+/* codes in FAISS byte order ([ntotal][bytes_per_vec], bit i -> byte i>>3, bit i&7; bits at and above nbits are 0) */
 int knn_lsh_get_codes(knn_lsh_handle h, uint8_t *out_host, int32_t bytes_per_vec);
 int knn_lsh_add_codes(knn_lsh_handle h, const uint8_t *codes_host, int64_t n, int32_t bytes_per_vec);
 void knn_lsh_free(knn_lsh_handle h);

@@ -287,7 +287,8 @@ extern "C" int knn_lsh_add(knn_lsh_s *h, const float *x_host, int64_t n)
     return 0;
 }
 
-// codes in FAISS byte order: [n][bytes_per_vec], bit i of a row = byte i>>3, bit i&7
+// codes in FAISS byte order: [n][bytes_per_vec], bit i of a row = byte i>>3, bit i&7.  The device codes carry 1 bits from
+// nbits up (the encoder's zero rotation rows: 0 >= 0); FAISS's codes have zeros there, so they are cleared on the way out.
 extern "C" int knn_lsh_get_codes(knn_lsh_s *h, uint8_t *out_host, int32_t bytes_per_vec)
 {
     if (!h || !out_host) return set_err(KNN_ERR_INVALID, "lsh_get_codes: null pointer");
@@ -296,6 +297,15 @@ extern "C" int knn_lsh_get_codes(knn_lsh_s *h, uint8_t *out_host, int32_t bytes_
     if (h->ntotal == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemcpy2D(out_host, (size_t)bytes_per_vec, h->codes, (size_t)h->W * 8, (size_t)bytes_per_vec, (size_t)h->ntotal, hipMemcpyDeviceToHost));
+    if ((int64_t)bytes_per_vec * 8 > h->nbits) {
+        const int b0 = h->nbits >> 3; // (< bytes_per_vec)
+        const uint8_t keep = (uint8_t)((1u << (h->nbits & 7)) - 1);
+        for (int64_t i = 0; i < h->ntotal; i++) {
+            uint8_t *row = out_host + (size_t)i * bytes_per_vec;
+            row[b0] &= keep;
+            memset(row + b0 + 1, 0, (size_t)(bytes_per_vec - b0 - 1));
+        }
+    }
     return 0;
 }
 

@@ -8,8 +8,9 @@ product: torch.matmul in float64 + torch.topk -- with the tie-tolerant rule of o
 within 1e-5 (relative to the magnitudes its fp32 sum is formed from: BASELINE.json's north-star tolerance) of the true
 score of the returned id, no id twice.
 
-The three developer fuzzers (tests/fuzz_*_gpu.py: random shapes / metrics / k / tuning flags / adversarial data against
-the oracle, bit for bit) run a time-bounded batch each, so that the driver's `-m gpu` run executes them too."""
+The four developer fuzzers (tests/fuzz_*_gpu.py: random shapes / metrics / k / tuning flags / adversarial data against
+the oracle -- IndexLSH's against the exact restatement of tests/lsh_reference.py --, bit for bit) run a time-bounded batch
+each, so that the driver's `-m gpu` run executes them too."""
 import sys
 from pathlib import Path
 
@@ -153,7 +154,8 @@ def test_pfam_sized_slice_every_row_against_fp64(gpu_faiss):
     assert np.array_equal(Ib, I[sample]) and np.array_equal(Db.view(np.uint32), D[sample].view(np.uint32)), "a batch of the same queries: the same bits"
 
 
-@pytest.mark.parametrize("which,ncases,budget_s", [("fuzz_gpu", 400, 25.0), ("fuzz_sym_gpu", 60, 20.0), ("fuzz_stream_gpu", 60, 25.0)])
+@pytest.mark.parametrize("which,ncases,budget_s", [("fuzz_gpu", 400, 25.0), ("fuzz_sym_gpu", 60, 20.0), ("fuzz_stream_gpu", 60, 25.0),
+                                                   ("fuzz_lsh_gpu", 300, 20.0)])
 def test_bounded_fuzz_batch(gpu_faiss, which, ncases, budget_s):
     """tests/fuzz_*_gpu.py, a time-bounded batch (seed 4): HIP path vs oracle bit for bit on random shapes, metrics, k, tuning
     flags and adversarial data (ties everywhere, duplicated rows, sorted columns, constant rows, tiny magnitudes)."""

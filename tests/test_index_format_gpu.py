@@ -217,6 +217,37 @@ def test_index_lsh_bytes(gpu_faiss, tmp_path):
     assert I[:, 0].tolist() == [0, 1, 2] and (D[:, 0] == 0).all()
 
 
+def test_index_lsh_bytes_sub_byte_tail(gpu_faiss, tmp_path):
+    """nbits = 13: two code bytes per row, the three bits above nbits zero in the file (FAISS's fvec2bitvec); read ->
+    write round-trips byte for byte, and freshly encoded rows read back with those bits clear as well"""
+    d, nbits, n = 4, 13, 4
+    A = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1], [1, 1, 0, 0], [0, 1, -1, 0], [-1, 0, 0, 1],
+                  [1, -1, 1, -1], [-1, -1, 0, 0], [0, 0, 1, 1], [1, 0, 1, 0], [0, -1, 0, -1], [1, 1, 1, 1]], np.float32)
+    x = np.array([[1, -2, 3, -4], [-1, 2, 0.5, 0.25], [0.1, 0.1, -0.3, 0.2], [0, 0, 0, 0]], np.float32)
+    bits = (x.astype(np.float64) @ A.T.astype(np.float64) >= 0).astype(np.uint8)
+    codes = [int(sum(int(b) << j for j, b in enumerate(row))) for row in bits]
+    assert codes[3] == (1 << nbits) - 1
+    code_bytes = [c >> (8 * i) & 0xFF for c in codes for i in range(2)]
+    expect = fourcc("IxHe") + header(d, n, 1) + struct.pack("<i", nbits) + struct.pack("<BB", 1, 0) + vec("f", []) + struct.pack("<i", 2)
+    expect += fourcc("rrot") + struct.pack("<B", 0) + vec("f", A.reshape(-1).tolist()) + vec("f", []) + struct.pack("<ii", d, nbits) + struct.pack("<B", 1)
+    expect += vec("B", code_bytes)
+    f = tmp_path / "hand_lsh13.index"
+    f.write_bytes(expect)
+    idx = gpu_faiss.read_index(str(f))
+    assert idx.ntotal == n and idx.nbits == nbits and idx.code_size == 2
+    assert idx.codes().reshape(-1).tolist() == code_bytes
+    g = tmp_path / "back_lsh13.index"
+    gpu_faiss.write_index(idx, str(g))
+    assert g.read_bytes() == expect
+    fresh = gpu_faiss.IndexLSH(d, nbits, _rotation=A)
+    fresh.add(x)
+    assert fresh.codes().reshape(-1).tolist() == code_bytes
+    gpu_faiss.write_index(fresh, str(g))
+    assert g.read_bytes() == expect
+    D, I = idx.search(x, 1)
+    assert I[:, 0].tolist() == [0, 1, 2, 3] and (D[:, 0] == 0).all()
+
+
 def test_real_faiss_reads_our_files_and_we_read_its_files(gpu_faiss, tmp_path):
     """Opportunistic: the day the real module is importable, both directions for IxFI / IxF2 / IHNf / IxHe."""
     faiss = pytest.importorskip("faiss", reason="the real faiss module is not installed on this box")
