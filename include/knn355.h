@@ -356,8 +356,23 @@ int knn_last_seed_info(knn_handle h, int32_t *seed_stride, int32_t *stat_rank, i
  *         >= 65 536 rows with long chunks, always under the statistical seed)
  * 524288  the 256 x 256 tile wherever a batch holds more than 128 queries and the index >= 1024 rows, and 256-row tiles in the
  *         symmetric whole-index self-search (tests, A/B)
+ * 1048576  never the exact 16-bit prefilter (knn_flat_set_scan16), A/B
+ * 2097152  the exact 16-bit prefilter wherever it applies, whatever the number of rows (tests; default: from 2^18 rows on)
  * Only 32 changes what a search returns (the other formula's rounding); every other combination returns the same bits. */
 int knn_set_tuning(knn_handle h, int32_t query_tile, int32_t nchunks, int32_t flags);
+
+/* Exact 16-bit prefilter, opt-in per index, before the first add: mode 1 keeps fp16 copies of the rows (d rounded
+ * up to 64 values, one power-of-two exponent per row: +50 % of the fp32 row bytes), rebuilt by every add, knn_flat_reserve,
+ * growth and knn_flat_normalize_rows; views share them (copies that move make earlier views stale, as moved rows do).  Streaming searches (one 32-query tile, inner product, >= 2^18 rows) then scan
+ * the copies, keep every row a rigorous error bound cannot rule out, re-score those with the fp32 chain and return the same
+ * bits as the fp32 scan; a query the bound cannot serve falls back to the fp32 scan on the device.  A row that is not finite
+ * turns the path off until knn_reset.  mode 0 (default) = off.  Not for HNSW indexes (KNN_ERR_UNSUPPORTED).  With
+ * KNN355_SCAN16=0 in the environment mode 1 is ignored. */
+int knn_flat_set_scan16(knn_handle h, int32_t mode);
+/* used = some piece of the last search took the 16-bit prefilter, candidates_max = the most rows any of its queries
+ * re-scored, fallbacks =
+ * prefiltered searches of this handle that fell back to the fp32 scan so far.  Waits for the device. */
+int knn_last_scan16_info(knn_handle h, int32_t *used, int32_t *candidates_max, int64_t *fallbacks);
 
 /* A caller that hands one batch of queries over in pieces (its own blocks, one slice per GPU) says how large the
  * whole batch is: FAISS chooses the squared-L2 formula by the batch ITS caller passed to index.search

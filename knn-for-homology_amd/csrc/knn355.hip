@@ -49,6 +49,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(1))) f32x4 *gptr4; // explicit global (not flat) loads
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #define KEY_PAD 0xFFFFFFFFFFFFFFFFull
 #ifndef KNN355_DIFF_SCALAR_Q
@@ -774,6 +775,13 @@ struct ScanParams {
     int npairs;
     int pool_tiles;     // the last pool_tiles tiles of every pair's range belong to a pool shared by ALL workgroups
     uint32_t *cu_turn;  // [2048] batch launches: one word per CU -- the two resident workgroups take turns in their K loops; NULL: off
+    // 16-bit prefilter (F16X build, see flat_scan_kernel): per-row / per-query power-of-two exponents of the fp16 copies
+    const int8_t *xexp;
+    const int *qexp;
+    // gated launch (the fp32 fallback behind a 16-bit prefiltered search): the kernel returns at once unless one of
+    // gate[0 .. gate_n) is set; NULL: always runs
+    const uint32_t *gate;
+    int gate_n;
     int sparse_epi;     // 128 x 128 batch builds: filter the tiles through the sparse epilogue (thresholds that let a percent of the
                         // scores pass: statistical seed, no seed) instead of filter_tile (exactly seeded scans: almost nothing passes,
                         // its wave-wide early-outs cost next to nothing; the sparse epilogue's fixed 2 us per tile cost a 10 M-row
@@ -1061,10 +1069,23 @@ __device__ __forceinline__ void sched_spread()
 // registers -- 256 of them the wave's 128 x 128 accumulators (AGPRs), 128 KB of LDS for the two staging buffers.  Half the
 // staged bytes per flop of the 128 x 128 tile, a quarter of the K-step barriers and first-fragment waits per flop; nothing
 // else on the CU fills the epilogue's gaps, so this build is for long chunks only (make_plan).
-template <int WM, int WN, int TM, int TN, bool L2, bool NTDB = false, bool SYM = false, bool BF16 = false, int DNQ = 0, int Q16 = 0>
+// F16X: the exact 16-bit prefilter.  The operands are fp16 copies of rows and queries, each scaled by a power
+// of two of its own (xexp / qexp), staged and multiplied like the BF16 build (v_mfma_f32_32x32x16_f16), but with everything
+// of the fp32 streaming build kept: paired walk, pool, tile-minimum seed, parked first tile.  Behind the K loop one ldexp per
+// accumulator register turns the scaled dot products into approximate scores; from there on the build is the fp32 one, run
+// with k' > k.  Its output is the exact top-k' of the APPROXIMATE scores, which the re-scoring tail checks against the
+// error bound and scores exactly (rescore16_kernel).  Inner product, one 32-query tile per launch.
+template <int WM, int WN, int TM, int TN, bool L2, bool NTDB = false, bool SYM = false, bool BF16 = false, int DNQ = 0, int Q16 = 0, bool F16X = false>
 __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel(ScanParams p)
 {
+    if (p.gate) { // (a gated fallback launch: uniform over the workgroup, in front of every barrier)
+        uint32_t any = 0;
+        for (int i = 0; i < p.gate_n; i++) any |= p.gate[i];
+        if (!any) return;
+    }
     constexpr bool DIFF = DNQ > 0; // the difference build, for batches of up to DNQ queries (8, 12, 16 or 20)
+    static_assert(!F16X || (NTDB && !L2 && !SYM && !BF16 && DNQ == 0 && Q16 == 0 && TN == 1), "the 16-bit prefilter: one query tile, inner product");
+    constexpr bool H16 = BF16 || F16X; // 16-bit operands: a staged 128-byte segment holds 64 values
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(!DIFF || (L2 && !SYM && !BF16 && WN == 1 && TN == 1), "the difference build: one 32-query tile, squared L2");
     constexpr bool M16 = Q16 > 0;
@@ -1215,6 +1236,9 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
             big_cokm[b] = __ballot(qok && !(p.skip_mask >= 0 && ((int)(q >> p.vshift) & p.skip_mask) == 0));
         }
     }
+    int f16_qe[NB]; // (F16X) the exponent of this lane's query of each query block
+#pragma unroll
+    for (int b = 0; b < NB; b++) f16_qe[b] = F16X ? p.qexp[min(q0 + (wn * TN + b) * 32 + li, p.nq - 1)] : 0;
     int tile_idx = 0; // tiles this workgroup has walked
     // the tile being walked / the one after it, as tile numbers of the view (-1: none)
     int cur_tile = paired ? (side == 0 ? tile_first : tile_first + n_own - 1) : tile_first;
@@ -1293,6 +1317,9 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
             // (visible after the K loop's barriers) instead of 16 * TM * TN scattered global loads
             // per lane at the end of the tile
             if (tid < DT) s_yn[tid] = p.yn[view_row(min(row0 + tid, p.nb - 1), p.row_mul, p.vshift)];
+        }
+        if constexpr (F16X) { // the rows' exponents, in the slot of the norms (inner product: unused)
+            if (tid < DT) ((int *)s_yn)[tid] = (int)p.xexp[view_row(min(row0 + tid, p.nb - 1), p.row_mul, p.vshift)];
         }
         const bool off_diag = SYM && row0 != q0; // (square tiles: the diagonal tile starts at the query tile's first row)
         // (256 x 256 builds) the queries' thresholds as they stand NOW: an agent-scope load is a round trip to memory, four of
@@ -1479,13 +1506,20 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 for (int b = 0; b < TN; b++)
                     bf[t & 1][b] = *(const f32x4 *)(B + ((wn * TN + b) * 32 + li) * 128 + slot);
             };
-            constexpr int M = BF16 ? TM * TN : 4 * TM * TN; // MFMAs per sub-step
+            constexpr int M = H16 ? TM * TN : 4 * TM * TN; // MFMAs per sub-step
             frag(0);
-            if constexpr (!BF16) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
+            if constexpr (!H16) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
             auto substep = [&](auto t_tag) {
                 constexpr int t = decltype(t_tag)::value;
                 if constexpr (t < 3) frag(t + 1);
-                if constexpr (BF16) {
+                if constexpr (F16X) {
+#pragma unroll
+                    for (int a = 0; a < TM; a++)
+#pragma unroll
+                        for (int b = 0; b < TN; b++)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[t & 1][a]),
+                                                                               __builtin_bit_cast(f16x8, bf[t & 1][b]), acc[a][b], 0, 0, 0);
+                } else if constexpr (BF16) {
 #pragma unroll
                     for (int a = 0; a < TM; a++)
 #pragma unroll
@@ -1523,7 +1557,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 // pin the order: LDS reads of t+1, then the MFMAs of t with the staging
                 // instructions spread between them (left alone, the scheduler sinks the reads
                 // behind the MFMAs to save registers and the wait is exposed)
-                if constexpr (!BF16) { // (the bf16 build is bound by staging, not by the matrix pipe: the compiler's order will do)
+                if constexpr (!H16) { // (the 16-bit builds are bound by staging, not by the matrix pipe: the compiler's order will do)
                     if constexpr (t < 3) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
                     constexpr int nd = n1 - n0, per = M / (nd + 1);
                     static_assert(per >= 1, "more staging instructions than MFMAs in a sub-step");
@@ -1737,6 +1771,17 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 for (int r = 0; r < 16; r++)
                     acc[a][0][r] = li < DIFF_NQ ? sT[li * DT + (wm * TM + a) * 32 + 4 * lh + (r & 3) + 8 * (r >> 2)] : INFINITY;
             __syncthreads();           // (the next tile's prologue stages into these buffers)
+        }
+        if constexpr (F16X) {
+            // acc = <q~, x~> of the scaled fp16 copies; the approximate score is acc * 2^(e_q + e_x) -- exact unless it
+            // falls below the normal range (then off by < 2^-149, which the bound carries)
+#pragma unroll
+            for (int a = 0; a < TM; a++)
+#pragma unroll
+                for (int b = 0; b < TN; b++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++)
+                        acc[a][b][r] = __builtin_ldexpf(acc[a][b][r], f16_qe[b] + ((const int *)s_yn)[rowl(a * 16 + r)]);
         }
         KNN_TRACE(1 + 2 * tile_idx);
         // Two workgroups per CU: behind its K loop a wave's instructions run beside the MFMAs of the OTHER workgroup's wave on
@@ -2612,6 +2657,10 @@ struct SelectParams {
     int64_t seed_nslots;  // threshold slots of the enclosing search (>= nq: the last query tile is padded)
     const uint32_t *qthr; // verification: a k-th score word above qthr[q] means the statistical threshold was too tight
     int *fail;
+    // gated launch (see ScanParams::gate); gate_count: counts the launches that ran (the fallbacks taken)
+    const uint32_t *gate;
+    int gate_n;
+    uint32_t *gate_count;
 };
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t x)
@@ -2641,6 +2690,12 @@ template <int R, int NT, bool SEED>
 __global__ __launch_bounds__(NT) void select_topk_kernel(SelectParams p)
 {
     constexpr int NW = NT / 64;
+    if (p.gate) { // (uniform, in front of every barrier)
+        uint32_t any = 0;
+        for (int i = 0; i < p.gate_n; i++) any |= p.gate[i];
+        if (!any) return;
+        if (p.gate_count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(p.gate_count, 1u);
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t *sb = (uint64_t *)smem; // [P] survivors, sorted in place (final mode)
     __shared__ int s_red[2][NW];
@@ -2928,8 +2983,14 @@ __global__ __launch_bounds__(NT) void select_topk_kernel(SelectParams p)
 __global__ void init_level_kernel(uint32_t *__restrict__ gthr, int64_t nslots, uint32_t *__restrict__ qcnt,
                                   uint32_t *__restrict__ qthr, int64_t nq, int *__restrict__ flag,
                                   uint64_t *__restrict__ pub = nullptr, int64_t npub = 0, uint32_t *__restrict__ arrive = nullptr,
-                                  int64_t narrive = 0, uint32_t *__restrict__ pair_ctr = nullptr, int64_t npairs = 0)
+                                  int64_t narrive = 0, uint32_t *__restrict__ pair_ctr = nullptr, int64_t npairs = 0,
+                                  const uint32_t *__restrict__ gate = nullptr, int gate_n = 0)
 {
+    if (gate) { // (a gated fallback launch, see ScanParams::gate)
+        uint32_t any = 0;
+        for (int j = 0; j < gate_n; j++) any |= gate[j];
+        if (!any) return;
+    }
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (pair_ctr) // paired walk: tickets 0 and 1 are the two workgroups' first tiles
         for (int64_t j = i; j <= npairs; j += (int64_t)gridDim.x * blockDim.x) pair_ctr[j] = j < npairs ? 2u : 0u; // ([npairs]: the pool's)
@@ -2975,6 +3036,171 @@ __global__ void pair_distance_kernel(const float *__restrict__ xb, const float *
         acc = v < 0.0f ? 0.0f : v;
     }
     out[pidx] = acc;
+}
+
+
+// ---------------------------------------------------------------------------
+// exact 16-bit prefilter: fp16 copies with power-of-two scales, the error bound, the re-scoring tail
+// ---------------------------------------------------------------------------
+// index-wide statistics of the fp16 copies (uint32 words): R = max |x - x'|, X' = max |x'|, X = max |x| (float bits, rounded
+// up), the largest row exponent (int), "a row holds a value that is not finite"
+enum { S16_R = 0, S16_XP = 1, S16_X = 2, S16_EMAX = 3, S16_NONFINITE = 4, S16_NSTAT = 8 };
+
+// a float >= v (v >= 0): a relative margin of 2^-20, rounded to float, one step up
+__device__ __forceinline__ float s16_up(double v)
+{
+    const float f = (float)(v * (1.0 + 0x1p-20));
+    return nextafterf(f, INFINITY);
+}
+
+// One wave converts one vector of n fp32 values (zeros from n to np16): y = fp16(x * 2^-e) with max|x| * 2^-e in [2^13, 2^14)
+// (e >= emin), scaled values below the fp16 normal range stored as 0 -- no 16-bit subnormals.  Returns e; *nx, *nxp, *nd: the
+// Euclidean norms of x, of x' = 2^e y and of x - x' (in double, every lane gets them); *bad: a value is not finite.
+__device__ __forceinline__ int s16_convert(const float *__restrict__ x, int n, int np16, _Float16 *__restrict__ y, int emin, int lane,
+                                           double *nx, double *nxp, double *nd, bool *bad)
+{
+    float mx = 0.0f;
+    bool nf = false;
+    for (int i = lane; i < n; i += 64) {
+        const float v = x[i];
+        nf |= !isfinite(v);
+        mx = fmaxf(mx, fabsf(v));
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    *bad = __ballot(nf) != 0ull;
+    int e = (mx > 0.0f && isfinite(mx)) ? ilogbf(mx) - 13 : 0;
+    e = max(e, emin);
+    double sx = 0.0, sxp = 0.0, sd = 0.0;
+    for (int i = lane; i < np16; i += 64) {
+        const float v = i < n ? x[i] : 0.0f;
+        _Float16 h = (_Float16)ldexpf(v, -e);
+        if (!(fabsf((float)h) >= 0x1p-14f)) h = (_Float16)0.0f;
+        y[i] = h;
+        const double xp = ldexp((double)(float)h, e), dv = (double)v;
+        sx += dv * dv;
+        sxp += xp * xp;
+        sd += (dv - xp) * (dv - xp);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        sx += __shfl_xor(sx, o, 64);
+        sxp += __shfl_xor(sxp, o, 64);
+        sd += __shfl_xor(sd, o, 64);
+    }
+    *nx = sqrt(sx);
+    *nxp = sqrt(sxp);
+    *nd = sqrt(sd);
+    return e;
+}
+
+// rows [r0, r0 + n) of the index -> fp16 copies [.][dp16] + exponents; their norms go into the statistics.  One wave per row.
+__global__ __launch_bounds__(256) void scan16_rows_kernel(const float *__restrict__ xb, int dp, int64_t r0, int64_t n, int dp16,
+                                                          _Float16 *__restrict__ xs, int8_t *__restrict__ xexp, uint32_t *__restrict__ stat)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t r = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= r0 + n) return;
+    double nx, nxp, nd;
+    bool bad;
+    const int e = s16_convert(xb + (size_t)r * dp, dp, dp16, xs + (size_t)r * dp16, -128, lane, &nx, &nxp, &nd, &bad);
+    if (lane == 0) {
+        xexp[r] = (int8_t)e; // (in [-128, 114]: ilogb of a finite float is at most 127)
+        if (bad) {
+            atomicOr(&stat[S16_NONFINITE], 1u);
+        } else {
+            atomicMax(&stat[S16_R], __float_as_uint(s16_up(nd)));
+            atomicMax(&stat[S16_XP], __float_as_uint(s16_up(nxp)));
+            atomicMax(&stat[S16_X], __float_as_uint(s16_up(nx)));
+            atomicMax((int *)&stat[S16_EMAX], e);
+        }
+    }
+}
+
+// Per search: the fp16 queries + exponents, and each query's bound B_q >= |s - s~| over every row:
+//   B_q = |q| R + |q - q'| X' + g(dp, u) |q| X + g(dp16, 4u) |q'| X' + 2^-140,   g(n, v) = n v / (1 - n v), u = 2^-24
+// (the contract's fmaf chain; the f16 MFMA's fp32 accumulation, allowed four times the error of a round-to-nearest add; the
+// ldexp of a score below the normal range).  fail[q] = 1 sends the search to its fp32 fallback: a query value or the bound is
+// not finite, an exponent sum could overflow a score, a row is not finite.  One wave per query.
+__global__ __launch_bounds__(64) void scan16_queries_kernel(const float *__restrict__ xq, int dp, int dp16, _Float16 *__restrict__ q16,
+                                                            int *__restrict__ qexp, float *__restrict__ Bq, uint32_t *__restrict__ fail,
+                                                            const uint32_t *__restrict__ stat, uint32_t *__restrict__ sstat, int first)
+{
+    const int lane = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    double nq, nqp, nd;
+    bool bad;
+    const int e = s16_convert(xq + (size_t)q * dp, dp, dp16, q16 + (size_t)q * dp16, -100000, lane, &nq, &nqp, &nd, &bad);
+    if (lane == 0) {
+        const double R = __uint_as_float(stat[S16_R]), Xp = __uint_as_float(stat[S16_XP]), X = __uint_as_float(stat[S16_X]);
+        const double u = 0x1p-24, g1 = dp * u / (1.0 - dp * u), g2 = dp16 * 4.0 * u / (1.0 - dp16 * 4.0 * u);
+        const double B = nq * R + nd * Xp + g1 * nq * X + g2 * nqp * Xp + 0x1p-140;
+        const float Bf = s16_up(B);
+        qexp[q] = e;
+        Bq[q] = Bf;
+        fail[q] = (bad || !isfinite(Bf) || (int64_t)e + (int)stat[S16_EMAX] > 80 || stat[S16_NONFINITE]) ? 1u : 0u;
+        if (q == 0 && first) sstat[0] = 0u; // (the largest window of this search -- its first prefiltered piece -- see rescore16_kernel)
+    }
+}
+
+// The tail of a 16-bit prefiltered search, one workgroup per query.  ak[q]: the exact top-kp of the approximate keys, sorted.
+// With t = the k-th of them and B = B_q, every row of the exact top-k has an approximate score <= t + 2B; all those rows are
+// among the kp if the kp-th approximate score is above t + 2B (or the kp hold fewer real rows) -- otherwise fail[q] = 1 and the
+// gated fp32 search behind this launch redoes the search.  The rows inside the window are scored with the contract's chain
+// (pair_distance_kernel's order) into exact keys ok[q][0 .. kp) (KEY_PAD elsewhere); their top-k is the search's result.
+__global__ __launch_bounds__(256) void rescore16_kernel(const uint64_t *__restrict__ ak, int kp, int k, const float *__restrict__ Bq,
+                                                        const uint32_t *__restrict__ pfail, uint32_t *__restrict__ fail,
+                                                        const float *__restrict__ xb, int dp, const float *__restrict__ xq, uint32_t id_base,
+                                                        uint64_t *__restrict__ ok, uint32_t *__restrict__ sstat)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float *sq = (float *)smem; // [dp] the query
+    __shared__ int s_fail, s_cnt;
+    __shared__ double s_lim;
+    const int tid = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    for (int i = tid; i < dp; i += 256) sq[i] = xq[(size_t)q * dp + i];
+    const uint64_t *a = ak + (size_t)q * kp;
+    if (tid == 0) {
+        int f = pfail[q] != 0u;
+        double lim = INFINITY;
+        const uint64_t tk = a[k - 1], last = a[kp - 1];
+        if (!f && tk != KEY_PAD) {
+            lim = (double)ord2f((uint32_t)(tk >> 32)) + 2.0 * (double)Bq[q];
+            if (last != KEY_PAD && !(lim < (double)ord2f((uint32_t)(last >> 32)))) f = 1;
+        }
+        s_fail = f;
+        s_lim = lim;
+        s_cnt = 0;
+        fail[q] = (uint32_t)f;
+    }
+    __syncthreads();
+    const bool f = s_fail != 0;
+    const double lim = s_lim;
+    int cnt = 0;
+    for (int j = tid; j < kp; j += 256) {
+        const uint64_t key = a[j];
+        uint64_t out = KEY_PAD;
+        if (!f && key != KEY_PAD && (double)ord2f((uint32_t)(key >> 32)) <= lim) {
+            const float *y = xb + (size_t)((uint32_t)key - id_base) * dp;
+            float acc = 0.0f;
+#pragma unroll 4
+            for (int k0 = 0; k0 < dp; k0 += 8) {
+                const f32x4 q0 = *(const f32x4 *)(sq + k0), q1 = *(const f32x4 *)(sq + k0 + 4);
+                const f32x4 y0 = *(const f32x4 *)(y + k0), y1 = *(const f32x4 *)(y + k0 + 4);
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    acc = __builtin_fmaf(q0[m], y0[m], acc);
+                    acc = __builtin_fmaf(q1[m], y1[m], acc);
+                }
+            }
+            const float v = -acc + 0.0f;
+            out = ((uint64_t)f2ord(v) << 32) | (uint32_t)key;
+            cnt++;
+        }
+        ok[(size_t)q * kp + j] = out;
+    }
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (tid == 0 && !f) atomicMax(&sstat[0], (uint32_t)s_cnt);
 }
 
 // ===========================================================================
@@ -3163,6 +3389,27 @@ struct knn_index_s {
     bool approx16 = false;  // the scan multiplies bf16 copies of rows and queries (HNSW's coarse entry index: approximate on purpose)
     bool keep16 = false;    // bf16 copies of the rows are kept beside the fp32 ones (HNSW storage: the beam walks on them); scans stay fp32
     DevBuf xb16, ws_q16;    // approx16: [cap_rows][dp] bf16 rows, [nq][dp] bf16 queries
+    // exact 16-bit prefilter (knn_flat_set_scan16): fp16 copies of the rows, [cap_rows][dp16] (dp16 = d rounded
+    // up to 64), one int8 exponent per row, the index-wide statistics (S16_*).  Views use their parent's.
+    int scan16 = 0;               // 0 off, 1 copies kept, 2 dropped (allocation failed) until the index is reset
+    // the copies cover every row and every row is finite -- shared with the views, so a row added to the parent that is not
+    // finite turns the path off for them too
+    std::shared_ptr<std::atomic<bool>> s16_ok = std::make_shared<std::atomic<bool>>(false);
+    int dp16 = 0;
+    DevBuf s16_rows_buf, s16_exp_buf, s16_stat_buf;
+    const _Float16 *s16_rows = nullptr;
+    const int8_t *s16_exp = nullptr;
+    const uint32_t *s16_stat = nullptr;
+    std::string s16_note;
+    // while a prefiltered search is being enqueued: 1 = its 16-bit pass, 2 = its gated fp32 fallback (search_view_s16)
+    int s16_mode = 0;
+    const int *s16_qexp = nullptr;
+    const uint32_t *s16_gate = nullptr;
+    int s16_gate_n = 0;
+    uint32_t *s16_gate_count = nullptr;
+    DevBuf ws_q16x, ws_s16q, ws_s16ak, ws_s16ok, ws_s16stat; // fp16 queries; exponents, bounds, flags; keys; [largest window, fallbacks]
+    bool last_s16_used = false;   // some piece of the last search (search_keys_impl) took the prefilter
+    int s16_pieces = 0;           // ... how many: the first one restarts the largest-window counter
     float *yn = nullptr; // [cap_rows + pad]
     size_t xb_bytes = 0, yn_bytes = 0; // allocation sizes (may exceed the row capacity: pooled)
     hipStream_t stream = nullptr;
@@ -3382,6 +3629,13 @@ extern "C" int knn_flat_view(knn_handle parent, knn_handle *out)
     h->yn = parent->yn;
     h->ntotal = parent->ntotal;
     h->cap_rows = parent->ntotal;
+    h->scan16 = parent->scan16;
+    h->dp16 = parent->dp16;
+    h->s16_rows = parent->s16_rows;
+    h->s16_exp = parent->s16_exp;
+    h->s16_stat = parent->s16_stat;
+    h->s16_ok = parent->s16_ok;
+    h->s16_note = parent->s16_note;
     if (!(h->stream = g_streams.take(h->device))) {
         delete h;
         return set_err(KNN_ERR_HIP, "flat_view: stream creation failed");
@@ -3406,6 +3660,16 @@ static void free_index_buffers(knn_index_s *h)
     if (!h->is_view) h->storage_gen->fetch_add(1);
     if (h->xb && !h->is_view) g_pool.give(h->xb, h->xb_bytes, h->device);
     if (h->yn && !h->is_view) g_pool.give(h->yn, h->yn_bytes, h->device);
+    if (!h->is_view) {
+        h->s16_rows_buf.release();
+        h->s16_exp_buf.release();
+        h->s16_stat_buf.release();
+        if (h->scan16 == 2) h->scan16 = 1; // (dropped copies are tried again from the next add on)
+    }
+    h->s16_rows = nullptr;
+    h->s16_exp = nullptr;
+    h->s16_stat = nullptr;
+    if (!h->is_view) h->s16_ok->store(false);
     h->xb = nullptr;
     h->yn = nullptr;
     h->ntotal = 0;
@@ -3420,7 +3684,8 @@ extern "C" void knn_free(knn_handle h)
         if (!h->is_view && h->xb) (void)hipDeviceSynchronize(); // a view's stream may still be scanning these rows
         free_index_buffers(h);
         DevBuf *bufs[] = {&h->xb16, &h->ws_q16, &h->ws_sym, &h->ws_qdiff, &h->ws_defer, &h->ws_turn, &h->ws_flag, &h->ws_q, &h->ws_qn, &h->ws_lists, &h->ws_D, &h->ws_I, &h->ws_tmp, &h->ws_tmp2, &h->ws_D1, &h->ws_I1, &h->ws_tmp3,
-                          &h->ws_rq, &h->ws_rqn, &h->ws_rcnt, &h->ws_rsegD, &h->ws_rsegI, &h->ws_roff, &h->ws_routD, &h->ws_routI, &h->ws_rsel, &h->ws_rq2, &h->ws_rexp};
+                          &h->ws_rq, &h->ws_rqn, &h->ws_rcnt, &h->ws_rsegD, &h->ws_rsegI, &h->ws_roff, &h->ws_routD, &h->ws_routI, &h->ws_rsel, &h->ws_rq2, &h->ws_rexp,
+                          &h->ws_q16x, &h->ws_s16q, &h->ws_s16ak, &h->ws_s16ok, &h->ws_s16stat};
         for (DevBuf *b : bufs) b->release();
         for (LevelBufs &b : h->ws_level) {
             b.qlist.release();
@@ -3513,10 +3778,58 @@ static int approx16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t
     return 0;
 }
 
+// fp16 copies of rows [r0, r0 + n) for the exact 16-bit prefilter.  Storage that has to grow is rebuilt from all
+// rows, and r0 = 0 restarts the index-wide statistics.  Copies that cannot be allocated are dropped: the index goes on with its
+// fp32 scans.  Waits for the stream (adds are synchronous): whether every row is finite decides whether searches may use them.
+// Called with n = 0 by knn_flat_reserve: the copies grow with the fp32 rows.  Copies that move (or are dropped) make every
+// view of the index stale, as moved fp32 rows do: a view holds their addresses.
+static int scan16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s)
+{
+    if (h->scan16 != 1 || h->is_view) return 0;
+    const size_t need = (size_t)h->cap_rows * h->dp16 * 2;
+    if (h->cap_rows > 0 && (h->s16_rows_buf.bytes < need || h->s16_exp_buf.bytes < (size_t)h->cap_rows || !h->s16_stat_buf.p)) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h->s16_rows_buf.p || h->s16_exp_buf.p) {
+            h->storage_gen->fetch_add(1); // (views of the old copies are dead ...)
+            (void)hipDeviceSynchronize(); // (... and nothing may still be scanning them: ensure() below hands them back to the pool)
+        }
+        if (h->s16_rows_buf.ensure(need) || h->s16_exp_buf.ensure((size_t)h->cap_rows) || h->s16_stat_buf.ensure(S16_NSTAT * 4)) {
+            h->s16_rows_buf.release();
+            h->s16_exp_buf.release();
+            h->s16_stat_buf.release();
+            h->s16_rows = nullptr;
+            h->s16_exp = nullptr;
+            h->s16_stat = nullptr;
+            h->s16_ok->store(false);
+            h->scan16 = 2;
+            h->s16_note = "dropped: no device memory for the fp16 copies";
+            return 0;
+        }
+        n += r0;
+        r0 = 0;
+    }
+    if (n <= 0) return 0;
+    h->s16_rows = (const _Float16 *)h->s16_rows_buf.p;
+    h->s16_exp = (const int8_t *)h->s16_exp_buf.p;
+    h->s16_stat = (const uint32_t *)h->s16_stat_buf.p;
+    uint32_t init[S16_NSTAT] = {0u, 0u, 0u, 0x80000000u, 0u, 0u, 0u, 0u}; // (largest exponent: INT_MIN)
+    if (r0 == 0) HIP_TRY(hipMemcpyAsync(h->s16_stat_buf.p, init, sizeof init, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(scan16_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->xb, h->dp, r0, n, h->dp16,
+                       (_Float16 *)h->s16_rows_buf.p, (int8_t *)h->s16_exp_buf.p, (uint32_t *)h->s16_stat_buf.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t nonfinite = 0;
+    HIP_TRY(hipMemcpyAsync(&nonfinite, (const uint32_t *)h->s16_stat_buf.p + S16_NONFINITE, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->s16_ok->store(nonfinite == 0);
+    h->s16_note = nonfinite ? "off: a row holds a value that is not finite" : "on";
+    return 0;
+}
+
 // before the first add: the index multiplies bf16 copies (rows padded to a multiple of 64 values)
 static int flat_set_approx16(knn_index_s *h)
 {
     if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "approx16: the index already holds rows");
+    if (h->scan16) return set_err(KNN_ERR_UNSUPPORTED, "approx16: the index keeps fp16 copies for the 16-bit prefilter");
     h->approx16 = true;
     h->dp = round_up(h->d, 64);
     return 0;
@@ -3526,6 +3839,7 @@ static int flat_set_approx16(knn_index_s *h)
 static int flat_keep16(knn_index_s *h)
 {
     if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "keep16: the index already holds rows");
+    if (h->scan16) return set_err(KNN_ERR_UNSUPPORTED, "keep16: the index keeps fp16 copies for the 16-bit prefilter");
     h->keep16 = true;
     return 0;
 }
@@ -3546,6 +3860,8 @@ static int add_dev_impl(knn_index_s *h, const float *x_dev, int64_t n, hipStream
     int rc = norms_dev_impl(dst, n, h->d, h->dp, h->yn + h->ntotal, s);
     if (rc) return rc;
     rc = approx16_sync_rows(h, h->ntotal, n, s);
+    if (rc) return rc;
+    rc = scan16_sync_rows(h, h->ntotal, n, s);
     if (rc) return rc;
     h->ntotal += n;
     return 0;
@@ -3589,6 +3905,8 @@ extern "C" int knn_flat_add(knn_handle h, const float *x_host, int64_t n)
         rc = norms_dev_impl(dst, n, h->d, h->dp, h->yn + h->ntotal, h->stream);
         if (rc) return rc;
         rc = approx16_sync_rows(h, h->ntotal, n, h->stream);
+        if (rc) return rc;
+        rc = scan16_sync_rows(h, h->ntotal, n, h->stream);
         if (rc) return rc;
         h->ntotal += n;
     } else {
@@ -3669,6 +3987,7 @@ static int launch_select(SelectParams sp, hipStream_t s, DevBuf *tmp = nullptr)
         a.seg_len = KNN_SELECT_SEG; a.nseg = nseg;
         a.nq = sp.nq; a.k = kk; a.metric = sp.metric;
         a.out_keys = (uint64_t *)tmp->p; a.out_stride = kk; a.out_fill = 0;
+        a.gate = sp.gate; a.gate_n = sp.gate_n;
         const size_t lds = (size_t)next_pow2_host(kk + std::max(kk >> 2, 32)) * 8;
         hipLaunchKernelGGL((select_topk_kernel<32, 1024, false>), dim3((unsigned)sp.nq, (unsigned)nseg), dim3(1024), lds, s, a);
         HIP_TRY(hipGetLastError());
@@ -3736,6 +4055,17 @@ static int launch_scan_cfg(const knn_index_s *h, const ScanParams &p, const Scan
 {
     const bool l2 = h->metric == KNN_METRIC_L2;
     void (*kern)(ScanParams) = nullptr;
+    if (h->s16_mode == 1) { // the 16-bit pass of a prefiltered search (search_view_s16)
+        if constexpr (WM == 4 && WN == 1 && TM == 2 && TN == 1) {
+            if (p.nqtiles != 1 || l2) return set_err(KNN_ERR_INVALID, "scan: the 16-bit prefilter serves one 32-query tile, inner product");
+            kern = flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>;
+            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+            hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
+        return set_err(KNN_ERR_INVALID, "scan: the 16-bit prefilter has the 32-query build only");
+    }
     // one query tile: rows are read once, non-temporal staging loads
     if constexpr (WM == 4 && TM == 2) {
         if (plan.diff) {
@@ -3767,7 +4097,7 @@ static int launch_scan_cfg(const knn_index_s *h, const ScanParams &p, const Scan
 // the 256 x 256 tile (2 x 2 waves of 4 x 4 MFMA tiles, one workgroup per CU): plain fp32 rows, several query tiles per launch
 static int launch_scan_big(const knn_index_s *h, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
 {
-    if (h->approx16) return set_err(KNN_ERR_INVALID, "scan: the 256-query tile serves plain fp32 rows");
+    if (h->approx16 || h->s16_mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 256-query tile serves plain fp32 rows");
     void (*kern)(ScanParams) = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 4, 4, true, false> : flat_scan_kernel<2, 2, 4, 4, false, false>;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
@@ -3779,7 +4109,7 @@ static int launch_scan_big(const knn_index_s *h, const ScanParams &p, const Scan
 template <int WM, int WN, int TM, int Q16>
 static int launch_scan16(const knn_index_s *h, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
 {
-    if (p.nqtiles != 1 || h->approx16) return set_err(KNN_ERR_INVALID, "scan: the 16-query-block builds serve one query tile of plain fp32 rows");
+    if (p.nqtiles != 1 || h->approx16 || h->s16_mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 16-query-block builds serve one query tile of plain fp32 rows");
     void (*kern)(ScanParams) = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<WM, WN, TM, 1, true, true, false, false, 0, Q16>
                                                           : flat_scan_kernel<WM, WN, TM, 1, false, true, false, false, 0, Q16>;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
@@ -3949,12 +4279,93 @@ struct SearchOut {
     int64_t seed_nslots = 0;
 };
 
+// ---- the exact 16-bit prefilter ----------------------------------------------------------------------------
+static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int row_mul,
+                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag = nullptr);
+
+// knn_set_tuning flags: never the 16-bit prefilter (A/B) / wherever it applies, whatever the number of rows (tests)
+static const int KNN_FLAG_S16_NEVER = 1 << 20, KNN_FLAG_S16_ANY_NB = 1 << 21;
+// approximate keys the 16-bit pass hands to the re-scoring tail: room for the window above the k-th (fp16 on normalised
+// rows: a few percent of k beyond it at 10 M rows, k = 100)
+static int s16_kprime(int k) { return std::min(KNN_WAVE_SELECT_MAX_K, std::max(2 * k, k + 64)); }
+
+// Does a search of the view take the prefiltered path?  A one-query-tile streaming search (the 32-query build) by inner
+// product over an index whose fp16 copies cover every row, from nb >= 2^18 rows on (below that the fp32 scan's fixed costs
+// dominate and the tail's launches would not pay).  Batch, symmetric, difference, HNSW and range searches never do.
+static bool s16_eligible(const knn_index_s *h, int64_t nb, int64_t nq, int k, int row_mul, int level, const SearchOut &out)
+{
+    if (h->scan16 != 1 || !h->s16_ok->load() || !h->s16_rows || h->s16_mode || level != 0 || row_mul != 1 || out.seed_cnt) return false;
+    if (h->metric != KNN_METRIC_INNER_PRODUCT || h->approx16 || (h->flags & KNN_FLAG_S16_NEVER)) return false;
+    if (nq < 1 || nq > 32 || (h->force_qt != 0 && h->force_qt != 32) || s16_kprime(k) <= k) return false; // (k' = k: no room for a window)
+    if ((size_t)h->dp * 4 + 64 > 65536) return false; // (rescore16_kernel holds the query in LDS, no opt-in beyond 64 KB)
+    return nb >= (1 << 18) || (h->flags & KNN_FLAG_S16_ANY_NB);
+}
+
+// One prefiltered search, six launches on the caller's stream, no host wait:
+//   scan16_queries_kernel   fp16 queries, exponents, bounds B_q, the per-query fallback flags
+//   16-bit pass             the streaming scan machinery on the fp16 copies with k' = s16_kprime(k): the exact top-k'
+//                           of the approximate scores (state reset, flat_scan_q32_d256_f16x, selection)
+//   rescore16_kernel        the window check and the exact scores of the rows inside the window
+//   selection               the exact top-k of those -> D / I or keys, exactly as the fp32 search writes them
+//   gated fp32 search       state reset, scan, selection of the plain search, each returning at once unless some query's
+//                           flag is set -- then it overwrites the output with the plain search's bits
+static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int vshift,
+                           const SearchOut &out, hipStream_t s, int *reset_flag)
+{
+    const int kp = s16_kprime(k);
+    if (h->ws_q16x.ensure((size_t)nq * h->dp16 * 2, h->done, s) || h->ws_s16q.ensure((size_t)nq * 16, h->done, s) ||
+        h->ws_s16ak.ensure((size_t)nq * kp * 8, h->done, s) || h->ws_s16ok.ensure((size_t)nq * kp * 8, h->done, s))
+        return set_err(KNN_ERR_HIP, "search: out of device memory");
+    if (!h->ws_s16stat.p) {
+        if (h->ws_s16stat.ensure(16)) return set_err(KNN_ERR_HIP, "search: out of device memory");
+        HIP_TRY(hipMemsetAsync(h->ws_s16stat.p, 0, 16, s));
+    }
+    _Float16 *q16 = (_Float16 *)h->ws_q16x.p;
+    int *qexp = (int *)h->ws_s16q.p;
+    float *Bq = (float *)(qexp + nq);
+    uint32_t *pfail = (uint32_t *)(Bq + nq), *rfail = pfail + nq;
+    uint32_t *sstat = (uint32_t *)h->ws_s16stat.p;
+    hipLaunchKernelGGL(scan16_queries_kernel, dim3((unsigned)nq), dim3(64), 0, s, q_dev, h->dp, h->dp16, q16, qexp, Bq, pfail, h->s16_stat, sstat,
+                       h->s16_pieces == 0 ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    SearchOut ao;
+    ao.keys = (uint64_t *)h->ws_s16ak.p; ao.keys_stride = kp; ao.keys_fill = 0;
+    h->s16_mode = 1;
+    h->s16_qexp = qexp;
+    int rc = search_view(h, (const float *)q16, nullptr, nq, kp, id_base, 1, vshift, 0, ao, false, s, reset_flag);
+    h->s16_mode = 0;
+    if (rc) return rc;
+    hipLaunchKernelGGL(rescore16_kernel, dim3((unsigned)nq), dim3(256), (size_t)h->dp * 4, s, (const uint64_t *)h->ws_s16ak.p, kp, k, Bq, pfail, rfail,
+                       h->xb, h->dp, q_dev, id_base, (uint64_t *)h->ws_s16ok.p, sstat);
+    HIP_TRY(hipGetLastError());
+    SelectParams sp = {};
+    sp.in = (const uint64_t *)h->ws_s16ok.p; sp.in_stride = kp; sp.n_fixed = kp; sp.cap = kp; sp.n_expect = kp;
+    sp.nq = nq; sp.k = k; sp.metric = h->metric;
+    sp.out_keys = out.keys; sp.out_stride = out.keys ? out.keys_stride : 0; sp.out_fill = out.keys_fill;
+    sp.D = out.D; sp.I = out.I;
+    rc = launch_select(sp, s);
+    if (rc) return rc;
+    h->s16_mode = 2;
+    h->s16_gate = rfail;
+    h->s16_gate_n = (int)nq;
+    h->s16_gate_count = sstat + 1;
+    rc = search_view(h, q_dev, xn, nq, k, id_base, 1, vshift, 0, out, false, s, nullptr);
+    h->s16_mode = 0;
+    h->s16_gate = nullptr;
+    h->s16_gate_n = 0;
+    h->s16_gate_count = nullptr;
+    h->last_s16_used = true;
+    h->s16_pieces++;
+    return rc;
+}
+
 // Exact top-k of the block-strided view (view_row) with stride row_mul / block shift vshift for
 // queries [nq][dp] on the device.  allow_stat: the caller checks h->ws_flag afterwards.
 static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int row_mul,
-                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag = nullptr)
+                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag)
 {
     const int64_t nb = view_rows(h->ntotal, row_mul, vshift);
+    if (s16_eligible(h, nb, nq, k, row_mul, level, out)) return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
     ScanPlan pl;
     const bool allow_pairs = !h->approx16; // (the bf16 build has no one-query-tile streaming case worth pairing)
     // (the 256 x 256 tile needs the statistical seed -- see below -- so only callers that can check its verification flag get it)
@@ -4050,6 +4461,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
             }
         }
     }
+    if (h->s16_mode == 2 && !pub_rounds) sstride = 0; // (a gated fallback runs no sample pass: its memsets could not be gated)
     if (pub_rounds) {
         sstride = 0;
         // the bound sits near the k / (publications x tile rows) quantile; the first tile(s) of every chunk are filtered
@@ -4102,7 +4514,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         if (pl.npairs && lb.pair_ctr.ensure(((size_t)pl.npairs + 1) * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         // A streaming search whose predecessor on this handle had exactly this shape finds the state already reset: that
         // search's final selection did it (SelectParams::rs_*) -- one launch and a ~10 us launch gap less per step.
-        if (pub_rounds && pl.npairs && !(h->flags & 64)) {
+        if (pub_rounds && pl.npairs && !(h->flags & 64) && !h->s16_mode) { // (not inside a prefiltered search: its two passes differ in shape)
             uint64_t sig = 0x9E3779B97F4A7C15ull;
             const uint64_t parts[] = {(uint64_t)nslots, (uint64_t)nq, (uint64_t)npub, (uint64_t)pl.nqtiles, (uint64_t)pl.npairs, (uint64_t)(uintptr_t)gthr,
                                       (uint64_t)(uintptr_t)qcnt, (uint64_t)(uintptr_t)qthr, (uint64_t)(uintptr_t)pub, (uint64_t)(uintptr_t)arrive,
@@ -4112,7 +4524,8 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         }
         if (!(reset_sig && lb.clean_sig == reset_sig)) {
             hipLaunchKernelGGL(init_level_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, gthr, (int64_t)nslots, qcnt, qthr, nq,
-                               reset_flag, pub, npub, arrive, (int64_t)pl.nqtiles, pl.npairs ? (uint32_t *)lb.pair_ctr.p : nullptr, (int64_t)pl.npairs);
+                               reset_flag, pub, npub, arrive, (int64_t)pl.nqtiles, pl.npairs ? (uint32_t *)lb.pair_ctr.p : nullptr, (int64_t)pl.npairs,
+                               h->s16_mode == 2 ? h->s16_gate : nullptr, h->s16_gate_n);
             HIP_TRY(hipGetLastError());
         }
         lb.clean_sig = 0; // (until this search's own selection has been enqueued)
@@ -4129,6 +4542,15 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     if (h->approx16) { // bf16 rows and queries: a row is dp / 2 four-byte units
         p.xb = (const float *)h->xb16.p;
         p.dp = h->dp / 2;
+    }
+    if (h->s16_mode == 1) { // the 16-bit pass: fp16 rows and queries (q_dev), a row is dp16 / 2 four-byte units
+        p.xb = (const float *)h->s16_rows;
+        p.dp = h->dp16 / 2;
+        p.xexp = h->s16_exp;
+        p.qexp = h->s16_qexp;
+    } else if (h->s16_mode == 2) {
+        p.gate = h->s16_gate;
+        p.gate_n = h->s16_gate_n;
     }
     p.nqtiles = pl.nqtiles; p.nchunks = pl.nchunks; p.tiles_base = pl.tiles_base; p.tiles_rem = pl.tiles_rem;
     p.lists = (uint64_t *)h->ws_lists.p; p.gthr = gthr;
@@ -4173,7 +4595,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         if (h->ws_defer.ensure((size_t)pl.grid * pl.qt * pl.dt * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         p.defer = (float *)h->ws_defer.p;
     }
-    const bool top = level == 0;
+    const bool top = level == 0 && h->s16_mode != 2; // (a gated fallback leaves the introspection to the 16-bit pass)
 #ifdef KNN355_TRACE
     if (level == (getenv("KNN355_TRACE_LEVEL") ? atoi(getenv("KNN355_TRACE_LEVEL")) : 0)) { // (developer build: which seed level's launch is stamped)
         if (g_trace_buf.ensure((size_t)pl.grid * 128 * 8)) return set_err(KNN_ERR_HIP, "trace: out of device memory");
@@ -4203,7 +4625,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     if (rc) return rc;
     if (top) {
         HIP_TRY(hipEventRecord(h->ev1, s));
-        h->last_kernel = pl.name; h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
+        h->last_kernel = h->s16_mode == 1 ? std::string(pl.name) + "_f16x" : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
         h->last_seed_stride = pub_rounds ? -pub_rounds * pub_m : sstride; // (negative: tile-minimum seed, keys per workgroup and query)
         h->last_seed_stat = seed_stat ? seed_j : 0;
         h->last_sample_rows = sstride ? view_rows(nb, sstride, p.vshift) : 0;
@@ -4224,6 +4646,11 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     sp.seed_cnt = out.seed_cnt; sp.seed_gthr = out.seed_gthr; sp.seed_qthr = out.seed_qthr; sp.seed_j = out.seed_j; sp.seed_stat = out.seed_stat;
     sp.seed_nslots = out.seed_nslots;
     sp.qthr = qthr; sp.fail = (int *)h->ws_flag.p;
+    if (h->s16_mode == 2) {
+        sp.gate = h->s16_gate;
+        sp.gate_n = h->s16_gate_n;
+        sp.gate_count = h->s16_gate_count;
+    }
     if (reset_sig && out.seed_cnt == nullptr) {
         sp.rs_gthr = gthr; sp.rs_qcnt = qcnt; sp.rs_qthr = qthr; sp.rs_nslots = (int)nslots;
         sp.rs_pub = (uint64_t *)lb.pub.p; sp.rs_pub_n = pub_rounds * pl.nchunks * pub_m;
@@ -4232,7 +4659,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     }
     rc = launch_select(sp, s, &h->ws_tmp);
     if (!rc && sp.rs_gthr) lb.clean_sig = reset_sig;
-    if (top && h->done) (void)hipEventRecord(h->done, s); // (everything this search enqueued: see DevBuf::ensure)
+    if (level == 0 && h->done) (void)hipEventRecord(h->done, s); // (everything this search enqueued: see DevBuf::ensure)
     return rc;
 }
 
@@ -4254,6 +4681,8 @@ static int search_keys_impl(knn_index_s *h, const float *q_dev, int64_t nq, int 
                             uint64_t *keys_out, float *D_out, int64_t *I_out, bool allow_stat, hipStream_t s)
 {
     BatchScope scope(h, nq);
+    h->last_s16_used = false;
+    h->s16_pieces = 0;
     const float *xn = nullptr;
     if (h->metric == KNN_METRIC_L2) {
         if (h->ws_qn.ensure((size_t)nq * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
@@ -4986,6 +5415,8 @@ extern "C" int knn_flat_normalize_rows(knn_handle h)
     if (rc) return rc;
     rc = approx16_sync_rows(h, 0, h->ntotal, h->stream);
     if (rc) return rc;
+    rc = scan16_sync_rows(h, 0, h->ntotal, h->stream); // (the rows changed: copies and statistics from scratch)
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -5093,6 +5524,38 @@ extern "C" int knn_flat_reserve(knn_handle h, int64_t nrows)
     h->xb_bytes = xb_got;
     h->yn_bytes = yn_got;
     h->cap_rows = nrows;
+    return scan16_sync_rows(h, h->ntotal, 0, h->stream); // (the fp16 copies grow with the rows)
+}
+
+extern "C" int knn_flat_set_scan16(knn_handle h, int32_t mode)
+{
+    if (!h) return set_err(KNN_ERR_INVALID, "set_scan16: null handle");
+    if (mode != 0 && mode != 1) return set_err(KNN_ERR_INVALID, "set_scan16: mode must be 0 or 1");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->is_view) return set_err(KNN_ERR_INVALID, "set_scan16: a view uses its parent's setting");
+    if (mode && (h->approx16 || h->keep16)) return set_err(KNN_ERR_UNSUPPORTED, "set_scan16: not for an index that keeps bf16 copies (HNSW)");
+    if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "set_scan16: the index already holds rows");
+    const char *env = getenv("KNN355_SCAN16");
+    if (mode == 1 && env && strcmp(env, "0") == 0) mode = 0; // (same-tree A/B runs)
+    h->scan16 = mode;
+    h->dp16 = round_up(h->d, 64);
+    h->s16_note = mode ? "on" : "off";
+    return 0;
+}
+
+extern "C" int knn_last_scan16_info(knn_handle h, int32_t *used, int32_t *candidates_max, int64_t *fallbacks)
+{
+    if (!h) return set_err(KNN_ERR_INVALID, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    uint32_t st[2] = {0u, 0u};
+    if (h->ws_s16stat.p) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipDeviceSynchronize()); // (the searches ran on their callers' streams)
+        HIP_TRY(hipMemcpy(st, h->ws_s16stat.p, sizeof st, hipMemcpyDeviceToHost));
+    }
+    if (used) *used = h->last_s16_used ? 1 : 0;
+    if (candidates_max) *candidates_max = h->last_s16_used ? (int32_t)st[0] : 0;
+    if (fallbacks) *fallbacks = (int64_t)st[1];
     return 0;
 }
 

@@ -198,6 +198,17 @@ class IndexFlat(Index):
         return {"kernel": name.value.decode(), "query_tile": qt.value, "db_tile": dt.value, "nchunks": nc.value,
                 "grid": grid.value, "ms": float(L.knn_last_scan_ms(self._h))}
 
+    def set_scan16(self, mode=1):
+        """Before the first add: keep fp16 copies of the rows for the exact 16-bit prefilter (knn_flat_set_scan16; 0 = off)"""
+        _lib.check(_lib.lib().knn_flat_set_scan16(self._h, int(mode)))
+
+    def last_scan16(self):
+        """{"used": the last search took the exact 16-bit prefilter, "candidates_max": most rows one of its queries re-scored,
+        "fallbacks": prefiltered searches of this handle that fell back to the fp32 scan so far}"""
+        used, cand, fb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        _lib.check(_lib.lib().knn_last_scan16_info(self._h, ctypes.byref(used), ctypes.byref(cand), ctypes.byref(fb)))
+        return {"used": bool(used.value), "candidates_max": cand.value, "fallbacks": fb.value}
+
     def last_range(self):
         """{"query_blocks": blocks of queries the last range search ran in, "redos": rescans of queries whose
         staging segment overflowed, "redo_queries": queries rescanned}; last_scan() names the range kernel"""

@@ -76,6 +76,7 @@ class HipShardBackend:
 
     def __init__(self, d, metric):
         self.index = _faiss.IndexFlat(d, metric)
+        self.index.set_scan16(1)  # fp16 copies of the shard: its streaming searches take the exact 16-bit prefilter
         self.metric = metric
         self.device = torch.device("cuda", int(_lib.lib().knn_device_of(self.index._h)))
         self._lanes = None

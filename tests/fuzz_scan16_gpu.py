@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Developer fuzz of the exact 16-bit prefilter (knn_flat_set_scan16): every case searches one index with
+the prefilter forced on ("whatever nb" tuning bit) and with it off ("never" bit) and compares D / I bit for bit, and
+against the CPU oracle.  Random shapes, k, batch sizes and data kinds: gaussian, L2-normalised, rows scaled by powers
+of two up to 2^+-40, magnitudes mixed inside rows, duplicated and zero rows, near-duplicates of a query that fp16 cannot
+tell apart (the device fallback), constant rows.  usage: fuzz_scan16_gpu.py [ncases] [seed]"""
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+from knn_for_homology_amd import faiss  # noqa: E402
+from oracle import knn_oracle as ko  # noqa: E402
+
+NEVER, ANY_NB = 1 << 20, 1 << 21
+KINDS = ("gauss", "normed", "scaled", "mixed", "dups", "near", "const")
+
+
+def data(rng, kind, nb, d, nq):
+    xb = rng.standard_normal((nb, d), dtype=np.float32)
+    xq = rng.standard_normal((nq, d), dtype=np.float32)
+    if kind == "normed":
+        xb /= np.linalg.norm(xb, axis=1, keepdims=True)
+        xq /= np.linalg.norm(xq, axis=1, keepdims=True)
+    elif kind == "scaled":
+        xb *= np.exp2(rng.integers(-40, 41, size=(nb, 1))).astype(np.float32)
+        xq *= np.float32(2.0 ** int(rng.integers(-20, 21)))
+    elif kind == "mixed":
+        xb[:, : max(1, d // 3)] *= np.float32(2.0 ** 18)
+    elif kind == "dups":
+        src = rng.integers(0, nb, size=nb // 4)
+        xb[rng.integers(0, nb, size=nb // 4)] = xb[src]
+        xb[rng.integers(0, nb, size=max(1, nb // 50))] = 0.0
+    elif kind == "near":
+        m = int(min(nb // 2, rng.integers(50, 3000)))
+        j = int(rng.integers(0, nq))
+        xb[:m] = xq[j] + rng.standard_normal((m, d), dtype=np.float32) * np.float32(1e-6)
+    elif kind == "const":
+        xb[:] = np.float32(rng.standard_normal())
+    return xb, xq
+
+
+def run(ncases=1000, seed=1):
+    rng = np.random.default_rng(seed)
+    orc = ko.oracle()
+    fails = used = fallbacks = 0
+    t0 = time.time()
+    for case in range(ncases):
+        d = int(rng.choice([8, 16, 32, 40, 64, 100, 128, 256, 300]))
+        nb = int(rng.integers(300, 40000))
+        nq = int(rng.integers(1, 33))
+        k = int(min(nb, rng.choice([1, 2, 10, 50, 100, 256, 500, 1000, 1500])))
+        kind = KINDS[case % len(KINDS)]
+        xb, xq = data(rng, kind, nb, d, nq)
+        idx = faiss.IndexFlat(d, faiss.METRIC_INNER_PRODUCT)
+        idx.set_scan16(1)
+        idx.add(xb)
+        fb0 = idx.last_scan16()["fallbacks"]
+        idx.set_tuning(0, 0, ANY_NB)
+        D, I = idx.search(xq, k)
+        info = idx.last_scan16()
+        idx.set_tuning(0, 0, NEVER)
+        D0, I0 = idx.search(xq, k)
+        Do, Io = orc.flat_search(xb, xq, k, faiss.METRIC_INNER_PRODUCT)
+        ok = (np.array_equal(I, I0) and np.array_equal(D.view(np.uint32), D0.view(np.uint32))
+              and np.array_equal(I, Io) and np.array_equal(D.view(np.uint32), Do.view(np.uint32)))
+        used += info["used"]
+        fallbacks += info["fallbacks"] - fb0
+        if not ok:
+            fails += 1
+            print(f"FAIL case {case}: d={d} nb={nb} nq={nq} k={k} kind={kind} {info}", flush=True)
+        elif case % 50 == 0:
+            print(f"case {case} ok ({time.time() - t0:.0f}s): d={d} nb={nb} nq={nq} k={k} kind={kind} {info}", flush=True)
+    print(f"SCAN16 FUZZ: {fails} failures of {ncases} cases; {used} took the prefilter, {fallbacks} fell back on the device "
+          f"({time.time() - t0:.0f}s)")
+    return fails
+
+
+if __name__ == "__main__":
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
+    s = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    sys.exit(1 if run(n, s) else 0)
