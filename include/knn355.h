@@ -332,33 +332,46 @@ int32_t knn_scan_times(knn_handle h, float *out_ms, int32_t max_n);
  * rows scanned by the sample pass (the main scan kernel skips them) */
 int knn_last_seed_info(knn_handle h, int32_t *seed_stride, int32_t *stat_rank, int64_t *stat_redo,
                        int64_t *sample_rows);
+/* knn_set_tuning flags, all off by default.  Only KNN_TUNE_NORM_L2 changes what a search returns (the other formula's
+ * rounding); every other combination returns the same bits. */
+enum {
+    KNN_TUNE_NO_POOL = 2,                /* no shared pool of tiles in a paired (one-query-tile) launch */
+    KNN_TUNE_NO_PAIRS = 4,               /* never pair the workgroups of a one-query-tile launch: static chunks instead */
+    KNN_TUNE_NO_SEED = 8,                /* no seeding at all (every chunk warms its thresholds up on its own) */
+    KNN_TUNE_EXACT_SEED = 16,            /* force the exact seed (a sample pass of its own in front of the scan) */
+    /* squared L2 by the norm formula |x|^2 + |y|^2 - 2<x,y> whatever the batch size (default: FAISS's rule -- batches of
+     * fewer than 20 queries use the sum of squared differences, larger ones the norm formula) */
+    KNN_TUNE_NORM_L2 = 32,
+    /* always launch the state-reset kernel in front of a streaming scan (default: the previous search's final selection
+     * leaves the state reset when the next search has the same shape) */
+    KNN_TUNE_ALWAYS_RESET = 64,
+    KNN_TUNE_STAT_SEED = 128,            /* force the statistical seed (synchronous entry points only) */
+    KNN_TUNE_NO_TURNS = 256,             /* the two workgroups of a CU do not take turns in their K loops (batch launches) */
+    KNN_TUNE_NO_STAT_SEED = 512,         /* never use the statistical seed */
+    KNN_TUNE_NO_SYM = 1024,              /* never use the symmetric launch of a whole-index self-search */
+    /* never use the tile-minimum seed (a streaming search then runs its seed sample as a launch of its own) */
+    KNN_TUNE_NO_TILE_MIN_SEED = 2048,
+    /* bits 12-13: publication rounds of the tile-minimum seed (0 = the library's choice), r << KNN_TUNE_PUB_ROUNDS_SHIFT */
+    KNN_TUNE_PUB_ROUNDS_SHIFT = 12,
+    KNN_TUNE_PUB_ROUNDS_MASK = 3 << 12,
+    /* never search the remainder behind the full 128-query tiles as a piece of its own (large databases: 129 queries are one
+     * 128-query launch and one streaming launch instead of two 128-query passes) */
+    KNN_TUNE_NO_REMAINDER_SPLIT = 16384,
+    /* plans without the 48- and 96-query tiles (33..48 queries then pay for a 64-query tile, 65..96 for 128 or two pieces) */
+    KNN_TUNE_NO_Q16 = 131072,
+    /* never the 256 x 256 tile (one workgroup per CU; the library's choice for synchronous searches of >= 256 queries over
+     * >= 65 536 rows with long chunks, always under the statistical seed) */
+    KNN_TUNE_NO_BIG_TILE = 262144,
+    /* the 256 x 256 tile wherever a batch holds more than 128 queries and the index >= 1024 rows, and 256-row tiles in the
+     * symmetric whole-index self-search (tests, A/B) */
+    KNN_TUNE_BIG_TILE = 524288,
+    KNN_TUNE_NO_SCAN16 = 1 << 20,        /* never the exact 16-bit prefilter (knn_flat_set_scan16), A/B */
+    /* the exact 16-bit prefilter wherever it applies, whatever the number of rows (tests; default: from 2^18 rows on) */
+    KNN_TUNE_SCAN16_ANY_NB = 1 << 21
+};
 /* force a scan configuration: query_tile in {0(auto),32,48,64,96,128,256} (48 and 96: the builds on 16-query MFMA blocks, one
  * query tile per launch -- honoured when the batch fits the tile, ignored otherwise); nchunks 0=auto (a forced count also turns the paired
- * walk off); flags, all off by default:
- *      2  no shared pool of tiles in a paired (one-query-tile) launch
- *      4  never pair the workgroups of a one-query-tile launch: static chunks instead
- *      8  no seeding at all (every chunk warms its thresholds up on its own)
- *     16  force the exact seed (a sample pass of its own in front of the scan)
- *     32  squared L2 by the norm formula |x|^2 + |y|^2 - 2<x,y> whatever the batch size (default: FAISS's rule --
- *         batches of fewer than 20 queries use the sum of squared differences, larger ones the norm formula)
- *     64  always launch the state-reset kernel in front of a streaming scan (default: the previous search's final
- *         selection leaves the state reset when the next search has the same shape)
- *    128  force the statistical seed (synchronous entry points only)
- *    256  the two workgroups of a CU do not take turns in their K loops (batch launches)
- *    512  never use the statistical seed
- *   1024  never use the symmetric launch of a whole-index self-search
- *   2048  never use the tile-minimum seed (a streaming search then runs its seed sample as a launch of its own)
- *   bits 12-13  publication rounds of the tile-minimum seed (0 = the library's choice)
- *  16384  never search the remainder behind the full 128-query tiles as a piece of its own (large databases: 129 queries
- *         are one 128-query launch and one streaming launch instead of two 128-query passes)
- * 131072  plans without the 48- and 96-query tiles (33..48 queries then pay for a 64-query tile, 65..96 for 128 or two pieces)
- * 262144  never the 256 x 256 tile (one workgroup per CU; the library's choice for synchronous searches of >= 256 queries over
- *         >= 65 536 rows with long chunks, always under the statistical seed)
- * 524288  the 256 x 256 tile wherever a batch holds more than 128 queries and the index >= 1024 rows, and 256-row tiles in the
- *         symmetric whole-index self-search (tests, A/B)
- * 1048576  never the exact 16-bit prefilter (knn_flat_set_scan16), A/B
- * 2097152  the exact 16-bit prefilter wherever it applies, whatever the number of rows (tests; default: from 2^18 rows on)
- * Only 32 changes what a search returns (the other formula's rounding); every other combination returns the same bits. */
+ * walk off); flags: KNN_TUNE_* above */
 int knn_set_tuning(knn_handle h, int32_t query_tile, int32_t nchunks, int32_t flags);
 
 /* Exact 16-bit prefilter, opt-in per index, before the first add: mode 1 keeps fp16 copies of the rows (d rounded

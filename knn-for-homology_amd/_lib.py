@@ -19,6 +19,29 @@ LIB_PATH = os.environ.get("KNN355_LIB") or os.path.join(_HERE, "libknn355.so")
 _lib = None
 
 
+# knn_set_tuning flags: copies of the KNN_TUNE_* enum of include/knn355.h, which defines and documents them
+# (tests/test_abi.py checks that the two agree)
+KNN_TUNE_NO_POOL = 2
+KNN_TUNE_NO_PAIRS = 4
+KNN_TUNE_NO_SEED = 8
+KNN_TUNE_EXACT_SEED = 16
+KNN_TUNE_NORM_L2 = 32
+KNN_TUNE_ALWAYS_RESET = 64
+KNN_TUNE_STAT_SEED = 128
+KNN_TUNE_NO_TURNS = 256
+KNN_TUNE_NO_STAT_SEED = 512
+KNN_TUNE_NO_SYM = 1024
+KNN_TUNE_NO_TILE_MIN_SEED = 2048
+KNN_TUNE_PUB_ROUNDS_SHIFT = 12
+KNN_TUNE_PUB_ROUNDS_MASK = 3 << 12
+KNN_TUNE_NO_REMAINDER_SPLIT = 16384
+KNN_TUNE_NO_Q16 = 131072
+KNN_TUNE_NO_BIG_TILE = 262144
+KNN_TUNE_BIG_TILE = 524288
+KNN_TUNE_NO_SCAN16 = 1 << 20
+KNN_TUNE_SCAN16_ANY_NB = 1 << 21
+
+
 class Knn355Error(RuntimeError):
     """Raised for every non-zero return code of the C ABI (FAISS surfaces its C++
     exceptions as RuntimeError too)."""

@@ -3401,12 +3401,6 @@ struct knn_index_s {
     const int8_t *s16_exp = nullptr;
     const uint32_t *s16_stat = nullptr;
     std::string s16_note;
-    // while a prefiltered search is being enqueued: 1 = its 16-bit pass, 2 = its gated fp32 fallback (search_view_s16)
-    int s16_mode = 0;
-    const int *s16_qexp = nullptr;
-    const uint32_t *s16_gate = nullptr;
-    int s16_gate_n = 0;
-    uint32_t *s16_gate_count = nullptr;
     DevBuf ws_q16x, ws_s16q, ws_s16ak, ws_s16ok, ws_s16stat; // fp16 queries; exponents, bounds, flags; keys; [largest window, fallbacks]
     bool last_s16_used = false;   // some piece of the last search (search_keys_impl) took the prefilter
     int s16_pieces = 0;           // ... how many: the first one restarts the largest-window counter
@@ -4050,19 +4044,33 @@ struct ScanPlan {
 // build, four chains per thread, reads at the HBM rate: 6.25 ms)
 static int diff_build_width(int64_t nq) { return nq <= 8 ? 8 : (nq <= 12 ? 12 : (nq <= 16 ? 16 : 20)); }
 
+// Which pass of a prefiltered search (search_view_s16) a search_view call enqueues, and what that pass reads.  The default is
+// a plain search.
+struct S16Pass {
+    int mode = 0;                    // 0 plain, 1 the 16-bit pass, 2 the gated fp32 fallback
+    const int *qexp = nullptr;       // 1: the fp16 queries' exponents
+    const uint32_t *gate = nullptr;  // 2: the per-query fallback flags [gate_n] (ScanParams::gate)
+    int gate_n = 0;
+    uint32_t *gate_count = nullptr;  // 2: counts the fallbacks taken (SelectParams::gate_count)
+};
+
+// one scan launch: plan.grid workgroups of 256 threads with plan.lds bytes of dynamic LDS
+static int launch_scan(void (*kern)(ScanParams), const ScanParams &p, const ScanPlan &plan, hipStream_t s)
+{
+    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 template <int WM, int WN, int TM, int TN>
-static int launch_scan_cfg(const knn_index_s *h, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
+static int launch_scan_cfg(const knn_index_s *h, const S16Pass &pass, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
 {
     const bool l2 = h->metric == KNN_METRIC_L2;
-    void (*kern)(ScanParams) = nullptr;
-    if (h->s16_mode == 1) { // the 16-bit pass of a prefiltered search (search_view_s16)
+    if (pass.mode == 1) { // the 16-bit pass of a prefiltered search (search_view_s16)
         if constexpr (WM == 4 && WN == 1 && TM == 2 && TN == 1) {
             if (p.nqtiles != 1 || l2) return set_err(KNN_ERR_INVALID, "scan: the 16-bit prefilter serves one 32-query tile, inner product");
-            kern = flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>;
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-            hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
-            HIP_TRY(hipGetLastError());
-            return 0;
+            return launch_scan(flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>, p, plan, s);
         }
         return set_err(KNN_ERR_INVALID, "scan: the 16-bit prefilter has the 32-query build only");
     }
@@ -4072,60 +4080,56 @@ static int launch_scan_cfg(const knn_index_s *h, const ScanParams &p, const Scan
             // (builds for up to 8, 12, 16 and 19 queries: the vector work of a K step grows with the build's width -- up to 8
             // queries scan at the speed of their HBM traffic)
             switch (diff_build_width(p.nq)) {
-            case 8: kern = flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 8>; break;
-            case 12: kern = flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 12>; break;
-            case 16: kern = flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 16>; break;
-            default: kern = flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 20>; break;
+            case 8: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 8>, p, plan, s);
+            case 12: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 12>, p, plan, s);
+            case 16: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 16>, p, plan, s);
+            default: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 20>, p, plan, s);
             }
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-            hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
-            HIP_TRY(hipGetLastError());
-            return 0;
         }
     }
+    void (*kern)(ScanParams) = nullptr;
     if (h->approx16) {
         if (p.nqtiles == 1) kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, true, false, true>;
         else kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, false, false, true>;
     } else if (p.nqtiles == 1) kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true> : flat_scan_kernel<WM, WN, TM, TN, false, true>;
     else kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false> : flat_scan_kernel<WM, WN, TM, TN, false, false>;
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_scan(kern, p, plan, s);
 }
 
 // the 256 x 256 tile (2 x 2 waves of 4 x 4 MFMA tiles, one workgroup per CU): plain fp32 rows, several query tiles per launch
-static int launch_scan_big(const knn_index_s *h, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
+static int launch_scan_big(const knn_index_s *h, const S16Pass &pass, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
 {
-    if (h->approx16 || h->s16_mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 256-query tile serves plain fp32 rows");
-    void (*kern)(ScanParams) = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 4, 4, true, false> : flat_scan_kernel<2, 2, 4, 4, false, false>;
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (h->approx16 || pass.mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 256-query tile serves plain fp32 rows");
+    return launch_scan(h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 4, 4, true, false> : flat_scan_kernel<2, 2, 4, 4, false, false>, p, plan, s);
 }
 
 // the builds on 16-query blocks (48 queries: 4 x 1 waves, 96: 2 x 2 waves; Q16 blocks per wave): one query tile per launch
 template <int WM, int WN, int TM, int Q16>
-static int launch_scan16(const knn_index_s *h, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
+static int launch_scan16(const knn_index_s *h, const S16Pass &pass, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
 {
-    if (p.nqtiles != 1 || h->approx16 || h->s16_mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 16-query-block builds serve one query tile of plain fp32 rows");
-    void (*kern)(ScanParams) = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<WM, WN, TM, 1, true, true, false, false, 0, Q16>
-                                                          : flat_scan_kernel<WM, WN, TM, 1, false, true, false, false, 0, Q16>;
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (p.nqtiles != 1 || h->approx16 || pass.mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 16-query-block builds serve one query tile of plain fp32 rows");
+    return launch_scan(h->metric == KNN_METRIC_L2 ? flat_scan_kernel<WM, WN, TM, 1, true, true, false, false, 0, Q16>
+                                                  : flat_scan_kernel<WM, WN, TM, 1, false, true, false, false, 0, Q16>,
+                       p, plan, s);
+}
+
+// knn_set_tuning rules that several plan decisions share
+// the statistical seed may run: seeding on, the exact seed not forced, the estimate not forbidden
+static bool stat_seed_allowed(const knn_index_s *h) { return !(h->flags & (KNN_TUNE_NO_SEED | KNN_TUNE_EXACT_SEED | KNN_TUNE_NO_STAT_SEED)); }
+// the tile-minimum seed may run: seeding on, neither the exact nor the statistical seed forced, the tile-minimum seed not forbidden
+static bool tile_min_seed_allowed(const knn_index_s *h)
+{
+    return !(h->flags & (KNN_TUNE_NO_SEED | KNN_TUNE_EXACT_SEED | KNN_TUNE_STAT_SEED | KNN_TUNE_NO_TILE_MIN_SEED));
 }
 
 // Does the 256 x 256 tile (flat_scan_kernel<2, 2, 4, 4>: one workgroup per CU) serve this search?  Its K loop keeps the matrix
 // pipe busier than two co-resident 128 x 128 workgroups do, but nothing hides its epilogues, a launch has half the
 // workgroups and four times the tile: it wants long chunks on every CU -- Pfam-sized batches, not CATH-sized ones.
-// flags & 262144: never; flags & 524288: wherever a batch has more than 128 queries (tests, A/B).
+// KNN_TUNE_NO_BIG_TILE: never; KNN_TUNE_BIG_TILE: wherever a batch has more than 128 queries (tests, A/B).
 static bool big_tile_pays(const knn_index_s *h, int64_t nb, int64_t nq)
 {
-    if (h->approx16 || (h->flags & 262144) || nq <= 128) return false;
-    if (h->flags & 524288) return nb >= 1024;
+    if (h->approx16 || (h->flags & KNN_TUNE_NO_BIG_TILE) || nq <= 128) return false;
+    if (h->flags & KNN_TUNE_BIG_TILE) return nb >= 1024;
     if (nb < 65536) return false; // (never a seed sample's own scan)
     const int64_t cus = std::max(1, h->num_cus);
     const int64_t work = ((nq + 255) / 256) * ((nb + 255) / 256); // 256 x 256 tiles of the search
@@ -4144,20 +4148,20 @@ static void make_plan(const knn_index_s *h, int64_t nb, int64_t nq, int k, bool 
     if (qt == 256 && (h->approx16 || nq <= 128)) qt = 0; // (the 256 x 256 tile: plain fp32 rows, more than one 128-query tile of queries)
     if (qt != 32 && qt != 48 && qt != 64 && qt != 96 && qt != 128 && qt != 256) {
         qt = nq <= 32 ? 32 : (nq <= 64 ? 64 : 128);
-        if (!h->approx16 && !(h->flags & 131072)) { // (flags & 131072: without the 16-query-block builds)
+        if (!h->approx16 && !(h->flags & KNN_TUNE_NO_Q16)) { // (KNN_TUNE_NO_Q16: without the 16-query-block builds)
             if (nq > 32 && nq <= 48) qt = 48;
             else if (nq > 64 && nq <= 96) qt = 96;
         }
         if (allow_big && big_tile_pays(h, nb, nq)) qt = 256;
     }
-    // FAISS's squared L2 for fewer than 20 queries: the sum of squared differences (flags & 32: the norm formula throughout).
+    // FAISS's squared L2 for fewer than 20 queries: the sum of squared differences (KNN_TUNE_NORM_L2: the norm formula throughout).
     // FAISS decides on the batch its caller handed over, so a piece of a larger batch (the last block of 16384 queries, the
     // remainder behind the full query tiles) keeps the formula of the whole.
     const bool small_batch = (h->batch_nq ? h->batch_nq : nq) < 20 && nq < 20;
-    if (h->metric == KNN_METRIC_L2 && small_batch && !h->approx16 && !(h->flags & 32)) qt = 32; // (the difference build exists for the 32-query tile only)
+    if (h->metric == KNN_METRIC_L2 && small_batch && !h->approx16 && !(h->flags & KNN_TUNE_NORM_L2)) qt = 32; // (the difference build exists for the 32-query tile only)
     pl.qt = qt;
     pl.dt = (qt == 32 || qt == 48 || qt == 256) ? 256 : 128;
-    pl.diff = h->metric == KNN_METRIC_L2 && small_batch && qt == 32 && !h->approx16 && !(h->flags & 32);
+    pl.diff = h->metric == KNN_METRIC_L2 && small_batch && qt == 32 && !h->approx16 && !(h->flags & KNN_TUNE_NORM_L2);
     pl.name = pl.diff ? "flat_scan_q32_d256_l2diff"
                       : (qt == 256 ? "flat_scan_q256_d256" : qt == 128 ? "flat_scan_q128_d128" : (qt == 96 ? "flat_scan_q96_d128" : (qt == 64 ? "flat_scan_q64_d128" : (qt == 48 ? "flat_scan_q48_d256" : "flat_scan_q32_d256"))));
     pl.nqtiles = (int)((nq + qt - 1) / qt);
@@ -4174,7 +4178,7 @@ static void make_plan(const knn_index_s *h, int64_t nb, int64_t nq, int k, bool 
     else if (k <= KNN_WAVE_SELECT_MAX_K) pl.cap = std::min(pl.cap, 4096);  // wave_select_mem: 1.25 k + a tile of appends fit
     const int64_t ntiles = (nb + pl.dt - 1) / pl.dt;
     pl.npairs = 0;
-    if (allow_pairs && pl.nqtiles == 1 && qt != 256 && h->force_chunks <= 0 && !(h->flags & 4) && ntiles >= (int64_t)dev_knob("KNN355_PAIR_MIN_TILES", 64)) {
+    if (allow_pairs && pl.nqtiles == 1 && qt != 256 && h->force_chunks <= 0 && !(h->flags & KNN_TUNE_NO_PAIRS) && ntiles >= (int64_t)dev_knob("KNN355_PAIR_MIN_TILES", 64)) {
         // one query tile, plenty of tiles: two workgroups per CU, paired (see flat_scan_kernel): each pair shares a
         // contiguous range of ~ ntiles / CUs tiles (at least two: fewer pairs than CUs on a small database)
         pl.npairs = (int)std::min<int64_t>(std::max(1, h->num_cus), ntiles / 2);
@@ -4281,10 +4285,9 @@ struct SearchOut {
 
 // ---- the exact 16-bit prefilter ----------------------------------------------------------------------------
 static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int row_mul,
-                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag = nullptr);
+                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag = nullptr,
+                       const S16Pass &pass = S16Pass());
 
-// knn_set_tuning flags: never the 16-bit prefilter (A/B) / wherever it applies, whatever the number of rows (tests)
-static const int KNN_FLAG_S16_NEVER = 1 << 20, KNN_FLAG_S16_ANY_NB = 1 << 21;
 // approximate keys the 16-bit pass hands to the re-scoring tail: room for the window above the k-th (fp16 on normalised
 // rows: a few percent of k beyond it at 10 M rows, k = 100)
 static int s16_kprime(int k) { return std::min(KNN_WAVE_SELECT_MAX_K, std::max(2 * k, k + 64)); }
@@ -4292,13 +4295,13 @@ static int s16_kprime(int k) { return std::min(KNN_WAVE_SELECT_MAX_K, std::max(2
 // Does a search of the view take the prefiltered path?  A one-query-tile streaming search (the 32-query build) by inner
 // product over an index whose fp16 copies cover every row, from nb >= 2^18 rows on (below that the fp32 scan's fixed costs
 // dominate and the tail's launches would not pay).  Batch, symmetric, difference, HNSW and range searches never do.
-static bool s16_eligible(const knn_index_s *h, int64_t nb, int64_t nq, int k, int row_mul, int level, const SearchOut &out)
+static bool s16_eligible(const knn_index_s *h, const S16Pass &pass, int64_t nb, int64_t nq, int k, int row_mul, int level, const SearchOut &out)
 {
-    if (h->scan16 != 1 || !h->s16_ok->load() || !h->s16_rows || h->s16_mode || level != 0 || row_mul != 1 || out.seed_cnt) return false;
-    if (h->metric != KNN_METRIC_INNER_PRODUCT || h->approx16 || (h->flags & KNN_FLAG_S16_NEVER)) return false;
+    if (h->scan16 != 1 || !h->s16_ok->load() || !h->s16_rows || pass.mode || level != 0 || row_mul != 1 || out.seed_cnt) return false;
+    if (h->metric != KNN_METRIC_INNER_PRODUCT || h->approx16 || (h->flags & KNN_TUNE_NO_SCAN16)) return false;
     if (nq < 1 || nq > 32 || (h->force_qt != 0 && h->force_qt != 32) || s16_kprime(k) <= k) return false; // (k' = k: no room for a window)
     if ((size_t)h->dp * 4 + 64 > 65536) return false; // (rescore16_kernel holds the query in LDS, no opt-in beyond 64 KB)
-    return nb >= (1 << 18) || (h->flags & KNN_FLAG_S16_ANY_NB);
+    return nb >= (1 << 18) || (h->flags & KNN_TUNE_SCAN16_ANY_NB);
 }
 
 // One prefiltered search, six launches on the caller's stream, no host wait:
@@ -4330,10 +4333,10 @@ static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, 
     HIP_TRY(hipGetLastError());
     SearchOut ao;
     ao.keys = (uint64_t *)h->ws_s16ak.p; ao.keys_stride = kp; ao.keys_fill = 0;
-    h->s16_mode = 1;
-    h->s16_qexp = qexp;
-    int rc = search_view(h, (const float *)q16, nullptr, nq, kp, id_base, 1, vshift, 0, ao, false, s, reset_flag);
-    h->s16_mode = 0;
+    S16Pass f16;
+    f16.mode = 1;
+    f16.qexp = qexp;
+    int rc = search_view(h, (const float *)q16, nullptr, nq, kp, id_base, 1, vshift, 0, ao, false, s, reset_flag, f16);
     if (rc) return rc;
     hipLaunchKernelGGL(rescore16_kernel, dim3((unsigned)nq), dim3(256), (size_t)h->dp * 4, s, (const uint64_t *)h->ws_s16ak.p, kp, k, Bq, pfail, rfail,
                        h->xb, h->dp, q_dev, id_base, (uint64_t *)h->ws_s16ok.p, sstat);
@@ -4345,50 +4348,50 @@ static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, 
     sp.D = out.D; sp.I = out.I;
     rc = launch_select(sp, s);
     if (rc) return rc;
-    h->s16_mode = 2;
-    h->s16_gate = rfail;
-    h->s16_gate_n = (int)nq;
-    h->s16_gate_count = sstat + 1;
-    rc = search_view(h, q_dev, xn, nq, k, id_base, 1, vshift, 0, out, false, s, nullptr);
-    h->s16_mode = 0;
-    h->s16_gate = nullptr;
-    h->s16_gate_n = 0;
-    h->s16_gate_count = nullptr;
+    S16Pass gated;
+    gated.mode = 2;
+    gated.gate = rfail;
+    gated.gate_n = (int)nq;
+    gated.gate_count = sstat + 1;
+    rc = search_view(h, q_dev, xn, nq, k, id_base, 1, vshift, 0, out, false, s, nullptr, gated);
     h->last_s16_used = true;
     h->s16_pieces++;
     return rc;
 }
 
 // Exact top-k of the block-strided view (view_row) with stride row_mul / block shift vshift for
-// queries [nq][dp] on the device.  allow_stat: the caller checks h->ws_flag afterwards.
+// queries [nq][dp] on the device.  allow_stat: the caller checks h->ws_flag afterwards.  pass: the pass of a prefiltered
+// search this is (search_view_s16), handed on unchanged to the seed sample's search.
 static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int row_mul,
-                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag)
+                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag, const S16Pass &pass)
 {
     const int64_t nb = view_rows(h->ntotal, row_mul, vshift);
-    if (s16_eligible(h, nb, nq, k, row_mul, level, out)) return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
+    if (s16_eligible(h, pass, nb, nq, k, row_mul, level, out)) return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
     ScanPlan pl;
     const bool allow_pairs = !h->approx16; // (the bf16 build has no one-query-tile streaming case worth pairing)
+    // the statistical seed may serve this search (its caller checks the verification flag)
+    const bool stat_ok = allow_stat && level == 0 && row_mul == 1 && stat_seed_allowed(h);
     // (the 256 x 256 tile needs the statistical seed -- see below -- so only callers that can check its verification flag get it)
-    const bool allow_big = (allow_stat && level == 0 && row_mul == 1 && !(h->flags & (8 | 16 | 512))) || (h->flags & 524288);
+    const bool allow_big = stat_ok || (h->flags & KNN_TUNE_BIG_TILE);
     make_plan(h, nb, nq, k, true, pl, allow_pairs, allow_big);
     if (level >= knn_index_s::MAX_LEVELS) return set_err(KNN_ERR_INVALID, "search: seed recursion too deep");
     // Exact seeding pays when the sample that gives every chunk a tight threshold (about two chunks'
     // worth of rows, at least 64 k) is a small fraction of the view: the streaming regime (few
-    // queries, huge database, hundreds of chunks).  flags & 8 turns all seeding off, flags & 16
-    // forces the exact seed, flags & 128 forces the statistical one, flags & 512 forbids it (tests).
+    // queries, huge database, hundreds of chunks).  KNN_TUNE_NO_SEED turns all seeding off, KNN_TUNE_EXACT_SEED
+    // forces the exact seed, KNN_TUNE_STAT_SEED forces the statistical one, KNN_TUNE_NO_STAT_SEED forbids it (tests).
     bool seed = nb >= 512 * (int64_t)k && std::max<int64_t>(2 * pl.chunk_rows, 64 * (int64_t)k) <= nb / 32;
-    if (h->flags & 16) seed = nb >= 8192 && nb >= 32 * (int64_t)k;
-    if (h->flags & (8 | 128)) seed = false;
+    if (h->flags & KNN_TUNE_EXACT_SEED) seed = nb >= 8192 && nb >= 32 * (int64_t)k;
+    if (h->flags & (KNN_TUNE_NO_SEED | KNN_TUNE_STAT_SEED)) seed = false;
     // (the 256 x 256 tile under a caller that can check the verification flag: the statistical estimate from every 256th row
     // instead of an exact search of every 32nd -- 10 M rows x 512 / 768 / 1536 queries 0.854 / 0.869 / 0.858 of the MFMA peak with
     // the exact seed where 1024 / 2048 queries, which the rule above leaves to the estimate, reach 0.887; the exact seed stays
     // the fallback when no rank qualifies)
     const bool exact_ok = seed;
-    if (seed && pl.qt == 256 && allow_stat && level == 0 && row_mul == 1 && !(h->flags & (8 | 16 | 512))) seed = false;
+    if (seed && pl.qt == 256 && stat_ok) seed = false;
     int sstride = seed ? seed_stride(nb, k, pl.chunk_rows) : 0;
     int seed_j = k, seed_stat = 0, svshift = vshift;
     double expect_n = 0; // typical candidates per query at the final selection (0: unknown, assume the capacity)
-    if (!seed && allow_stat && level == 0 && row_mul == 1 && !(h->flags & (8 | 16 | 512))) {
+    if (!seed && stat_ok) {
         // statistical seed: single rows, every 32nd (every 16th of a small database, every 64th of a
         // large one): a few percent of the work, one round of workgroups at CATH size
         int st = nb >= (1 << 20) ? 64 : (nb >= 8192 ? 32 : 16);
@@ -4405,7 +4408,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
 #ifdef KNN355_DEV
         if (getenv("KNN355_STAT_STRIDE")) st = atoi(getenv("KNN355_STAT_STRIDE")); // (developer build: the statistical sample's stride)
 #endif
-        const bool force = (h->flags & 128) != 0;
+        const bool force = (h->flags & KNN_TUNE_STAT_SEED) != 0;
         const int64_t S = view_rows(nb, st, 0);
         const int j = stat_seed_rank(S, nb, k);
         if (j > 0 && (force || (nq >= dev_knob("KNN355_STAT_MIN_NQ", 65) && nb >= 8192))) {
@@ -4434,11 +4437,11 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     // Tile-minimum seed (see flat_scan_kernel): where the exact seed would run a sample pass first, a launch with enough
     // chunks seeds itself -- each chunk publishes its first tiles' best key per query, the k-th smallest published key
     // is the bound.  Needs: the 32- or 64-query tile, plain fp32 rows, enough publications for k (<= 4096 of them).
-    // flags & 2048: never.  (The 128-query tile of a one-query-tile launch was tried: 100 k rows x 128 queries 0.66 -> 0.38 ms
+    // KNN_TUNE_NO_TILE_MIN_SEED: never.  (The 128-query tile of a one-query-tile launch was tried: 100 k rows x 128 queries 0.66 -> 0.38 ms
     // where no sample pass exists, but the code in that build cost its other launches 2-14 % -- 1.25 M rows 2.80 -> 3.20 ms;
     // such batches are searched as two 64-query pieces instead, see search_keys_impl.)
     int pub_rounds = 0, pub_m = 1;
-    const bool pub_shape = !(h->flags & (8 | 16 | 128 | 2048)) && !h->approx16 && pl.qt <= 64 && pl.cap >= 2 * pl.dt && pl.tiles_base >= (pl.npairs ? dev_knob("KNN355_PUB_MIN_TILES_PAIRED", 2) : 4);
+    const bool pub_shape = tile_min_seed_allowed(h) && !h->approx16 && pl.qt <= 64 && pl.cap >= 2 * pl.dt && pl.tiles_base >= (pl.npairs ? dev_knob("KNN355_PUB_MIN_TILES_PAIRED", 2) : 4);
     if (seed && pub_shape) {
         for (int r = 2; r >= 1; r--) // (one round if it gives enough publications)
             if ((int64_t)r * pl.nchunks <= 2048 && (int64_t)r * pl.nchunks >= 2 * (int64_t)k + 64 && r < pl.tiles_base) pub_rounds = r;
@@ -4461,7 +4464,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
             }
         }
     }
-    if (h->s16_mode == 2 && !pub_rounds) sstride = 0; // (a gated fallback runs no sample pass: its memsets could not be gated)
+    if (pass.mode == 2 && !pub_rounds) sstride = 0; // (a gated fallback runs no sample pass: its memsets could not be gated)
     if (pub_rounds) {
         sstride = 0;
         // the bound sits near the k / (publications x tile rows) quantile; the first tile(s) of every chunk are filtered
@@ -4498,7 +4501,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         // a statistical seed needs the sample's best ~1.25 j rows only (its bound has rank <= 1.25 j, and only rows that
         // beat the bound are handed on): the sample is searched with that k, not the caller's
         const int k_sample = seed_stat ? std::min(k, seed_j + std::max(seed_j >> 2, 8) + 8) : k;
-        rc = search_view(h, q_dev, xn, nq, k_sample, id_base, row_mul * sstride, svshift, level + 1, so, false, s, reset_flag);
+        rc = search_view(h, q_dev, xn, nq, k_sample, id_base, row_mul * sstride, svshift, level + 1, so, false, s, reset_flag, pass);
         if (rc) return rc;
     } else {
         const int64_t nn = std::max<int64_t>((int64_t)nslots, nq);
@@ -4514,7 +4517,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         if (pl.npairs && lb.pair_ctr.ensure(((size_t)pl.npairs + 1) * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         // A streaming search whose predecessor on this handle had exactly this shape finds the state already reset: that
         // search's final selection did it (SelectParams::rs_*) -- one launch and a ~10 us launch gap less per step.
-        if (pub_rounds && pl.npairs && !(h->flags & 64) && !h->s16_mode) { // (not inside a prefiltered search: its two passes differ in shape)
+        if (pub_rounds && pl.npairs && !(h->flags & KNN_TUNE_ALWAYS_RESET) && !pass.mode) { // (not inside a prefiltered search: its two passes differ in shape)
             uint64_t sig = 0x9E3779B97F4A7C15ull;
             const uint64_t parts[] = {(uint64_t)nslots, (uint64_t)nq, (uint64_t)npub, (uint64_t)pl.nqtiles, (uint64_t)pl.npairs, (uint64_t)(uintptr_t)gthr,
                                       (uint64_t)(uintptr_t)qcnt, (uint64_t)(uintptr_t)qthr, (uint64_t)(uintptr_t)pub, (uint64_t)(uintptr_t)arrive,
@@ -4525,7 +4528,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         if (!(reset_sig && lb.clean_sig == reset_sig)) {
             hipLaunchKernelGGL(init_level_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, gthr, (int64_t)nslots, qcnt, qthr, nq,
                                reset_flag, pub, npub, arrive, (int64_t)pl.nqtiles, pl.npairs ? (uint32_t *)lb.pair_ctr.p : nullptr, (int64_t)pl.npairs,
-                               h->s16_mode == 2 ? h->s16_gate : nullptr, h->s16_gate_n);
+                               pass.gate, pass.gate_n);
             HIP_TRY(hipGetLastError());
         }
         lb.clean_sig = 0; // (until this search's own selection has been enqueued)
@@ -4543,15 +4546,14 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         p.xb = (const float *)h->xb16.p;
         p.dp = h->dp / 2;
     }
-    if (h->s16_mode == 1) { // the 16-bit pass: fp16 rows and queries (q_dev), a row is dp16 / 2 four-byte units
+    if (pass.mode == 1) { // the 16-bit pass: fp16 rows and queries (q_dev), a row is dp16 / 2 four-byte units
         p.xb = (const float *)h->s16_rows;
         p.dp = h->dp16 / 2;
         p.xexp = h->s16_exp;
-        p.qexp = h->s16_qexp;
-    } else if (h->s16_mode == 2) {
-        p.gate = h->s16_gate;
-        p.gate_n = h->s16_gate_n;
+        p.qexp = pass.qexp;
     }
+    p.gate = pass.gate; // (a gated fallback)
+    p.gate_n = pass.gate_n;
     p.nqtiles = pl.nqtiles; p.nchunks = pl.nchunks; p.tiles_base = pl.tiles_base; p.tiles_rem = pl.tiles_rem;
     p.lists = (uint64_t *)h->ws_lists.p; p.gthr = gthr;
     p.qlist = qlist; p.qcnt = qcnt; p.qcap = qcap;
@@ -4577,7 +4579,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         HIP_TRY(hipGetLastError());
         p.xq_diff = (const float *)h->ws_qdiff.p;
     }
-    if (pl.nqtiles > 1 && !h->approx16 && pl.tiles_base >= 2 && pl.qt != 256 && !(h->flags & 256)) { // (turn taking: batch launches with real chunks, two workgroups per CU)
+    if (pl.nqtiles > 1 && !h->approx16 && pl.tiles_base >= 2 && pl.qt != 256 && !(h->flags & KNN_TUNE_NO_TURNS)) { // (turn taking: batch launches with real chunks, two workgroups per CU)
         if (h->ws_turn.ensure(2048 * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         if (h->turn_zeroed != h->ws_turn.p) { // (once per allocation: a fill in front of every launch was 10 us of idle GPU per CATH-sized search)
             HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
@@ -4585,8 +4587,8 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         }
         p.cu_turn = (uint32_t *)h->ws_turn.p;
     }
-    // the pool: about a tenth of every pair's tiles (none with flags & 2)
-    p.pool_tiles = pl.npairs && !(h->flags & 2) ? std::min(std::max(1, (pl.tiles_base + 5) / 10), pl.tiles_base / 4) : 0;
+    // the pool: about a tenth of every pair's tiles (none with KNN_TUNE_NO_POOL)
+    p.pool_tiles = pl.npairs && !(h->flags & KNN_TUNE_NO_POOL) ? std::min(std::max(1, (pl.tiles_base + 5) / 10), pl.tiles_base / 4) : 0;
 #ifdef KNN355_DEV
     if (p.pool_tiles && getenv("KNN355_POOL_PCT")) // (developer build: the pool's share of every pair's range, in percent)
         p.pool_tiles = std::min(std::max(1, pl.tiles_base * atoi(getenv("KNN355_POOL_PCT")) / 100), pl.tiles_base - 2);
@@ -4595,7 +4597,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         if (h->ws_defer.ensure((size_t)pl.grid * pl.qt * pl.dt * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         p.defer = (float *)h->ws_defer.p;
     }
-    const bool top = level == 0 && h->s16_mode != 2; // (a gated fallback leaves the introspection to the 16-bit pass)
+    const bool top = level == 0 && pass.mode != 2; // (a gated fallback leaves the introspection to the 16-bit pass)
 #ifdef KNN355_TRACE
     if (level == (getenv("KNN355_TRACE_LEVEL") ? atoi(getenv("KNN355_TRACE_LEVEL")) : 0)) { // (developer build: which seed level's launch is stamped)
         if (g_trace_buf.ensure((size_t)pl.grid * 128 * 8)) return set_err(KNN_ERR_HIP, "trace: out of device memory");
@@ -4616,16 +4618,16 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         h->nlaunches++;
         HIP_TRY(hipEventRecord(h->ev0, s));
     }
-    if (pl.qt == 256) rc = launch_scan_big(h, p, pl, s);
-    else if (pl.qt == 128) rc = launch_scan_cfg<2, 2, 2, 2>(h, p, pl, s);
-    else if (pl.qt == 96) rc = launch_scan16<2, 2, 2, 3>(h, p, pl, s);
-    else if (pl.qt == 48) rc = launch_scan16<4, 1, 2, 3>(h, p, pl, s);
-    else if (pl.qt == 64) rc = launch_scan_cfg<2, 2, 2, 1>(h, p, pl, s);
-    else rc = launch_scan_cfg<4, 1, 2, 1>(h, p, pl, s);
+    if (pl.qt == 256) rc = launch_scan_big(h, pass, p, pl, s);
+    else if (pl.qt == 128) rc = launch_scan_cfg<2, 2, 2, 2>(h, pass, p, pl, s);
+    else if (pl.qt == 96) rc = launch_scan16<2, 2, 2, 3>(h, pass, p, pl, s);
+    else if (pl.qt == 48) rc = launch_scan16<4, 1, 2, 3>(h, pass, p, pl, s);
+    else if (pl.qt == 64) rc = launch_scan_cfg<2, 2, 2, 1>(h, pass, p, pl, s);
+    else rc = launch_scan_cfg<4, 1, 2, 1>(h, pass, p, pl, s);
     if (rc) return rc;
     if (top) {
         HIP_TRY(hipEventRecord(h->ev1, s));
-        h->last_kernel = h->s16_mode == 1 ? std::string(pl.name) + "_f16x" : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
+        h->last_kernel = pass.mode == 1 ? std::string(pl.name) + "_f16x" : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
         h->last_seed_stride = pub_rounds ? -pub_rounds * pub_m : sstride; // (negative: tile-minimum seed, keys per workgroup and query)
         h->last_seed_stat = seed_stat ? seed_j : 0;
         h->last_sample_rows = sstride ? view_rows(nb, sstride, p.vshift) : 0;
@@ -4646,11 +4648,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     sp.seed_cnt = out.seed_cnt; sp.seed_gthr = out.seed_gthr; sp.seed_qthr = out.seed_qthr; sp.seed_j = out.seed_j; sp.seed_stat = out.seed_stat;
     sp.seed_nslots = out.seed_nslots;
     sp.qthr = qthr; sp.fail = (int *)h->ws_flag.p;
-    if (h->s16_mode == 2) {
-        sp.gate = h->s16_gate;
-        sp.gate_n = h->s16_gate_n;
-        sp.gate_count = h->s16_gate_count;
-    }
+    sp.gate = pass.gate; sp.gate_n = pass.gate_n; sp.gate_count = pass.gate_count;
     if (reset_sig && out.seed_cnt == nullptr) {
         sp.rs_gthr = gthr; sp.rs_qcnt = qcnt; sp.rs_qthr = qthr; sp.rs_nslots = (int)nslots;
         sp.rs_pub = (uint64_t *)lb.pub.p; sp.rs_pub_n = pub_rounds * pl.nchunks * pub_m;
@@ -4717,13 +4715,14 @@ static int search_keys_impl(knn_index_s *h, const float *q_dev, int64_t nq, int 
         int64_t q0, m;
     };
     std::vector<Piece> pieces;
-    const bool split = h->ntotal >= (1 << 18) && !h->force_qt && !(h->flags & 16384);
+    const bool split = h->ntotal >= (1 << 18) && !h->force_qt && !(h->flags & KNN_TUNE_NO_REMAINDER_SPLIT);
     // A database of 32 k .. 262 k rows has no sample pass to seed a 128-query launch with, and the 64-query build seeds
     // itself: a batch of 65..128 queries goes as two 64-query pieces (100 k rows x 100 queries: 0.56 -> 0.41 ms) -- unless the
     // statistical seed can serve the one launch (synchronous callers) and k is large: from k ~ 200 on the one seeded
     // 128-query launch is ahead (100 k rows x 128 queries, k = 1000: 0.53 ms against 0.85 in pieces; k = 100: 0.49 against 0.44).
     const bool split_small = !split && h->ntotal >= (1 << 15) && nq > 64 && nq <= 128 && !h->force_qt && !h->force_chunks && !h->approx16 &&
-                             !(h->flags & (8 | 16 | 128 | 2048 | 16384)) && (k <= 200 || !allow_stat || (h->flags & 512));
+                             tile_min_seed_allowed(h) && !(h->flags & KNN_TUNE_NO_REMAINDER_SPLIT) &&
+                             (k <= 200 || !allow_stat || (h->flags & KNN_TUNE_NO_STAT_SEED));
     for (int64_t b = 0; b < nblocks; b++) {
         int64_t q0 = b * QB, m = nblocks == 1 ? nq : std::min(QB, nq - q0);
         if (split_small) {
@@ -4736,7 +4735,7 @@ static int search_keys_impl(knn_index_s *h, const float *q_dev, int64_t nq, int 
         // A batch the 256 x 256 tile serves (big_tile_pays; synchronous callers: it needs the statistical seed) whose full tiles
         // end in half a 256-query tile: that half goes with the remainder, on the 128 x 128 tile -- 10 M rows x 640 queries:
         // 512 on the wide tile + 128 on the narrow one, not three wide query tiles of which one is half empty.
-        const bool may_big = (allow_stat && !(h->flags & (8 | 16 | 512))) || (h->flags & 524288);
+        const bool may_big = (allow_stat && stat_seed_allowed(h)) || (h->flags & KNN_TUNE_BIG_TILE);
         if (split && may_big && !h->force_chunks && full % 256 == 128 && full >= 384 && big_tile_pays(h, h->ntotal, full - 128)) {
             pieces.push_back({q0, full - 128});
             q0 += full - 128;
@@ -4745,7 +4744,7 @@ static int search_keys_impl(knn_index_s *h, const float *q_dev, int64_t nq, int 
         }
         // (round 4: 33..48 and 65..96 queries have builds of their own width -- 16-query blocks, make_plan -- so a remainder of
         // up to 96 queries is one piece: 10 M rows x 80 queries: 18.7 ms as 64 + 16, ~16 as one 96-query pass)
-        const bool q96 = !h->approx16 && !(h->flags & 131072);
+        const bool q96 = !h->approx16 && !(h->flags & KNN_TUNE_NO_Q16);
         if (!split || m <= 64 || r == 0 || r > 96 || (r > 64 && full && !q96) || (!full && q96)) { // (without the 96-query build: 65..96 behind full tiles cost two narrow passes what the padded tile does)
             pieces.push_back({q0, m});
             continue;
@@ -4925,7 +4924,7 @@ static int sym_stat_stride(int64_t n)
 static bool self_search_symmetric_eligible(const knn_index_s *h, int k, int *j_out = nullptr, int *qcap_out = nullptr)
 {
     const int64_t n = h->ntotal;
-    if (n < dev_knob("KNN355_SYM_MIN_N", 3000) || k > KNN_REGISTER_SELECT_MAX_K || k >= n || (h->flags & (8 | 16 | 512 | 1024)) || h->force_qt || h->force_chunks || h->approx16) return false;
+    if (n < dev_knob("KNN355_SYM_MIN_N", 3000) || k > KNN_REGISTER_SELECT_MAX_K || k >= n || !stat_seed_allowed(h) || (h->flags & KNN_TUNE_NO_SYM) || h->force_qt || h->force_chunks || h->approx16) return false;
     const int st = sym_stat_stride(n);
     const int64_t S = view_rows(n, st, 0);
     const int j = stat_seed_rank(S, n, k);
@@ -4954,10 +4953,10 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
     const int64_t S = view_rows(n, st, 0);
     const double expect = 1.3 * (double)j * (double)n / (double)S + 1.25 * k;
     ScanPlan pl;
-    // (tile shape, list capacity, LDS.  256-row tiles only on demand, flags & 524288: the symmetric launch filters every tile
+    // (tile shape, list capacity, LDS.  256-row tiles only on demand, KNN_TUNE_BIG_TILE: the symmetric launch filters every tile
     // twice and executes half the flops per row pair, its epilogue weighs twice as much beside the K loop -- Pfam-sized
     // k = 100 / 1000: 372.7 / 392.6 ms on 256-row tiles against 349.7 / 377.4 on 128-row tiles, one box)
-    make_plan(h, n, n, k, true, pl, false, (h->flags & 524288) != 0);
+    make_plan(h, n, n, k, true, pl, false, (h->flags & KNN_TUNE_BIG_TILE) != 0);
     if (pl.qt != pl.dt || (pl.qt != 128 && pl.qt != 256)) return 0;
     const int TS = pl.qt; // square tiles of 128 rows (two workgroups per CU) or 256 rows (one: flat_scan_kernel<2, 2, 4, 4>, large indexes)
     const int T = (int)((n + TS - 1) / TS);
@@ -5038,7 +5037,7 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
     p.id_base = 0; p.row_mul = 1; p.vshift = 0; p.skip_mask = st - 1;
     p.kslot = knn_kslot(k);
     p.fail = (int *)h->ws_flag.p;
-    if (!(h->flags & 256) && TS == 128) {
+    if (!(h->flags & KNN_TUNE_NO_TURNS) && TS == 128) {
         if (h->ws_turn.ensure(2048 * 4)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
         if (h->turn_zeroed != h->ws_turn.p) {
             HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
@@ -5567,8 +5566,8 @@ extern "C" int knn_set_tuning(knn_handle h, int32_t query_tile, int32_t nchunks,
     std::lock_guard<std::mutex> lk(h->mu);
     h->force_qt = query_tile;
     h->force_chunks = nchunks;
-    h->flags = flags & ~(3 << 12); // (bit 17 = 131072: plans without the 16-query-block builds, see make_plan)
-    h->pub_rounds_force = (flags >> 12) & 3; // bits 12-13: publication rounds of the tile-minimum seed (0: the host's choice)
+    h->flags = flags & ~KNN_TUNE_PUB_ROUNDS_MASK;
+    h->pub_rounds_force = (flags & KNN_TUNE_PUB_ROUNDS_MASK) >> KNN_TUNE_PUB_ROUNDS_SHIFT; // (0: the host's choice)
     return 0;
 }
 

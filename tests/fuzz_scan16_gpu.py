@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer fuzz of the exact 16-bit prefilter (knn_flat_set_scan16): every case searches one index with
-the prefilter forced on ("whatever nb" tuning bit) and with it off ("never" bit) and compares D / I bit for bit, and
+the prefilter forced on (KNN_TUNE_SCAN16_ANY_NB) and with it off (KNN_TUNE_NO_SCAN16) and compares D / I bit for bit, and
 against the CPU oracle.  Random shapes, k, batch sizes and data kinds: gaussian, L2-normalised, rows scaled by powers
 of two up to 2^+-40, magnitudes mixed inside rows, duplicated and zero rows, near-duplicates of a query that fp16 cannot
 tell apart (the device fallback), constant rows.  usage: fuzz_scan16_gpu.py [ncases] [seed]"""
@@ -13,9 +13,9 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from knn_for_homology_amd import faiss  # noqa: E402
+from knn_for_homology_amd._lib import KNN_TUNE_NO_SCAN16, KNN_TUNE_SCAN16_ANY_NB  # noqa: E402
 from oracle import knn_oracle as ko  # noqa: E402
 
-NEVER, ANY_NB = 1 << 20, 1 << 21
 KINDS = ("gauss", "normed", "scaled", "mixed", "dups", "near", "const")
 
 
@@ -59,10 +59,10 @@ def run(ncases=1000, seed=1):
         idx.set_scan16(1)
         idx.add(xb)
         fb0 = idx.last_scan16()["fallbacks"]
-        idx.set_tuning(0, 0, ANY_NB)
+        idx.set_tuning(0, 0, KNN_TUNE_SCAN16_ANY_NB)
         D, I = idx.search(xq, k)
         info = idx.last_scan16()
-        idx.set_tuning(0, 0, NEVER)
+        idx.set_tuning(0, 0, KNN_TUNE_NO_SCAN16)
         D0, I0 = idx.search(xq, k)
         Do, Io = orc.flat_search(xb, xq, k, faiss.METRIC_INNER_PRODUCT)
         ok = (np.array_equal(I, I0) and np.array_equal(D.view(np.uint32), D0.view(np.uint32))

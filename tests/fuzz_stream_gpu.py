@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer fuzz of the STREAMING regime (few queries, >= 131 k rows: paired workgroups, shared pool of tiles,
-tile-minimum seed, batches searched in pieces) against the CPU oracle, bit for bit.  Random shapes / metrics / k / tuning flags (2 = no pool, 4 = no
-pairs, 2048 = sample pass instead of the tile-minimum seed, 8 = no seeding at all, bits 12-13 = publication rounds) and
+tile-minimum seed, batches searched in pieces) against the CPU oracle, bit for bit.  Random shapes / metrics / k / tuning flags (KNN_TUNE_NO_POOL,
+KNN_TUNE_NO_PAIRS, KNN_TUNE_NO_TILE_MIN_SEED = sample pass instead of the tile-minimum seed, KNN_TUNE_NO_SEED, publication rounds) and
 data kinds (gaussian, massive ties, duplicated rows, sorted so that every tile beats the previous one, constant rows,
 the best rows packed into one tile).  usage: fuzz_stream_gpu.py [ncases] [seed]"""
 import sys
@@ -13,6 +13,8 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from knn_for_homology_amd import faiss  # noqa: E402
+from knn_for_homology_amd._lib import (KNN_TUNE_NO_PAIRS, KNN_TUNE_NO_POOL, KNN_TUNE_NO_REMAINDER_SPLIT, KNN_TUNE_NO_SEED,  # noqa: E402
+                                       KNN_TUNE_NO_TILE_MIN_SEED, KNN_TUNE_PUB_ROUNDS_SHIFT)
 from oracle import knn_oracle as ko  # noqa: E402
 
 
@@ -32,12 +34,13 @@ def run(ncases=40, seed=1, budget_s=None):
         nq = int(rng.choice([1, 2, 7, 31, 32, 33, 41, 48, 64]))
         k = int(rng.choice([1, 2, 10, 64, 100, 101, 200, 256, 481, 600, 1000, 1536, 1537, 1800, 2048]))
         metric = int(rng.integers(0, 2))
-        flags = int(rng.choice([0, 0, 0, 2, 4, 2048, 2048 | 4, 8, 1 << 12, 2 << 12]))
+        flags = int(rng.choice([0, 0, 0, KNN_TUNE_NO_POOL, KNN_TUNE_NO_PAIRS, KNN_TUNE_NO_TILE_MIN_SEED, KNN_TUNE_NO_TILE_MIN_SEED | KNN_TUNE_NO_PAIRS,
+                                 KNN_TUNE_NO_SEED, 1 << KNN_TUNE_PUB_ROUNDS_SHIFT, 2 << KNN_TUNE_PUB_ROUNDS_SHIFT]))
         if rng.integers(0, 5) == 0:  # a batch searched in pieces (the remainder behind the full 128-query tiles on its own)
             nq = int(rng.choice([65, 81, 96, 129, 150, 161, 170, 193, 224, 257]))
             k = min(k, 256)
             d = min(d, 32)
-            flags = int(rng.choice([0, 0, 16384, 2048]))
+            flags = int(rng.choice([0, 0, KNN_TUNE_NO_REMAINDER_SPLIT, KNN_TUNE_NO_TILE_MIN_SEED]))
         kind = int(rng.integers(0, 6))
         if kind == 0:
             xb = rng.standard_normal((nb, d), dtype=np.float32)

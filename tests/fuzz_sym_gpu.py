@@ -10,6 +10,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from knn_for_homology_amd import faiss  # noqa: E402
+from knn_for_homology_amd._lib import KNN_TUNE_BIG_TILE, KNN_TUNE_NO_SYM  # noqa: E402
 from oracle import knn_oracle as ko  # noqa: E402
 
 
@@ -46,10 +47,10 @@ def run(ncases=40, seed=1, budget_s=None):
         idx = faiss.IndexFlat(d, metric)
         idx.add(x)
         if rng.integers(0, 4) == 0:
-            idx.set_tuning(0, 0, 524288)  # (the symmetric launch on 256-row tiles)
+            idx.set_tuning(0, 0, KNN_TUNE_BIG_TILE)  # (the symmetric launch on 256-row tiles)
         D, I = idx.search_self(k)
         kern, seedinfo = idx.last_scan()["kernel"], idx.last_seed()
-        idx.set_tuning(0, 0, 1024)
+        idx.set_tuning(0, 0, KNN_TUNE_NO_SYM)
         Dp, Ip = idx.search_self(k)
         sample = rng.choice(n, 16, replace=False)
         Do, Io = orc.flat_search(x, x[sample], k, metric, l2_mode=1)  # (the search was one big batch: the norm formula)

@@ -115,13 +115,13 @@ def main():
     # seeded (recursive) searches: big enough that the strided sample kicks in
     xb6 = rng.standard_normal((40000, 128), dtype=np.float32)
     xq6 = rng.standard_normal((70, 128), dtype=np.float32)
-    case("seeded 40k d=128 k=10", xb6, xq6, 10, 0, flags=16)
-    case("seeded 40k d=128 k=100 l2", xb6, xq6, 100, 1, flags=16)
-    case("seeded 40k d=128 k=100 q32", xb6, xq6[:20], 100, 0, flags=16)
+    case("seeded 40k d=128 k=10", xb6, xq6, 10, 0, flags=_lib.KNN_TUNE_EXACT_SEED)
+    case("seeded 40k d=128 k=100 l2", xb6, xq6, 100, 1, flags=_lib.KNN_TUNE_EXACT_SEED)
+    case("seeded 40k d=128 k=100 q32", xb6, xq6[:20], 100, 0, flags=_lib.KNN_TUNE_EXACT_SEED)
     case("auto 40k d=128 k=10 q32", xb6, xq6[:20], 10, 0)
-    case("unseeded (flags=8) same", xb6, xq6, 100, 1, flags=8)
+    case("unseeded (KNN_TUNE_NO_SEED) same", xb6, xq6, 100, 1, flags=_lib.KNN_TUNE_NO_SEED)
     xb7 = np.sort(rng.standard_normal((30000, 64), dtype=np.float32), axis=0)  # adversarial order
-    case("sorted columns 30k d=64", xb7, xb7[::500].copy(), 50, 1, flags=16)
+    case("sorted columns 30k d=64", xb7, xb7[::500].copy(), 50, 1, flags=_lib.KNN_TUNE_EXACT_SEED)
     print("FAILS:", fails)
     return 1 if fails else 0
 

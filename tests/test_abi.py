@@ -26,6 +26,33 @@ def test_library_exports_every_declared_symbol():
     assert set(names) <= set(_lib.EXPORTS), set(names) - set(_lib.EXPORTS)
 
 
+def _header_tuning_flags():
+    """name -> value of every KNN_TUNE_* enumerator in include/knn355.h (values: integers, <<, |)."""
+    text = (ROOT / "include" / "knn355.h").read_text()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    flags = {}
+    for body in re.findall(r"enum\s*\{(.*?)\}", text, flags=re.S):
+        for item in body.split(","):
+            m = re.fullmatch(r"\s*(KNN_TUNE_[A-Z0-9_]+)\s*=\s*([0-9<| ()]+?)\s*", item)
+            if m:
+                assert m.group(1) not in flags, f"{m.group(1)} defined twice"
+                flags[m.group(1)] = eval(m.group(2), {"__builtins__": {}})
+            else:
+                assert "KNN_TUNE_" not in item, f"unparsed enumerator {item.strip()!r}"
+    return flags
+
+
+def test_tuning_flags_match_the_header():
+    """knn_set_tuning's flag names and values in _lib.py are those of the header's enum, in both directions."""
+    from knn_for_homology_amd import _lib
+    header = _header_tuning_flags()
+    assert len(header) >= 19
+    python = {n: getattr(_lib, n) for n in dir(_lib) if n.startswith("KNN_TUNE_")}
+    assert set(python) == set(header), (set(header) - set(python), set(python) - set(header))
+    for name, value in header.items():
+        assert python[name] == value, f"{name}: header {value}, _lib.py {python[name]}"
+
+
 def test_version_and_device_count_need_no_gpu():
     from knn_for_homology_amd import _lib
     L = _lib.lib()

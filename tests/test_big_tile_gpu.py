@@ -1,14 +1,14 @@
 """GPU parity tests of the 256 x 256 tile (flat_scan_kernel<2, 2, 4, 4>: one workgroup per CU, the accumulators of a wave's
 128 x 128 scores in AGPRs, the late-barrier K loop): the batch regime's build for Pfam-sized searches.  The plan picks it by
-itself for long chunks only (make_plan / big_tile_pays); here it is FORCED (set_tuning query_tile = 256, or flags 524288 --
+itself for long chunks only (make_plan / big_tile_pays); here it is FORCED (set_tuning query_tile = 256, or KNN_TUNE_BIG_TILE --
 the symmetric self-search ignores a forced tile) onto small shapes and compared bit for bit with the CPU oracle and with the
-128 x 128 build (flags 262144: never the 256 tile).  Every distance is one fma chain whatever the tile: same bits."""
+128 x 128 build (KNN_TUNE_NO_BIG_TILE: never the 256 tile).  Every distance is one fma chain whatever the tile: same bits."""
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from knn_for_homology_amd._lib import KNN_TUNE_BIG_TILE, KNN_TUNE_NO_BIG_TILE, KNN_TUNE_NO_SEED, KNN_TUNE_NO_SYM, KNN_TUNE_STAT_SEED
 
-BIG, NOBIG = 524288, 262144
+pytestmark = pytest.mark.gpu
 
 
 def _bits(a):
@@ -49,12 +49,12 @@ def test_big_tile_vs_oracle(gpu_faiss, oracle, nq, nb, d, k, nch, metric):
     Do, Io = oracle.flat_search(xb, xq, k, metric)
     _assert_same(D, I, Do, Io)
     # the flag form (what a whole-index self-search honours), unseeded and under a forced statistical seed
-    for flags in (BIG, BIG | 8, BIG | 128):
+    for flags in (KNN_TUNE_BIG_TILE, KNN_TUNE_BIG_TILE | KNN_TUNE_NO_SEED, KNN_TUNE_BIG_TILE | KNN_TUNE_STAT_SEED):
         idx.set_tuning(0, nch, flags)
         D2, I2 = idx.search(xq, k)
         assert idx.last_scan()["query_tile"] == (256 if nb >= 1024 else 128)  # (the flag spares tiny databases: seed samples)
         _assert_same(D2, I2, Do, Io)
-    idx.set_tuning(0, nch, NOBIG)
+    idx.set_tuning(0, nch, KNN_TUNE_NO_BIG_TILE)
     D3, I3 = idx.search(xq, k)
     assert idx.last_scan()["query_tile"] != 256
     _assert_same(D3, I3, Do, Io)
@@ -102,14 +102,14 @@ def test_symmetric_self_search_on_big_tiles(gpu_faiss, oracle, n, d, k, metric):
     x[2000:2050] = x[1950:2000]
     idx = gpu_faiss.IndexFlat(d, metric)
     idx.add(x)
-    idx.set_tuning(0, 0, BIG)
+    idx.set_tuning(0, 0, KNN_TUNE_BIG_TILE)
     D, I = idx.search_self(k)
     assert idx.last_scan()["kernel"] == "flat_scan_q256_d256_sym" and idx.last_seed()["stat_rank"] > 0, idx.last_scan()
-    idx.set_tuning(0, 0, NOBIG)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_BIG_TILE)
     D1, I1 = idx.search_self(k)
     assert idx.last_scan()["kernel"] == "flat_scan_q128_d128_sym"
     _assert_same(D, I, D1, I1)
-    idx.set_tuning(0, 0, BIG | 1024)
+    idx.set_tuning(0, 0, KNN_TUNE_BIG_TILE | KNN_TUNE_NO_SYM)
     Dp, Ip = idx.search_self(k)
     assert idx.last_scan()["kernel"] == "flat_scan_q256_d256"
     _assert_same(D, I, Dp, Ip)
@@ -131,7 +131,7 @@ def test_symmetric_big_tiles_repair_a_failed_estimate(gpu_faiss, oracle):
     x[near] = base[None, :] + 0.05 * rng.standard_normal((near.size, d)).astype(np.float32)
     idx = gpu_faiss.IndexFlat(d, 0)
     idx.add(x)
-    idx.set_tuning(0, 0, BIG)
+    idx.set_tuning(0, 0, KNN_TUNE_BIG_TILE)
     before = idx.last_seed()["stat_redo"]
     D, I = idx.search_self(k)
     assert idx.last_seed()["stat_redo"] > before
@@ -149,7 +149,7 @@ def test_half_a_wide_query_tile_goes_with_the_remainder(gpu_faiss, oracle):
     xb[200_000:200_050] = xb[:50]
     idx = gpu_faiss.IndexFlat(d, 0)
     idx.add(xb)
-    idx.set_tuning(0, 0, BIG)
+    idx.set_tuning(0, 0, KNN_TUNE_BIG_TILE)
     for nq, last_tile in ((512, 256), (640, 128), (936, 48), (1024, 256)):
         xq = rng.standard_normal((nq, d), dtype=np.float32)
         xq[:3] = xb[:3]

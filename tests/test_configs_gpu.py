@@ -195,9 +195,9 @@ def test_gather_distances_matches_oracle(gpu_faiss, oracle, metric):
     qidx = np.repeat(np.arange(nq), counts).astype(np.int32)
     want = oracle.pair_distances(xb, xq, qidx, cand, metric)
     assert np.array_equal(_bits(out), _bits(want))
-    # ... which are the flat search's distances for those pairs (the norm formula: flags 32 -- a 9-query L2 search would
+    # ... which are the flat search's distances for those pairs (the norm formula: KNN_TUNE_NORM_L2 -- a 9-query L2 search would
     # otherwise return FAISS's small-batch sum of squared differences)
-    idx.set_tuning(0, 0, 32)
+    idx.set_tuning(0, 0, _lib.KNN_TUNE_NORM_L2)
     D, I = idx.search(xq, 2048)
     for i in (2, 3, 6):
         ref = dict(zip(I[i].tolist(), _bits(D[i]).tolist()))

@@ -6,6 +6,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, DATASETS
+from knn_for_homology_amd._lib import (KNN_TUNE_ALWAYS_RESET, KNN_TUNE_EXACT_SEED, KNN_TUNE_NO_PAIRS, KNN_TUNE_NO_POOL,
+                                       KNN_TUNE_NO_Q16, KNN_TUNE_NO_REMAINDER_SPLIT, KNN_TUNE_NO_SEED, KNN_TUNE_NO_SYM,
+                                       KNN_TUNE_NO_TILE_MIN_SEED, KNN_TUNE_NORM_L2, KNN_TUNE_PUB_ROUNDS_SHIFT, KNN_TUNE_STAT_SEED)
 
 pytestmark = pytest.mark.gpu
 
@@ -161,7 +164,7 @@ def test_random_vs_oracle(gpu_faiss, oracle, nq, nb, d, k, qt, nch, metric):
 def test_sixteen_query_block_builds_vs_oracle(gpu_faiss, oracle, nq, nb, d, k, nch, metric):
     """a query tile costs its whole width -- 33 queries paid for 64, 65 for 128.  The 48- and 96-query
     tiles are built from 16 x 16 x 4 MFMAs (the same k-ordered fma chain: every bit as before).  The plan picks them by itself;
-    flags 131072 switches them off: the same bits either way."""
+    KNN_TUNE_NO_Q16 switches them off: the same bits either way."""
     rng = np.random.default_rng(nq * 7919 + nb + d + k)
     xb = rng.standard_normal((nb, d), dtype=np.float32)
     xb[nb // 2: nb // 2 + 5] = xb[:5]  # exact duplicates: ties -> lower id
@@ -175,7 +178,7 @@ def test_sixteen_query_block_builds_vs_oracle(gpu_faiss, oracle, nq, nb, d, k, n
     assert idx.last_scan()["query_tile"] == (32 if in_pieces else (48 if nq <= 48 else 96)), idx.last_scan()
     Do, Io = oracle.flat_search(xb, xq, k, metric)
     _assert_same(D, I, Do, Io)
-    idx.set_tuning(0, nch, 131072)
+    idx.set_tuning(0, nch, KNN_TUNE_NO_Q16)
     D2, I2 = idx.search(xq, k)
     assert idx.last_scan()["query_tile"] in (32, 64, 128)
     _assert_same(D2, I2, Do, Io)
@@ -187,7 +190,7 @@ def test_sixteen_query_block_builds_vs_oracle(gpu_faiss, oracle, nq, nb, d, k, n
 
 def test_remainders_behind_full_query_tiles_use_their_own_width(gpu_faiss, oracle):
     """128 k + r queries on a database that is streamed from HBM: the remainder r is searched with the narrowest build that
-    holds it (32 / 48 / 64 / 96 queries); the pieces return the bits of one launch (flags 16384)."""
+    holds it (32 / 48 / 64 / 96 queries); the pieces return the bits of one launch (KNN_TUNE_NO_REMAINDER_SPLIT)."""
     rng = np.random.default_rng(5)
     nb, d, k = 300_000, 32, 20
     xb = rng.standard_normal((nb, d), dtype=np.float32)
@@ -198,7 +201,7 @@ def test_remainders_behind_full_query_tiles_use_their_own_width(gpu_faiss, oracl
         idx.set_tuning(0, 0, 0)
         D, I = idx.search(xq, k)
         assert idx.last_scan()["query_tile"] == tile, (nq, idx.last_scan())
-        idx.set_tuning(0, 0, 16384)
+        idx.set_tuning(0, 0, KNN_TUNE_NO_REMAINDER_SPLIT)
         D1, I1 = idx.search(xq, k)
         _assert_same(D, I, D1, I1)
         Do, Io = oracle.flat_search(xb, xq[-8:], k, 0)
@@ -239,7 +242,7 @@ def test_sorted_database_never_overflows_lists(gpu_faiss, oracle, k, nq, metric)
     idx = gpu_faiss.IndexFlat(d, metric)
     idx.add(xb)
     for nch in (1, 0):
-        idx.set_tuning(0, nch, 8)  # no seeding: the lists warm up on their own
+        idx.set_tuning(0, nch, KNN_TUNE_NO_SEED)  # no seeding: the lists warm up on their own
         D, I = idx.search(xq, k)
         _assert_same(D, I, *oracle.flat_search(xb, xq, k, metric))
 
@@ -247,14 +250,14 @@ def test_sorted_database_never_overflows_lists(gpu_faiss, oracle, k, nq, metric)
 @pytest.mark.parametrize("metric", [0, 1])
 @pytest.mark.parametrize("k", [10, 100, 301])
 def test_statistical_seed_matches_oracle(gpu_faiss, oracle, k, metric):
-    """flags=128 forces the statistical seed (batch regime: threshold = j-th score of a strided sample, j << k,
+    """KNN_TUNE_STAT_SEED forces the statistical seed (batch regime: threshold = j-th score of a strided sample, j << k,
     result verified against it): same bits as the oracle, through the host entry and through search_self."""
     rng = np.random.default_rng(100 + k)
     nb, d, nq = 20000, 64, 300
     xb = rng.standard_normal((nb, d), dtype=np.float32)
     xq = np.concatenate([rng.standard_normal((nq - 40, d), dtype=np.float32), xb[:40]])
     idx = gpu_faiss.IndexFlat(d, metric)
-    idx.set_tuning(0, 0, 128)
+    idx.set_tuning(0, 0, KNN_TUNE_STAT_SEED)
     idx.add(xb)
     D, I = idx.search(xq, k)
     seed = idx.last_seed()
@@ -312,7 +315,7 @@ def test_statistical_seed_failure_is_caught_and_repaired(gpu_faiss, oracle, metr
     xb[near] = base[None, :] + 0.05 * rng.standard_normal((near.size, d)).astype(np.float32)
     xq = (base[None, :] + 0.05 * rng.standard_normal((nq, d))).astype(np.float32)
     idx = gpu_faiss.IndexFlat(d, metric)
-    idx.set_tuning(0, 0, 128)
+    idx.set_tuning(0, 0, KNN_TUNE_STAT_SEED)
     idx.add(xb)
     before = idx.last_seed()["stat_redo"]
     D, I = idx.search(xq, k)
@@ -327,11 +330,11 @@ def test_statistical_seed_failure_is_caught_and_repaired(gpu_faiss, oracle, metr
     _assert_same(D2[-100:], I2[-100:], *oracle.flat_search(xb, xq2[-100:], k, metric))
 
 
-@pytest.mark.parametrize("flags", [8, 16, 0])
+@pytest.mark.parametrize("flags", [KNN_TUNE_NO_SEED, KNN_TUNE_EXACT_SEED, 0])
 def test_long_candidate_arrays_take_the_segment_pass(gpu_faiss, oracle, flags):
     """Few queries against many rows: hundreds of chunks hand on their survivors, the per-query candidate arrays are
-    sized for more than 32768 keys and the final selection runs its segment pass first (flags=8: unseeded, arrays
-    really that long; 16: exact seed; 0: whatever the plan picks)."""
+    sized for more than 32768 keys and the final selection runs its segment pass first (KNN_TUNE_NO_SEED: unseeded, arrays
+    really that long; KNN_TUNE_EXACT_SEED: exact seed; 0: whatever the plan picks)."""
     rng = np.random.default_rng(900 + flags)
     nb, d, nq, k = 300_000, 32, 5, 100
     xb = rng.standard_normal((nb, d), dtype=np.float32)
@@ -390,7 +393,7 @@ def test_large_results_live_in_page_locked_memory(gpu_faiss, oracle):
 @pytest.mark.parametrize("n,d,k", [(9000, 64, 10), (14433, 128, 301), (20011, 32, 1000)])
 def test_symmetric_self_search_matches_plain_and_oracle(gpu_faiss, oracle, n, d, k, metric):
     """search_self over the whole index multiplies only the score tiles on and above the diagonal (every tile serves the
-    queries of its row tile and of its column tile); flags=1024 forces the plain launch.  Same bits, with duplicates,
+    queries of its row tile and of its column tile); KNN_TUNE_NO_SYM forces the plain launch.  Same bits, with duplicates,
     a ragged last tile and k up to 1000; oracle bits on sampled rows."""
     rng = np.random.default_rng(n + k)
     x = rng.standard_normal((n, d), dtype=np.float32)
@@ -400,7 +403,7 @@ def test_symmetric_self_search_matches_plain_and_oracle(gpu_faiss, oracle, n, d,
     idx.add(x)
     D, I = idx.search_self(k)
     assert idx.last_scan()["kernel"] == "flat_scan_q128_d128_sym" and idx.last_seed()["stat_rank"] > 0
-    idx.set_tuning(0, 0, 1024)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_SYM)
     Dp, Ip = idx.search_self(k)
     assert idx.last_scan()["kernel"] == "flat_scan_q128_d128"
     _assert_same(D, I, Dp, Ip)
@@ -505,14 +508,14 @@ def test_exact_duplicates_break_ties_by_lower_id(gpu_faiss, oracle):
 
 @pytest.mark.parametrize("metric", [0, 1])
 def test_seeded_search_matches_oracle(gpu_faiss, oracle, metric):
-    """flags=16 forces the recursive strided-sample seeding (normally reserved for the
-    streaming regime); flags=8 disables it.  Both must return the oracle's bits, also on a
+    """KNN_TUNE_EXACT_SEED forces the recursive strided-sample seeding (normally reserved for the
+    streaming regime); KNN_TUNE_NO_SEED disables it.  Both must return the oracle's bits, also on a
     database sorted so that every new tile beats the previous ones."""
     rng = np.random.default_rng(31)
     xb = rng.standard_normal((40000, 128), dtype=np.float32)
     xq = rng.standard_normal((70, 128), dtype=np.float32)
     Do, Io = oracle.flat_search(xb, xq, 100, metric)
-    for flags, nq in ((16, 70), (16, 20), (8, 70), (0, 20)):
+    for flags, nq in ((KNN_TUNE_EXACT_SEED, 70), (KNN_TUNE_EXACT_SEED, 20), (KNN_TUNE_NO_SEED, 70), (0, 20)):
         idx = gpu_faiss.IndexFlat(128, metric)
         idx.set_tuning(0, 0, flags)
         idx.add(xb)
@@ -521,7 +524,7 @@ def test_seeded_search_matches_oracle(gpu_faiss, oracle, metric):
     xs = np.sort(rng.standard_normal((30000, 64), dtype=np.float32), axis=0)
     q = xs[::500].copy()
     idx = gpu_faiss.IndexFlat(64, metric)
-    idx.set_tuning(0, 0, 16)
+    idx.set_tuning(0, 0, KNN_TUNE_EXACT_SEED)
     idx.add(xs)
     _assert_same(*idx.search(q, 50), *oracle.flat_search(xs, q, 50, metric))
 
@@ -538,7 +541,7 @@ def test_seed_sample_blocks_with_ragged_tail(gpu_faiss, oracle, nb):
     xq = np.concatenate([xb[planted], rng.standard_normal((9, d), dtype=np.float32)])
     for metric in (0, 1):
         Do, Io = oracle.flat_search(xb, xq, k, metric)
-        for flags in (16, 0):
+        for flags in (KNN_TUNE_EXACT_SEED, 0):
             idx = gpu_faiss.IndexFlat(d, metric)
             idx.set_tuning(0, 0, flags)
             idx.add(xb)
@@ -698,7 +701,7 @@ def test_full_size_10m_streaming(gpu_faiss, oracle):
     assert (np.diff(D, axis=1) <= 0).all() and I.min() >= 0 and I.max() < nb
     srt = np.sort(I, axis=1)
     assert (srt[:, 1:] != srt[:, :-1]).all()
-    for qt, nch, flags in ((0, 301, 8), (128, 0, 0)):
+    for qt, nch, flags in ((0, 301, KNN_TUNE_NO_SEED), (128, 0, 0)):
         idx.set_tuning(qt, nch, flags)
         D2, I2 = idx.search(q, k)
         _assert_same(D2, I2, D, I)
@@ -790,7 +793,7 @@ def test_device_search_of_many_queries_runs_in_blocks(gpu_faiss, oracle, metric)
 def test_tile_minimum_seed_matches_oracle(gpu_faiss, oracle, metric, nb, d, nq, k, rounds):
     """Few queries, many rows: the scan seeds itself (every chunk publishes the best key of its first tiles, the k-th
     smallest published key bounds the global k-th) instead of running a sample pass first.  Same bits as the oracle and
-    as the sample-pass build (flags 2048), with duplicates and ties in the data."""
+    as the sample-pass build (KNN_TUNE_NO_TILE_MIN_SEED), with duplicates and ties in the data."""
     rng = np.random.default_rng(nb + k)
     xb = rng.standard_normal((nb, d), dtype=np.float32)
     xb[nb // 2: nb // 2 + 300] = xb[:300]          # exact duplicates: ties on the score word
@@ -798,7 +801,7 @@ def test_tile_minimum_seed_matches_oracle(gpu_faiss, oracle, metric, nb, d, nq, 
     xq = np.concatenate([rng.standard_normal((max(nq - 2, 0), d), dtype=np.float32), xb[:min(2, nq)]])[:nq]
     idx = gpu_faiss.IndexFlat(d, metric)
     idx.add(xb)
-    idx.set_tuning(0, 0, rounds << 12)
+    idx.set_tuning(0, 0, rounds << KNN_TUNE_PUB_ROUNDS_SHIFT)
     D, I = idx.search(xq, k)
     seed = idx.last_seed()
     assert seed["stride"] < 0, f"expected the tile-minimum seed, got {seed} {idx.last_scan()}"
@@ -806,7 +809,7 @@ def test_tile_minimum_seed_matches_oracle(gpu_faiss, oracle, metric, nb, d, nq, 
         assert seed["stride"] == -rounds
     Do, Io = oracle.flat_search(xb, xq, k, metric)
     _assert_same(D, I, Do, Io)
-    idx.set_tuning(0, 0, 2048)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_TILE_MIN_SEED)
     D2, I2 = idx.search(xq, k)
     assert idx.last_seed()["stride"] >= 0
     _assert_same(D2, I2, Do, Io)
@@ -848,7 +851,7 @@ def test_tile_minimum_seed_with_one_key_per_wave_for_large_k(gpu_faiss, oracle, 
     _assert_same(D, I, Do, Io)
     D1, I1 = idx.search(xq, k)  # (back to back: the state the first search's selection left)
     _assert_same(D1, I1, Do, Io)
-    idx.set_tuning(0, 0, 2048)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_TILE_MIN_SEED)
     D2, I2 = idx.search(xq, k)
     assert idx.last_seed()["stride"] >= 0
     _assert_same(D2, I2, Do, Io)
@@ -874,7 +877,7 @@ def test_k_between_1537_and_2048_selects_by_probing_the_list(gpu_faiss, oracle, 
         assert idx.last_seed()["stride"] == seed, (idx.last_seed(), idx.last_scan())
     Do, Io = oracle.flat_search(xb, xq, k, metric)
     _assert_same(D, I, Do, Io)
-    for flags in (8, 2048, 4):
+    for flags in (KNN_TUNE_NO_SEED, KNN_TUNE_NO_TILE_MIN_SEED, KNN_TUNE_NO_PAIRS):
         idx.set_tuning(0, 0, flags)
         D2, I2 = idx.search(xq, k)
         _assert_same(D2, I2, Do, Io)
@@ -886,7 +889,7 @@ def test_short_streaming_launches_pair_and_seed_themselves(gpu_faiss, oracle, me
     """From two tiles per CU on (131 k rows with the 32-query tile, 66 k with the 64-query tile) a one-query-tile launch
     pairs its workgroups and seeds itself: every pair shares 2-8 tiles, a workgroup may walk a single one (whose parked
     scores it filters on the spot).  Shards of a 1-4 M-row database on eight GPUs are this size.  Same bits as the
-    oracle, as static chunks (flags 4), as the sample pass (2048) and unseeded (8)."""
+    oracle, as static chunks (KNN_TUNE_NO_PAIRS), as the sample pass (KNN_TUNE_NO_TILE_MIN_SEED) and unseeded (KNN_TUNE_NO_SEED)."""
     rng = np.random.default_rng(nb + k)
     xb = rng.standard_normal((nb, d), dtype=np.float32)
     xb[nb // 2: nb // 2 + 200] = xb[:200]
@@ -902,7 +905,7 @@ def test_short_streaming_launches_pair_and_seed_themselves(gpu_faiss, oracle, me
     _assert_same(D, I, Do, Io)
     D1, I1 = idx.search(xq, k)
     _assert_same(D1, I1, Do, Io)
-    for flags in (4, 2048, 8, 2):
+    for flags in (KNN_TUNE_NO_PAIRS, KNN_TUNE_NO_TILE_MIN_SEED, KNN_TUNE_NO_SEED, KNN_TUNE_NO_POOL):
         idx.set_tuning(0, 0, flags)
         D2, I2 = idx.search(xq, k)
         _assert_same(D2, I2, Do, Io)
@@ -911,7 +914,7 @@ def test_short_streaming_launches_pair_and_seed_themselves(gpu_faiss, oracle, me
 @pytest.mark.parametrize("metric", [0, 1])
 def test_batches_of_65_to_128_queries_on_a_mid_sized_database_go_as_two_pieces(gpu_faiss, oracle, metric):
     """32 k .. 262 k rows: no sample pass exists to seed a 128-query launch with, the 64-query build seeds itself -- the
-    batch is searched as two 64-query pieces.  Same bits as the one 128-query launch (flags 16384) and as the oracle."""
+    batch is searched as two 64-query pieces.  Same bits as the one 128-query launch (KNN_TUNE_NO_REMAINDER_SPLIT) and as the oracle."""
     rng = np.random.default_rng(65 + metric)
     nb, d, k = 100_000, 32, 40
     xb = rng.standard_normal((nb, d), dtype=np.float32)
@@ -926,7 +929,7 @@ def test_batches_of_65_to_128_queries_on_a_mid_sized_database_go_as_two_pieces(g
         rest = nq - 64  # (the second piece: the narrowest build that holds it)
         second = "flat_scan_q32_d256" if rest <= 32 else ("flat_scan_q48_d256" if rest <= 48 else "flat_scan_q64_d128")
         assert idx.last_scan()["kernel"] == ("flat_scan_q128_d128" if nq > 128 else ("flat_scan_q64_d128" if nq <= 64 else second)), (nq, idx.last_scan())
-        idx.set_tuning(0, 0, 16384)
+        idx.set_tuning(0, 0, KNN_TUNE_NO_REMAINDER_SPLIT)
         D1, I1 = idx.search(xq, k)
         assert idx.last_scan()["kernel"] == ("flat_scan_q128_d128" if nq > 96 else ("flat_scan_q96_d128" if nq > 64 else "flat_scan_q64_d128"))
         _assert_same(D, I, D1, I1)
@@ -938,7 +941,7 @@ def test_batches_of_65_to_128_queries_on_a_mid_sized_database_go_as_two_pieces(g
 def test_statistical_seed_serves_batches_from_65_queries_on(gpu_faiss, oracle, metric, nb, d, nq, k):
     """129 .. 1023 queries used to run unseeded, with few long chunks so that every chunk's warm-up was amortised (50 k rows
     x 256 queries, k = 1000: 38 workgroups, 2.4 ms); now the statistical seed (verified, repaired on failure) serves them
-    too: 0.52 ms.  Same bits as the oracle and as the unseeded search (flags 8)."""
+    too: 0.52 ms.  Same bits as the oracle and as the unseeded search (KNN_TUNE_NO_SEED)."""
     rng = np.random.default_rng(nb + nq + k)
     xb = rng.standard_normal((nb, d), dtype=np.float32)
     xb[nb // 3: nb // 3 + 400] = xb[:400]
@@ -950,7 +953,7 @@ def test_statistical_seed_serves_batches_from_65_queries_on(gpu_faiss, oracle, m
     assert idx.last_seed()["stat_rank"] > 0, (idx.last_seed(), idx.last_scan())
     Do, Io = oracle.flat_search(xb, xq, k, metric)
     _assert_same(D, I, Do, Io)
-    idx.set_tuning(0, 0, 8)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_SEED)
     D2, I2 = idx.search(xq, k)
     assert idx.last_seed()["stat_rank"] == 0
     _assert_same(D2, I2, Do, Io)
@@ -971,7 +974,7 @@ def test_symmetric_self_search_from_3000_rows_on(gpu_faiss, oracle, metric, n, d
     assert idx.last_scan()["kernel"].endswith("_sym") == (n >= 3000), idx.last_scan()
     Do, Io = oracle.flat_search(x, x, k, metric, l2_mode=1)
     _assert_same(D, I, Do, Io)
-    idx.set_tuning(0, 0, 1024)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_SYM)
     Dp, Ip = idx.search_self(k)
     assert not idx.last_scan()["kernel"].endswith("_sym")
     _assert_same(Dp, Ip, Do, Io)
@@ -1001,7 +1004,7 @@ def test_per_wave_publications_with_adversarial_order(gpu_faiss, oracle):
 def test_l2_small_batch_is_the_sum_of_squared_differences(gpu_faiss, oracle, nb, d, nq, k):
     """IndexFlat(d, METRIC_L2).search with fewer than 20 queries returns sum (x - y)^2 (FAISS's knn_L2sqr takes its SIMD
     path below distance_compute_blas_threshold = 20 [ext]; reachable through seqvec_search/main.py:22-45 with
-    metric=METRIC_L2): bit for bit the oracle's difference chain, in every seeding / pairing regime; flags=32 keeps the
+    metric=METRIC_L2): bit for bit the oracle's difference chain, in every seeding / pairing regime; KNN_TUNE_NORM_L2 keeps the
     norm formula."""
     rng = np.random.default_rng(nb + nq)
     xb = rng.standard_normal((nb, d), dtype=np.float32)
@@ -1013,7 +1016,7 @@ def test_l2_small_batch_is_the_sum_of_squared_differences(gpu_faiss, oracle, nb,
     assert idx.last_scan()["kernel"] == "flat_scan_q32_d256_l2diff"
     _assert_same(D, I, *oracle.flat_search(xb, xq, k, 1))
     assert (D[-1, 0] == 0.0) and I[-1, 0] == 0, "a row's distance to itself is exactly 0, the lower id of a duplicate first"
-    idx.set_tuning(0, 0, 32)
+    idx.set_tuning(0, 0, KNN_TUNE_NORM_L2)
     D2, I2 = idx.search(xq, k)
     assert idx.last_scan()["kernel"] == "flat_scan_q32_d256"
     _assert_same(D2, I2, *oracle.flat_search(xb, xq, k, 1, l2_mode=1))
@@ -1048,7 +1051,7 @@ def test_l2_formula_switches_at_twenty_queries(gpu_faiss, oracle):
 def test_streaming_searches_back_to_back_reuse_the_reset_state(gpu_faiss, oracle):
     """A streaming search whose predecessor had the same shape skips its state-reset launch (the predecessor's final
     selection left the thresholds, counts, publications and ticket counters reset).  Sequences of searches with changing
-    queries, batch sizes, k and metrics -- and the same sequence with the reset launch forced (flags 64) -- all return the
+    queries, batch sizes, k and metrics -- and the same sequence with the reset launch forced (KNN_TUNE_ALWAYS_RESET) -- all return the
     oracle's bits."""
     rng = np.random.default_rng(64)
     nb, d = 620_000, 32
@@ -1057,7 +1060,7 @@ def test_streaming_searches_back_to_back_reuse_the_reset_state(gpu_faiss, oracle
     qs = [rng.standard_normal((nq, d), dtype=np.float32) for nq in (32, 32, 32, 7, 7, 32, 1, 1, 64, 64, 32)]
     ks = [100, 100, 10, 10, 10, 100, 5, 5, 20, 20, 100]
     for metric in (0, 1):
-        for flags in (0, 64):
+        for flags in (0, KNN_TUNE_ALWAYS_RESET):
             idx = gpu_faiss.IndexFlat(d, metric)
             idx.add(xb)
             idx.set_tuning(0, 0, flags)
@@ -1117,7 +1120,7 @@ def test_l2_formula_follows_the_whole_batch_not_its_pieces(gpu_faiss, oracle):
     xs = rng.standard_normal((16384 + 7, 24), dtype=np.float32)
     s = gpu_faiss.IndexFlat(24, 1)
     s.add(xs)
-    s.set_tuning(0, 0, 1024)
+    s.set_tuning(0, 0, KNN_TUNE_NO_SYM)
     Ds, Is = s.search_self(4)
     Do, Io = oracle.flat_search(xs, xs[-40:], 4, 1)
     _assert_same(Ds[-40:], Is[-40:], Do, Io)
@@ -1128,7 +1131,7 @@ def test_l2_formula_follows_the_whole_batch_not_its_pieces(gpu_faiss, oracle):
 def test_remainder_behind_the_full_query_tiles_is_searched_on_its_own(gpu_faiss, oracle, metric):
     """On a database that is streamed from HBM the queries behind the last full 128-query tile are searched with the
     narrowest build that holds them (<= 32: streaming build, <= 48 / 64 / 96: the 48- / 64- / 96-query builds) instead of a padded
-    128-query tile.  Same bits as one launch (flags 16384) and as the oracle, whatever the split."""
+    128-query tile.  Same bits as one launch (KNN_TUNE_NO_REMAINDER_SPLIT) and as the oracle, whatever the split."""
     rng = np.random.default_rng(129 + metric)
     nb, d, k = 300_000, 32, 20
     xb = rng.standard_normal((nb, d), dtype=np.float32)
@@ -1147,7 +1150,7 @@ def test_remainder_behind_the_full_query_tiles_is_searched_on_its_own(gpu_faiss,
             return ("flat_scan_q32_d256" if m <= 32 else ("flat_scan_q48_d256" if m <= 48 else ("flat_scan_q64_d128" if m <= 64 else
                     ("flat_scan_q96_d128" if m <= 96 else "flat_scan_q128_d128"))))
         assert last == (build(r) if 0 < r <= 96 else "flat_scan_q128_d128"), (nq, last)
-        idx.set_tuning(0, 0, 16384)
+        idx.set_tuning(0, 0, KNN_TUNE_NO_REMAINDER_SPLIT)
         D1, I1 = idx.search(xq, k)
         assert idx.last_scan()["kernel"] == (build(nq) if nq <= 128 else "flat_scan_q128_d128")
         _assert_same(D, I, D1, I1)

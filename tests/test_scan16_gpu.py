@@ -1,13 +1,14 @@
 """GPU: the exact 16-bit prefilter (knn_flat_set_scan16) returns the fp32 scan's bits.
 
-Every search is compared bit for bit with the CPU oracle and with the same index under the "never" tuning bit; the
-"whatever nb" bit engages the path on databases small enough for the oracle."""
+Every search is compared bit for bit with the CPU oracle and with the same index under KNN_TUNE_NO_SCAN16; KNN_TUNE_SCAN16_ANY_NB
+engages the path on databases small enough for the oracle."""
 import numpy as np
 import pytest
 
+from knn_for_homology_amd._lib import KNN_TUNE_NO_SCAN16, KNN_TUNE_SCAN16_ANY_NB
+
 pytestmark = pytest.mark.gpu
 
-NEVER, ANY_NB = 1 << 20, 1 << 21
 IP, L2 = 0, 1
 
 
@@ -26,13 +27,13 @@ def _same(a, b):
 
 
 def _check(idx, xq, k, oracle=None, xb=None, expect_used=True):
-    idx.set_tuning(0, 0, ANY_NB)
+    idx.set_tuning(0, 0, KNN_TUNE_SCAN16_ANY_NB)
     got = idx.search(xq, k)
     info = idx.last_scan16()
     assert info["used"] == expect_used, info
     if expect_used:
         assert idx.last_scan()["kernel"] == "flat_scan_q32_d256_f16x", idx.last_scan()
-    idx.set_tuning(0, 0, NEVER)
+    idx.set_tuning(0, 0, KNN_TUNE_NO_SCAN16)
     ref = idx.search(xq, k)
     assert not idx.last_scan16()["used"]
     assert idx.last_scan()["kernel"] == "flat_scan_q32_d256", idx.last_scan()
@@ -98,7 +99,7 @@ def test_nonfinite_row_turns_the_path_off(gpu_faiss):
     _check(idx, xq, 10, expect_used=False)
     idx.reset()
     idx.add(np.ones((100, 64), dtype=np.float32))  # (a reset clears the flag: finite rows again)
-    idx.set_tuning(0, 0, ANY_NB)
+    idx.set_tuning(0, 0, KNN_TUNE_SCAN16_ANY_NB)
     idx.search(xq, 10)
     assert idx.last_scan16()["used"]
 
@@ -132,7 +133,7 @@ def test_growth_normalize_and_views(gpu_faiss, oracle):
     oracle.normalize_l2(xn)
     _check(idx, xq, 50, oracle, xn)
     v = idx.view()
-    v.set_tuning(0, 0, ANY_NB)
+    v.set_tuning(0, 0, KNN_TUNE_SCAN16_ANY_NB)
     got = v.search(xq, 50)
     assert v.last_scan16()["used"]
     assert _same(got, oracle.flat_search(xn, xq, 50, IP))
@@ -144,7 +145,7 @@ def test_refused_for_views_after_add_and_off_switch(gpu_faiss):
     with pytest.raises(Exception):
         idx.set_scan16(1)  # rows already there
     plain = _index(gpu_faiss, np.ones((300, 64), dtype=np.float32), on=False)
-    plain.set_tuning(0, 0, ANY_NB)
+    plain.set_tuning(0, 0, KNN_TUNE_SCAN16_ANY_NB)
     plain.search(np.ones((2, 64), dtype=np.float32), 5)
     assert not plain.last_scan16()["used"]
 
@@ -189,7 +190,7 @@ def test_reserve_then_view_then_add(gpu_faiss, oracle):
         old.search(xq, 10)  # the rows and their copies moved
     v = idx.view()
     idx.add(xb[10000:20000])  # fits the reservation: nothing moves
-    v.set_tuning(0, 0, ANY_NB)
+    v.set_tuning(0, 0, KNN_TUNE_SCAN16_ANY_NB)
     got = v.search(xq, 10)
     assert v.last_scan16()["used"]
     assert _same(got, oracle.flat_search(xb[:10000], xq, 10, IP))
@@ -213,7 +214,7 @@ def test_sharded_keys_prefiltered_without_fallback(gpu_faiss, oracle):
     keys = b.search_keys(q, 100, base).cpu().numpy()
     info = b.index.last_scan16()
     assert info["used"] and info["fallbacks"] == before, info
-    b.index.set_tuning(0, 0, NEVER)
+    b.index.set_tuning(0, 0, KNN_TUNE_NO_SCAN16)
     ref = b.search_keys(q, 100, base).cpu().numpy()
     b.index.set_tuning(0, 0, 0)
     assert np.array_equal(keys, ref)
@@ -245,6 +246,6 @@ def test_flagship_shape_10m(gpu_faiss):
     info = b.index.last_scan16()
     print(f"flagship shape: {info}")
     assert info["used"] and info["fallbacks"] == 0, info
-    b.index.set_tuning(0, 0, NEVER)
+    b.index.set_tuning(0, 0, KNN_TUNE_NO_SCAN16)
     ref = b.search_keys(q, 100, 0).cpu().numpy()
     assert np.array_equal(keys, ref)
