@@ -249,7 +249,8 @@ int knn_hnsw_stats(knn_hnsw_handle h, int64_t *pairs, int64_t *rounds, int64_t *
 /* ---- faiss.IndexLSH(d, nbits) -----------------------------------------------
  * seqvec_search/create_index.py:41-45, pfam/search.py:27-37, pfam/proteins_search.py:25-26.
  * rotation_host: [nbits][d] row-major projection rows (FAISS uses a random orthonormal
- * matrix from its own RNG; the caller supplies one).  Codes: bit j = (x . rot_j >= 0);
+ * matrix from its own RNG; the caller supplies one).  Codes: bit j = (x . rot_j >= 0), or
+ * (x . rot_j >= t_j) once thresholds are trained or set (below);
  * search returns the k smallest Hamming distances as float32, ties by lower id. */
 typedef struct knn_lsh_s *knn_lsh_handle;
 int knn_lsh_create(int32_t d, int32_t nbits, const float *rotation_host, knn_lsh_handle *out);
@@ -261,6 +262,24 @@ int32_t knn_lsh_code_words(knn_lsh_handle h);
 /* codes in FAISS byte order ([ntotal][bytes_per_vec], bit i -> byte i>>3, bit i&7; bits at and above nbits are 0) */
 int knn_lsh_get_codes(knn_lsh_handle h, uint8_t *out_host, int32_t bytes_per_vec);
 int knn_lsh_add_codes(knn_lsh_handle h, const uint8_t *codes_host, int64_t n, int32_t bytes_per_vec);
+/* IndexLSH(d, nbits, rotate_data, train_thresholds = true).train(x) -- every reference script calls train before add
+ * (seqvec_search/create_index.py:43, pfam/search.py:35, pfam/proteins_search.py:87).  FAISS 1.7.2 IndexLSH::train
+ * (published behaviour restated): the threshold of bit j is the median of x . rot_j over the n training rows (sorted
+ * s: s[n/2] for odd n, (s[n/2 - 1] + s[n/2]) / 2 in float for even n; -0.0 counts as +0.0), and codes become
+ * bit j = (x . rot_j >= t_j) for add and search alike.  Computes and installs the thresholds.  n < 1, a NaN projection
+ * or a NaN median: KNN_ERR_INVALID (the handle keeps what it had).  The n x (code bits padded to 128 * 2^i) float
+ * projections stay on the device for the call: more than half of the free device memory is KNN_ERR_UNSUPPORTED.
+ * FAISS lets a filled index be trained again and leaves its stale codes behind; here train and set_thresholds on a
+ * handle that holds rows are KNN_ERR_INVALID. */
+int knn_lsh_train(knn_lsh_handle h, const float *x_host, int64_t n);
+/* IndexLSH::thresholds as read_index finds them in an "IxHe" file: thr_host [nbits]; NULL removes them (bit j =
+ * (x . rot_j >= 0) again).  A NaN entry is KNN_ERR_INVALID. */
+int knn_lsh_set_thresholds(knn_lsh_handle h, const float *thr_host);
+/* IndexLSH::thresholds for write_index: out_host [nbits]; KNN_ERR_INVALID if the handle has none */
+int knn_lsh_get_thresholds(knn_lsh_handle h, float *out_host);
+/* measurement (tools/lsh_train_probe.py): HIP-event milliseconds of the last successful knn_lsh_train -- the slabs'
+ * uploads, their projection kernels, the median selection */
+int knn_lsh_last_train_ms(knn_lsh_handle h, float *upload_ms, float *project_ms, float *select_ms);
 void knn_lsh_free(knn_lsh_handle h);
 
 /* ---- consumers of (hits, scores): SURVEY section 8(f) N4 --------------------------

@@ -111,6 +111,10 @@ def _declare(L):
         "knn_lsh_code_words": (c_int32, [H]),
         "knn_lsh_get_codes": (c_int32, [H, c_void_p, c_int32]),
         "knn_lsh_add_codes": (c_int32, [H, c_void_p, c_int64, c_int32]),
+        "knn_lsh_train": (c_int32, [H, c_void_p, c_int64]),
+        "knn_lsh_set_thresholds": (c_int32, [H, c_void_p]),
+        "knn_lsh_get_thresholds": (c_int32, [H, c_void_p]),
+        "knn_lsh_last_train_ms": (c_int32, [H, f32p, f32p, f32p]),
         "knn_lsh_free": (None, [H]),
         "knn_eval_remove_self_hit": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
         "knn_eval_labels": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -8,8 +8,17 @@
 // distances as float32 (ties: lower id first here).  FAISS draws its matrix from its own RNG,
 // so codes are not bit-compatible with FAISS; the matrix is supplied by the caller.
 //
-//   lsh_encode_kernel    MFMA projection of 128 rows x 128 bits per workgroup, sign bits packed
+// IndexLSH(d, nbits, rotate_data, train_thresholds = true) (FAISS 1.7.2 IndexLSH::train, restated from the published
+// source as well): train() projects the training rows without thresholds and takes, per bit, the median of that
+// bit's projections -- s[n/2] of the sorted column for odd n, (s[n/2 - 1] + s[n/2]) / 2 in float for even n; bit j of
+// a code is then (x . a_j - t_j >= 0).
+//
+//   lsh_encode_kernel    MFMA projection of 128 rows x 128 bits per workgroup, bits (acc >= threshold) packed
 //                        with one ballot per accumulator register
+//   lsh_project_kernel   the same projection (lsh_project_tile: one K loop for both), accumulators stored
+//                        transposed as P[bit][row] for the training
+//   lsh_median_kernel    one workgroup per bit: exact order statistics n/2 - 1 and n/2 of a column of P by an
+//                        MSB-first radix select over the order-preserving uint32 image of the floats
 //   hamming_scan_kernel  one thread per database row: XOR + popcount against 32 query codes held
 //                        in LDS, same candidate lists / thresholds / wave_select as the flat scan
 
@@ -18,6 +27,8 @@ struct knn_lsh_s {
     int device = 0;
     int64_t ntotal = 0, cap_rows = 0;
     float *rot = nullptr;      // [W*64][dp] rotation rows (zero rows pad the tail)
+    float *thr = nullptr;      // [W*64] per-bit thresholds (zeros pad the tail: padding bits stay 1), or null: none
+    float train_ms[3] = {0, 0, 0}; // upload, projection, selection of the last knn_lsh_train (HIP events)
     uint64_t *codes = nullptr; // [cap_rows][W]
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -29,21 +40,23 @@ struct LshEncodeParams {
     const float *rot; // [W*64][dp]
     int64_t n;
     int dp, W;
-    uint32_t *codes32; // [n][2W]
+    uint32_t *codes32; // [n][2W]                       (lsh_encode_kernel)
+    const float *thr;  // [W*64] thresholds, or null     (lsh_encode_kernel)
+    float *proj;       // [W*64][ldp], whole 128-row tiles (lsh_project_kernel)
+    int64_t ldp;
 };
 
-__global__ __launch_bounds__(256, 2) void lsh_encode_kernel(LshEncodeParams p)
+// The projection of one 128-row x 128-bit tile: the K loop shared by lsh_encode_kernel and lsh_project_kernel, so that
+// the training sees the very accumulators the encoder compares (same staging, same swizzle, same MFMA order).
+// acc[a][b]: lane = bit (bit0 + (wn * 2 + b) * 32 + li), register r = row (row0 + (wm * 2 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh)
+__device__ __forceinline__ void lsh_project_tile(const LshEncodeParams &p, const int64_t row0, const int bit0, char *smem, f32x16 (&acc)[2][2])
 {
     constexpr int NR = 256; // 128 data rows + 128 rotation rows per K step
     constexpr int STAGE_BYTES = NR * 128;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     char *stage0 = smem, *stage1 = smem + STAGE_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
-    const int nbt = p.W / 2; // 128-bit column tiles
-    const int64_t row0 = (int64_t)(blockIdx.x / nbt) * 128;
-    const int bit0 = (blockIdx.x % nbt) * 128;
     const float *srcp[8];
     int lds_off[8];
 #pragma unroll
@@ -61,7 +74,6 @@ __global__ __launch_bounds__(256, 2) void lsh_encode_kernel(LshEncodeParams p)
             srcp[nn] = p.rot + (size_t)(bit0 + rb) * p.dp + 4 * s;
         }
     }
-    f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -103,19 +115,199 @@ __global__ __launch_bounds__(256, 2) void lsh_encode_kernel(LshEncodeParams p)
                         acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a][m], bf[b][m], acc[a][b], 0, 0, 0);
         }
     }
-    // sign bits: lane = bit (column), register = row; one ballot packs 32 bits of two rows
+}
+
+__global__ __launch_bounds__(256, 2) void lsh_encode_kernel(LshEncodeParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int li = lane & 31, lh = lane >> 5;
+    const int nbt = p.W / 2; // 128-bit column tiles
+    const int64_t row0 = (int64_t)(blockIdx.x / nbt) * 128;
+    const int bit0 = (blockIdx.x % nbt) * 128;
+    f32x16 acc[2][2];
+    lsh_project_tile(p, row0, bit0, smem, acc);
+    // code bits: lane = bit (column), register = row; one ballot packs 32 bits of two rows.  FAISS subtracts the threshold
+    // and tests the sign (x - t >= 0); x >= t is the same predicate in IEEE fp32 as long as denormals are kept (x - t is
+    // then zero only for x == t, and its sign is that of the comparison) -- the fp32 default on gfx950, and the build
+    // passes no flush flag -- so the accumulator is compared directly.  Without thresholds the operand is 0.0f as ever.
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++) {
             const int word = (bit0 >> 5) + wn * 2 + b;
+            const float t = p.thr ? p.thr[word * 32 + li] : 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const uint64_t m = __ballot(acc[a][b][r] >= 0.0f);
+                const uint64_t m = __ballot(acc[a][b][r] >= t);
                 const int64_t row = row0 + (wm * 2 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (li == 0 && row < p.n) p.codes32[(size_t)row * (2 * p.W) + word] = lh ? (uint32_t)(m >> 32) : (uint32_t)m;
             }
         }
+}
+
+// The training's projection: the accumulators of lsh_project_tile stored transposed, P[bit][row], so that each bit's
+// column is contiguous for lsh_median_kernel.  A lane holds rows 8g + 4 lh ... + 3 of its bit in registers 4g ... 4g + 3:
+// one 16-byte store each (ldp and the slab offsets are multiples of 128 rows).  Whole tiles are stored: the rows of a
+// partial tile beyond n repeat row n - 1 (the staging clamps) and land in the padding of P up to ldp, or in the next
+// slab's rows, which that slab's launch -- later on the same stream -- overwrites.
+__global__ __launch_bounds__(256, 2) void lsh_project_kernel(LshEncodeParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int li = lane & 31, lh = lane >> 5;
+    const int nbt = p.W / 2;
+    const int64_t row0 = (int64_t)(blockIdx.x / nbt) * 128;
+    const int bit0 = (blockIdx.x % nbt) * 128;
+    f32x16 acc[2][2];
+    lsh_project_tile(p, row0, bit0, smem, acc);
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) {
+            float *col = p.proj + (size_t)(bit0 + (wn * 2 + b) * 32 + li) * p.ldp + row0 + (wm * 2 + a) * 32 + 4 * lh;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                f32x4 v;
+#pragma unroll
+                for (int i = 0; i < 4; i++) v[i] = acc[a][b][4 * g + i];
+                *(f32x4 *)(col + 8 * g) = v;
+            }
+        }
+}
+
+// ---- per-bit medians ---------------------------------------------------------------------------------------------------
+// One workgroup per bit column of P.  Keys: the float's bits with -0.0 mapped to +0.0 first (std::sort treats the two as
+// equal; the canonical one defines the threshold's bits), then the usual order-preserving image (negative: all bits
+// flipped, else the sign bit set).  Three digit passes (11 + 11 + 10 bits, MSB first) narrow the key of rank n/2: a pass
+// histograms the digit of every key that carries the prefix found so far (LDS integer atomics: counts, so the result does
+// not depend on their order), a workgroup scan finds the digit's bin and the rank inside it.  Ties need no special case:
+// the third pass ends on the key itself, with the number of keys below it.  For even n the rank n/2 - 1 is the same key
+// when fewer than n/2 keys lie below it, else the largest key below it (one more pass over the column, which by then
+// sits in L2).  status[bit]: 1 a NaN projection, 2 a NaN threshold (+inf and -inf around the middle).
+struct LshMedianParams {
+    const float *proj; // [nbits][ldp]
+    int64_t n, ldp;
+    float *thr;      // [nbits]
+    int32_t *status; // [nbits]
+};
+
+__device__ __forceinline__ uint32_t lsh_float_key(float v)
+{
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0; // -0.0 -> +0.0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float lsh_key_float(uint32_t key)
+{
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// f(key) for every key of the column: 16-byte loads (columns start on 512-byte boundaries), then the tail
+template <typename F>
+__device__ __forceinline__ void lsh_column_keys(const float *col, int64_t n, int tid, F f)
+{
+    const int64_t n4 = n >> 2;
+    for (int64_t i = tid; i < n4; i += 256) {
+        const f32x4 v = *(const f32x4 *)(col + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; j++) f(lsh_float_key(v[j]));
+    }
+    const int64_t i = 4 * n4 + tid;
+    if (i < n) f(lsh_float_key(col[i]));
+}
+
+// the bin that holds rank `rank` of hist[0 .. 2047], the rank inside that bin, and the count below the bin -> s_sel[0..2]
+__device__ __forceinline__ void lsh_find_bin(const uint32_t *hist, uint32_t rank, uint32_t *s_wave, uint32_t *s_sel, int tid)
+{
+    uint32_t c[8], part = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { c[j] = hist[tid * 8 + j]; part += c[j]; }
+    const int lane = tid & 63, wave = tid >> 6;
+    uint32_t incl = part;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = 0; w < wave; w++) base += s_wave[w];
+    uint32_t lo = base + incl - part; // keys in the bins before this thread's
+    if (rank >= lo && rank < lo + part) { // exactly one thread: the counts of all bins sum to more than rank
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (rank < lo + c[j]) { s_sel[0] = tid * 8 + j; s_sel[1] = rank - lo; s_sel[2] = lo; break; }
+            lo += c[j];
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void lsh_median_kernel(LshMedianParams p)
+{
+    __shared__ uint32_t s_hist[2048];
+    __shared__ uint32_t s_wave[4];
+    __shared__ uint32_t s_sel[3];
+    __shared__ uint32_t s_flag, s_max;
+    const int tid = threadIdx.x;
+    const int bit = blockIdx.x;
+    const float *col = p.proj + (size_t)bit * p.ldp;
+    const int64_t n = p.n;
+    uint32_t rank = (uint32_t)(n >> 1); // (n < 2^31: knn_lsh_train checks)
+    uint32_t below = 0;                 // keys below the prefix found so far
+    uint32_t prefix = 0;
+    if (tid == 0) { s_flag = 0; s_max = 0; }
+    // pass 1: bits 31..21 (and the NaN check), pass 2: bits 20..10, pass 3: bits 9..0
+#pragma unroll 1
+    for (int pass = 0; pass < 3; pass++) {
+        for (int i = tid; i < 2048; i += 256) s_hist[i] = 0;
+        __syncthreads();
+        if (pass == 0) {
+            bool nan = false;
+            lsh_column_keys(col, n, tid, [&](uint32_t key) {
+                // NaN images: above +inf's (0xFF800000) or below -inf's (0x007FFFFF)
+                nan |= key > 0xFF800000u || key < 0x007FFFFFu;
+                atomicAdd(&s_hist[key >> 21], 1u);
+            });
+            if (nan) s_flag = 1;
+        } else if (pass == 1) {
+            lsh_column_keys(col, n, tid, [&](uint32_t key) {
+                if ((key >> 21) == prefix) atomicAdd(&s_hist[(key >> 10) & 0x7FFu], 1u);
+            });
+        } else {
+            lsh_column_keys(col, n, tid, [&](uint32_t key) {
+                if ((key >> 10) == prefix) atomicAdd(&s_hist[key & 0x3FFu], 1u);
+            });
+        }
+        __syncthreads();
+        lsh_find_bin(s_hist, rank, s_wave, s_sel, tid);
+        prefix = (prefix << (pass == 2 ? 10 : 11)) | s_sel[0];
+        rank = s_sel[1];
+        below += s_sel[2];
+        __syncthreads();
+    }
+    const uint32_t key_hi = prefix; // the key of rank n/2; `below` keys are smaller
+    uint32_t key_lo = key_hi;
+    if (!(n & 1) && below == (uint32_t)(n >> 1)) { // rank n/2 - 1 is the largest key below it
+        uint32_t best = 0;
+        lsh_column_keys(col, n, tid, [&](uint32_t key) {
+            if (key < key_hi && key > best) best = key;
+        });
+        atomicMax(&s_max, best);
+        __syncthreads();
+        key_lo = s_max;
+    }
+    if (tid == 0) {
+        float t = lsh_key_float(key_hi);
+        if (!(n & 1)) t = (lsh_key_float(key_lo) + t) / 2;
+        p.thr[bit] = t;
+        p.status[bit] = s_flag ? 1 : (t != t ? 2 : 0);
+    }
 }
 
 struct HammingParams {
@@ -222,6 +414,7 @@ extern "C" void knn_lsh_free(knn_lsh_s *h)
     if (!h) return;
     if (hipSetDevice(h->device) == hipSuccess) {
         if (h->rot) (void)hipFree(h->rot);
+        if (h->thr) (void)hipFree(h->thr);
         if (h->codes) (void)hipFree(h->codes);
         DevBuf *bufs[] = {&h->ws_x, &h->ws_xp, &h->ws_q, &h->ws_lists, &h->ws_gthr, &h->ws_qlist, &h->ws_qcnt, &h->ws_D, &h->ws_I, &h->ws_D2, &h->ws_I2};
         for (auto b : bufs) b->release();
@@ -233,16 +426,28 @@ extern "C" void knn_lsh_free(knn_lsh_s *h)
 extern "C" int64_t knn_lsh_ntotal(knn_lsh_s *h) { return h ? h->ntotal : -1; }
 extern "C" int32_t knn_lsh_code_words(knn_lsh_s *h) { return h ? h->W : -1; }
 
-// encodes n host rows into dst_codes (device, [n][W]) in slabs
-static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, uint64_t *dst_codes)
+// encodes n host rows into dst_codes (device, [n][W]) in slabs -- or, with proj given (the training), stores their
+// projections into proj[W*64][ldp] instead and adds the slabs' upload and kernel times (HIP events) to ms[0], ms[1].
+// A slab is a whole number of 128-row tiles, so that every slab's rows start on a tile of proj.
+static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, uint64_t *dst_codes, float *proj = nullptr, int64_t ldp = 0,
+                                float *ms = nullptr)
 {
-    const int64_t slab = std::max<int64_t>(128, (int64_t)(256ull << 20) / ((int64_t)h->dp * 4));
+    const int64_t slab = std::max<int64_t>(128, (int64_t)(256ull << 20) / ((int64_t)h->dp * 4) / 128 * 128);
     if (h->ws_x.ensure((size_t)std::min(n, slab) * h->d * 4) || h->ws_xp.ensure((size_t)std::min(n, slab) * h->dp * 4))
         return set_err(KNN_ERR_HIP, "lsh: out of device memory");
     hipStream_t s = h->stream;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    struct EventGuard {
+        hipEvent_t *e;
+        ~EventGuard() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
+    } guard{ev};
+    if (ms)
+        for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]));
     for (int64_t i0 = 0; i0 < n; i0 += slab) {
         const int64_t m = std::min(slab, n - i0);
+        if (ms) HIP_TRY(hipEventRecord(ev[0], s));
         HIP_TRY(hipMemcpyAsync(h->ws_x.p, x_host + i0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
+        if (ms) HIP_TRY(hipEventRecord(ev[1], s));
         const float *xp = (const float *)h->ws_x.p;
         if (h->dp != h->d) {
             int64_t tot = m * h->dp;
@@ -253,14 +458,144 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
         }
         LshEncodeParams p;
         p.x = xp; p.rot = h->rot; p.n = m; p.dp = h->dp; p.W = h->W;
-        p.codes32 = (uint32_t *)(dst_codes + (size_t)i0 * h->W);
+        p.codes32 = proj ? nullptr : (uint32_t *)(dst_codes + (size_t)i0 * h->W);
+        p.thr = h->thr;
+        p.proj = proj ? proj + i0 : nullptr;
+        p.ldp = ldp;
         const unsigned grid = (unsigned)(((m + 127) / 128) * (h->W / 2));
         const size_t lds = 2 * 256 * 128;
-        HIP_TRY(hipFuncSetAttribute((const void *)lsh_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(lsh_encode_kernel, dim3(grid), dim3(256), lds, s, p);
+        if (proj) {
+            HIP_TRY(hipFuncSetAttribute((const void *)lsh_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(lsh_project_kernel, dim3(grid), dim3(256), lds, s, p);
+        } else {
+            HIP_TRY(hipFuncSetAttribute((const void *)lsh_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(lsh_encode_kernel, dim3(grid), dim3(256), lds, s, p);
+        }
         HIP_TRY(hipGetLastError());
+        if (ms) HIP_TRY(hipEventRecord(ev[2], s));
         HIP_TRY(hipStreamSynchronize(s));
+        if (ms) {
+            float up = 0, pr = 0;
+            HIP_TRY(hipEventElapsedTime(&up, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&pr, ev[1], ev[2]));
+            ms[0] += up;
+            ms[1] += pr;
+        }
     }
+    return 0;
+}
+
+// installs thr_host[nbits] as the handle's thresholds (the tail up to W*64 is 0: a padding bit stays 0 >= 0), null: none
+static int lsh_install_thresholds(knn_lsh_s *h, const float *thr_host)
+{
+    if (!thr_host) {
+        if (h->thr) {
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            (void)hipFree(h->thr);
+        }
+        h->thr = nullptr;
+        return 0;
+    }
+    std::vector<float> padded((size_t)h->W * 64, 0.0f);
+    memcpy(padded.data(), thr_host, (size_t)h->nbits * 4);
+    if (!h->thr) HIP_TRY(hipMalloc((void **)&h->thr, padded.size() * 4));
+    HIP_TRY(hipMemcpy(h->thr, padded.data(), padded.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// IndexLSH::train with train_thresholds (seqvec_search/create_index.py:43, pfam/search.py:35, pfam/proteins_search.py:87
+// call train before add): per-bit medians of the training rows' projections, installed as the thresholds
+extern "C" int knn_lsh_train(knn_lsh_s *h, const float *x_host, int64_t n)
+{
+    if (!h || !x_host) return set_err(KNN_ERR_INVALID, "lsh_train: null pointer");
+    if (n < 1) return set_err(KNN_ERR_INVALID, "lsh_train: need at least one training row");
+    if (n >= (1ll << 31)) return set_err(KNN_ERR_UNSUPPORTED, "lsh_train: more than 2^31 - 1 training rows");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->ntotal) return set_err(KNN_ERR_INVALID, "lsh_train: the index already holds rows (their codes would go stale)");
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t ldp = (n + 127) / 128 * 128;
+    const size_t need = (size_t)h->W * 64 * ldp * 4;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b / 2)
+        return set_err(KNN_ERR_UNSUPPORTED, "lsh_train: the projections of the training rows take " + std::to_string(need) +
+                                                " bytes, more than half of the " + std::to_string(free_b) +
+                                                " bytes free on the device: train on a sample of the rows");
+    struct Scratch { // (freed whichever way the call returns)
+        float *P = nullptr, *thr = nullptr;
+        int32_t *status = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Scratch()
+        {
+            if (P) (void)hipFree(P);
+            if (thr) (void)hipFree(thr);
+            if (status) (void)hipFree(status);
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } sc;
+    if (hipMalloc((void **)&sc.P, need) != hipSuccess || hipMalloc((void **)&sc.thr, (size_t)h->nbits * 4) != hipSuccess ||
+        hipMalloc((void **)&sc.status, (size_t)h->nbits * 4) != hipSuccess)
+        return set_err(KNN_ERR_HIP, "lsh_train: out of device memory");
+    HIP_TRY(hipEventCreate(&sc.e0));
+    HIP_TRY(hipEventCreate(&sc.e1));
+    float ms[3] = {0, 0, 0};
+    // the projections are taken without thresholds whatever the handle holds: lsh_project_kernel does not read them
+    int rc = lsh_encode_host_rows(h, x_host, n, nullptr, sc.P, ldp, ms);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    LshMedianParams mp;
+    mp.proj = sc.P; mp.n = n; mp.ldp = ldp; mp.thr = sc.thr; mp.status = sc.status;
+    HIP_TRY(hipEventRecord(sc.e0, s));
+    hipLaunchKernelGGL(lsh_median_kernel, dim3(h->nbits), dim3(256), 0, s, mp); // (the padding columns are skipped)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.e1, s));
+    std::vector<float> thr((size_t)h->nbits);
+    std::vector<int32_t> status((size_t)h->nbits);
+    HIP_TRY(hipMemcpyAsync(thr.data(), sc.thr, thr.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status.data(), sc.status, status.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipEventElapsedTime(&ms[2], sc.e0, sc.e1));
+    for (int b = 0; b < h->nbits; b++)
+        if (status[b])
+            return set_err(KNN_ERR_INVALID, std::string("lsh_train: ") + (status[b] == 1 ? "a projection onto bit " : "the median (+inf and -inf around the middle) of bit ") +
+                                                std::to_string(b) + " is NaN");
+    rc = lsh_install_thresholds(h, thr.data());
+    if (rc) return rc;
+    memcpy(h->train_ms, ms, sizeof ms);
+    return 0;
+}
+
+// IndexLSH::thresholds of an index file (read_index), or of another index; NULL removes them
+extern "C" int knn_lsh_set_thresholds(knn_lsh_s *h, const float *thr_host)
+{
+    if (!h) return set_err(KNN_ERR_INVALID, "lsh_set_thresholds: null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->ntotal) return set_err(KNN_ERR_INVALID, "lsh_set_thresholds: the index already holds rows (their codes would go stale)");
+    if (thr_host)
+        for (int b = 0; b < h->nbits; b++)
+            if (thr_host[b] != thr_host[b]) return set_err(KNN_ERR_INVALID, "lsh_set_thresholds: the threshold of bit " + std::to_string(b) + " is NaN");
+    HIP_TRY(hipSetDevice(h->device));
+    return lsh_install_thresholds(h, thr_host);
+}
+
+extern "C" int knn_lsh_get_thresholds(knn_lsh_s *h, float *out_host)
+{
+    if (!h || !out_host) return set_err(KNN_ERR_INVALID, "lsh_get_thresholds: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->thr) return set_err(KNN_ERR_INVALID, "lsh_get_thresholds: the index has no thresholds");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpy(out_host, h->thr, (size_t)h->nbits * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int knn_lsh_last_train_ms(knn_lsh_s *h, float *upload_ms, float *project_ms, float *select_ms)
+{
+    if (!h || !upload_ms || !project_ms || !select_ms) return set_err(KNN_ERR_INVALID, "lsh_last_train_ms: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *upload_ms = h->train_ms[0];
+    *project_ms = h->train_ms[1];
+    *select_ms = h->train_ms[2];
     return 0;
 }
 

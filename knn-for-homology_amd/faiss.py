@@ -410,9 +410,9 @@ def _r_vec(f, dtype):
     return np.frombuffer(_r_exact(f, n * item), dtype=dtype)
 
 
-def _w_header(f, fourcc, d, ntotal, metric):
+def _w_header(f, fourcc, d, ntotal, metric, is_trained=True):
     f.write(fourcc)
-    f.write(_struct.pack("<iqqq?i", d, ntotal, 1 << 20, 1 << 20, True, metric))
+    f.write(_struct.pack("<iqqq?i", d, ntotal, 1 << 20, 1 << 20, bool(is_trained), metric))
 
 
 def _r_header(f):
