@@ -280,7 +280,36 @@ int knn_lsh_get_thresholds(knn_lsh_handle h, float *out_host);
 /* measurement (tools/lsh_train_probe.py): HIP-event milliseconds of the last successful knn_lsh_train -- the slabs'
  * uploads, their projection kernels, the median selection */
 int knn_lsh_last_train_ms(knn_lsh_handle h, float *upload_ms, float *project_ms, float *select_ms);
+/* IndexLSH::reset: drops the rows; rotation and thresholds stay */
+int knn_lsh_reset(knn_lsh_handle h);
 void knn_lsh_free(knn_lsh_handle h);
+
+/* ---- faiss.IndexRefineFlat(base) --------------------------------------------
+ * FAISS 1.7.2 IndexRefine::search (published behaviour restated; the reference uses its LSH index as exactly such a
+ * shortlist: seqvec_search/main.py:132, pfam/search.py:27-51): the base index returns kb = k * k_factor labels per
+ * query, the refine index scores those rows exactly against its stored fp32 vectors and the best k come back.
+ * Scores: one fp32 chain per (query, label) in the contract's k order; inner product = the bits knn_flat_search
+ * returns; L2 = the sum of squared differences at EVERY nq (IndexFlat::compute_distance_subset calls fvec_L2sqr per
+ * pair, never the norm formula): the bits knn_flat_search returns for fewer than 20 queries.  Results best first,
+ * equal scores by ascending label, unfilled slots -1 with -FLT_MAX (IP) / +FLT_MAX (L2).  1 <= k <= kb <= KNN_MAX_K:
+ * k < 1 or k > kb is KNN_ERR_INVALID, kb > KNN_MAX_K is KNN_ERR_UNSUPPORTED.  nq = 0 returns 0; an index without rows
+ * fills every slot as unfilled.  One corner differs from FAISS 1.7.2: a label of -1 (the base found fewer than kb
+ * rows) never competes, where FAISS leaves the base's distance in place for it. */
+/* IndexFlat::compute_distance_subset + reorder_2_heaps: labels_host int64 [nq][kb] from any base index over the same
+ * rows.  Metric and rows are h's.  -1 is skipped; a label < -1 or >= ntotal is KNN_ERR_INVALID, checked before
+ * anything is launched (D_host / I_host stay untouched).  A label that occurs twice in a row is scored twice and may
+ * be returned twice, as in FAISS (up to 32 copies of one label per row; more may displace better labels). */
+int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, const int64_t *labels_host, int64_t kb, int64_t k,
+                    float *D_host, int64_t *I_host);
+/* IndexRefineFlat(IndexLSH).search in one call: knn_lsh_search's batches with the kb Hamming hits of each batch
+ * re-scored against flat's rows on the device; only [nq][k] is downloaded.  base and flat must be on the same device
+ * with the same d and the same ntotal (KNN_ERR_INVALID otherwise).  Locks both handles: base first, then flat. */
+int knn_lsh_search_refine(knn_lsh_handle base, knn_handle flat, const float *q_host, int64_t nq, int64_t kb, int64_t k,
+                          float *D_host, int64_t *I_host);
+/* measurement (tools/refine_probe.py): HIP-event milliseconds of the last successful knn_flat_refine /
+ * knn_lsh_search_refine that used this flat handle -- its rescore launches and its final selections, summed over
+ * the batches */
+int knn_last_refine_ms(knn_handle h, float *rescore_ms, float *select_ms);
 
 /* ---- consumers of (hits, scores): SURVEY section 8(f) N4 --------------------------
  * Host buffers in and out.  hits are int64 [nq][k] as returned by search. */

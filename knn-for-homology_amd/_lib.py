@@ -115,7 +115,11 @@ def _declare(L):
         "knn_lsh_set_thresholds": (c_int32, [H, c_void_p]),
         "knn_lsh_get_thresholds": (c_int32, [H, c_void_p]),
         "knn_lsh_last_train_ms": (c_int32, [H, f32p, f32p, f32p]),
+        "knn_lsh_reset": (c_int32, [H]),
         "knn_lsh_free": (None, [H]),
+        "knn_flat_refine": (c_int32, [H, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+        "knn_lsh_search_refine": (c_int32, [H, H, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+        "knn_last_refine_ms": (c_int32, [H, f32p, f32p]),
         "knn_eval_remove_self_hit": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
         "knn_eval_labels": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
         "knn_eval_sets": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),

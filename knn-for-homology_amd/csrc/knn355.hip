@@ -25,6 +25,7 @@
 //   merge_select_kernel  one wave per (query, group of lists): exact top-k of <= 4096 keys,
 //                        last round sorts and writes D / I.
 //   hnsw.inc / lsh.inc / eval.inc   IndexHNSWFlat, IndexLSH, consumers of (hits, scores).
+//   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
 #include <hip/hip_runtime.h>
 #include <thread>
 #include <type_traits>
@@ -3445,6 +3446,9 @@ struct knn_index_s {
     std::vector<float> range_D;
     std::vector<int64_t> range_I;
     int64_t range_qblocks = 0, range_redos = 0, range_redo_queries = 0; // query blocks, overflow rescans, queries rescanned
+    // refine (refine.inc): queries as uploaded / padded, labels, rescored keys, results; HIP-event times of the last call
+    DevBuf ws_rfq, ws_rfqp, ws_rfI, ws_rfkeys, ws_rfD, ws_rfI2;
+    float refine_ms[2] = {0.f, 0.f}; // rescore launches, final selections
     float last_ms = 0.f;
 };
 
@@ -3679,7 +3683,8 @@ extern "C" void knn_free(knn_handle h)
         free_index_buffers(h);
         DevBuf *bufs[] = {&h->xb16, &h->ws_q16, &h->ws_sym, &h->ws_qdiff, &h->ws_defer, &h->ws_turn, &h->ws_flag, &h->ws_q, &h->ws_qn, &h->ws_lists, &h->ws_D, &h->ws_I, &h->ws_tmp, &h->ws_tmp2, &h->ws_D1, &h->ws_I1, &h->ws_tmp3,
                           &h->ws_rq, &h->ws_rqn, &h->ws_rcnt, &h->ws_rsegD, &h->ws_rsegI, &h->ws_roff, &h->ws_routD, &h->ws_routI, &h->ws_rsel, &h->ws_rq2, &h->ws_rexp,
-                          &h->ws_q16x, &h->ws_s16q, &h->ws_s16ak, &h->ws_s16ok, &h->ws_s16stat};
+                          &h->ws_q16x, &h->ws_s16q, &h->ws_s16ak, &h->ws_s16ok, &h->ws_s16stat,
+                          &h->ws_rfq, &h->ws_rfqp, &h->ws_rfI, &h->ws_rfkeys, &h->ws_rfD, &h->ws_rfI2};
         for (DevBuf *b : bufs) b->release();
         for (LevelBufs &b : h->ws_level) {
             b.qlist.release();
@@ -5983,6 +5988,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 }
 
 #include "hnsw.inc"
+#include "refine.inc"
 #include "lsh.inc"
 #include "eval.inc"
 #include "range.inc"

@@ -32,7 +32,7 @@ struct knn_lsh_s {
     uint64_t *codes = nullptr; // [cap_rows][W]
     hipStream_t stream = nullptr;
     std::mutex mu;
-    DevBuf ws_x, ws_xp, ws_q, ws_lists, ws_gthr, ws_qlist, ws_qcnt, ws_D, ws_I, ws_D2, ws_I2; // (ws_D2 / ws_I2: second result set of a search of several batches)
+    DevBuf ws_x, ws_xp, ws_q, ws_lists, ws_gthr, ws_qlist, ws_qcnt, ws_D, ws_I, ws_D2, ws_I2, ws_cD, ws_cI; // (ws_D2 / ws_I2: second result set of a search of several batches; ws_cD / ws_cI: the Hamming hits a refined search re-scores)
 };
 
 struct LshEncodeParams {
@@ -416,7 +416,7 @@ extern "C" void knn_lsh_free(knn_lsh_s *h)
         if (h->rot) (void)hipFree(h->rot);
         if (h->thr) (void)hipFree(h->thr);
         if (h->codes) (void)hipFree(h->codes);
-        DevBuf *bufs[] = {&h->ws_x, &h->ws_xp, &h->ws_q, &h->ws_lists, &h->ws_gthr, &h->ws_qlist, &h->ws_qcnt, &h->ws_D, &h->ws_I, &h->ws_D2, &h->ws_I2};
+        DevBuf *bufs[] = {&h->ws_x, &h->ws_xp, &h->ws_q, &h->ws_lists, &h->ws_gthr, &h->ws_qlist, &h->ws_qcnt, &h->ws_D, &h->ws_I, &h->ws_D2, &h->ws_I2, &h->ws_cD, &h->ws_cI};
         for (auto b : bufs) b->release();
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
@@ -429,10 +429,12 @@ extern "C" int32_t knn_lsh_code_words(knn_lsh_s *h) { return h ? h->W : -1; }
 // encodes n host rows into dst_codes (device, [n][W]) in slabs -- or, with proj given (the training), stores their
 // projections into proj[W*64][ldp] instead and adds the slabs' upload and kernel times (HIP events) to ms[0], ms[1].
 // A slab is a whole number of 128-row tiles, so that every slab's rows start on a tile of proj.
+// (xp_out: where the LAST slab's rows, zero padded to dp, stay on the device until the handle's next call)
+static int64_t lsh_slab_rows(const knn_lsh_s *h) { return std::max<int64_t>(128, (int64_t)(256ull << 20) / ((int64_t)h->dp * 4) / 128 * 128); }
 static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, uint64_t *dst_codes, float *proj = nullptr, int64_t ldp = 0,
-                                float *ms = nullptr)
+                                float *ms = nullptr, const float **xp_out = nullptr)
 {
-    const int64_t slab = std::max<int64_t>(128, (int64_t)(256ull << 20) / ((int64_t)h->dp * 4) / 128 * 128);
+    const int64_t slab = lsh_slab_rows(h);
     if (h->ws_x.ensure((size_t)std::min(n, slab) * h->d * 4) || h->ws_xp.ensure((size_t)std::min(n, slab) * h->dp * 4))
         return set_err(KNN_ERR_HIP, "lsh: out of device memory");
     hipStream_t s = h->stream;
@@ -456,6 +458,7 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
             HIP_TRY(hipGetLastError());
             xp = (const float *)h->ws_xp.p;
         }
+        if (xp_out) *xp_out = xp;
         LshEncodeParams p;
         p.x = xp; p.rot = h->rot; p.n = m; p.dp = h->dp; p.W = h->W;
         p.codes32 = proj ? nullptr : (uint32_t *)(dst_codes + (size_t)i0 * h->W);
@@ -681,22 +684,17 @@ static int launch_hamming(const HammingParams &p, int grid, size_t lds, hipStrea
     return 0;
 }
 
-extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int64_t k, float *D_host, int64_t *I_host)
+// The batch loop of knn_lsh_search and knn_lsh_search_refine (the caller holds the locks and has checked the shapes): the
+// kb smallest Hamming distances of every query, selected on the device.  flat == null: those are the result (k == kb).
+// flat given: the batch's kb ids stay on the device, refine_batch scores them against flat's rows with the batch's fp32
+// queries -- still on the device from the encode step -- and its best k are the result.  Either way only [m][k] goes down.
+static int lsh_search_batches(knn_lsh_s *h, knn_index_s *flat, const float *q_host, int64_t nq, int64_t kb, int64_t k, float *D_host,
+                              int64_t *I_host, RefineEvents &rev)
 {
-    if (!h) return set_err(KNN_ERR_INVALID, "lsh_search: null handle");
-    if (nq < 0 || k < 1) return set_err(KNN_ERR_INVALID, "lsh_search: bad shape");
-    if (k > KNN_MAX_K) return set_err(KNN_ERR_UNSUPPORTED, "lsh_search: k > 2048 is not supported");
-    if (nq == 0) return 0;
-    if (!q_host || !D_host || !I_host) return set_err(KNN_ERR_INVALID, "lsh_search: null pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->ntotal == 0) {
-        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = FLT_MAX; I_host[i] = -1; }
-        return 0;
-    }
     hipStream_t s = h->stream;
     const int QT = 32, DT = 256;
-    const int64_t QB = 16384;
+    // (a refined batch keeps its queries on the device: no more of them than one slab of the encoder uploads at a time)
+    const int64_t QB = flat ? std::min<int64_t>(16384, lsh_slab_rows(h)) : 16384;
     const int W = h->W;
     // Several batches (pfam/search.py searches every row, k = 1000): two sets of result buffers, and the results of batch
     // b - 1 go down on the device's copy stream while batch b is scanned (see hnsw_search_device)
@@ -740,18 +738,19 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
         const int slot = piped ? (int)(bi & 1) : 0;
         if (piped && bi >= 2) HIP_TRY(hipStreamWaitEvent(s, evd[slot], 0)); // (the results of batch b - 2 have left these buffers)
         if (h->ws_q.ensure((size_t)m * W * 8)) return set_err(KNN_ERR_HIP, "lsh_search: out of device memory");
-        int rc = lsh_encode_host_rows(h, q_host + b0 * h->d, m, (uint64_t *)h->ws_q.p);
+        const float *xq_dev = nullptr;
+        int rc = lsh_encode_host_rows(h, q_host + b0 * h->d, m, (uint64_t *)h->ws_q.p, nullptr, 0, nullptr, &xq_dev);
         if (rc) return rc;
         HammingParams p;
-        p.codes = h->codes; p.qcodes = (const uint64_t *)h->ws_q.p; p.nb = h->ntotal; p.nq = m; p.W = W; p.k = (int)k;
-        p.cap = std::max(512, next_pow2_host(2 * (int)k + DT));
-        if (k <= KNN_REGISTER_SELECT_MAX_K) p.cap = std::min(p.cap, 2048);
-        else if (k <= KNN_WAVE_SELECT_MAX_K) p.cap = std::min(p.cap, 4096);
-        p.kslot = knn_kslot((int)k);
+        p.codes = h->codes; p.qcodes = (const uint64_t *)h->ws_q.p; p.nb = h->ntotal; p.nq = m; p.W = W; p.k = (int)kb;
+        p.cap = std::max(512, next_pow2_host(2 * (int)kb + DT));
+        if (kb <= KNN_REGISTER_SELECT_MAX_K) p.cap = std::min(p.cap, 2048);
+        else if (kb <= KNN_WAVE_SELECT_MAX_K) p.cap = std::min(p.cap, 4096);
+        p.kslot = knn_kslot((int)kb);
         p.nqtiles = (int)((m + QT - 1) / QT);
         const int64_t ntiles = (h->ntotal + DT - 1) / DT;
         int64_t want = std::max<int64_t>(1, (1024 + p.nqtiles - 1) / p.nqtiles);
-        const int64_t min_tiles = std::max<int64_t>(2, (4 * k + DT - 1) / DT);
+        const int64_t min_tiles = std::max<int64_t>(2, (4 * kb + DT - 1) / DT);
         want = std::max<int64_t>(1, std::min(want, std::max<int64_t>(1, ntiles / min_tiles)));
         const size_t per_wg = (size_t)QT * p.cap * 8;
         want = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)((2ull << 30) / per_wg) / p.nqtiles));
@@ -762,7 +761,8 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
         p.qcap = p.nchunks * p.kslot;
         if (h->ws_lists.ensure((size_t)grid * per_wg) || h->ws_gthr.ensure((size_t)p.nqtiles * QT * 4) ||
             h->ws_qlist.ensure((size_t)m * p.qcap * 8) || h->ws_qcnt.ensure((size_t)m * 4) || dD[slot]->ensure((size_t)std::min(QB, nq) * k * 4) ||
-            dI[slot]->ensure((size_t)std::min(QB, nq) * k * 8))
+            dI[slot]->ensure((size_t)std::min(QB, nq) * k * 8) ||
+            (flat && (h->ws_cD.ensure((size_t)m * kb * 4) || h->ws_cI.ensure((size_t)m * kb * 8))))
             return set_err(KNN_ERR_HIP, "lsh_search: out of device memory");
         HIP_TRY(hipMemsetAsync(h->ws_gthr.p, 0xFF, (size_t)p.nqtiles * QT * 4, s));
         HIP_TRY(hipMemsetAsync(h->ws_qcnt.p, 0, (size_t)m * 4, s));
@@ -782,10 +782,14 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
         // carry the distance as a float: METRIC_L2 formatting)
         SelectParams sp = {};
         sp.in = p.qlist; sp.in_stride = p.qcap; sp.cnt = p.qcnt; sp.cap = p.qcap;
-        sp.nq = m; sp.k = (int)k; sp.metric = KNN_METRIC_L2;
-        sp.D = (float *)dD[slot]->p; sp.I = (int64_t *)dI[slot]->p;
+        sp.nq = m; sp.k = (int)kb; sp.metric = KNN_METRIC_L2;
+        sp.D = (float *)(flat ? h->ws_cD.p : dD[slot]->p); sp.I = (int64_t *)(flat ? h->ws_cI.p : dI[slot]->p);
         rc = launch_select(sp, s);
         if (rc) return rc;
+        if (flat) { // exact scores of the kb hits, the best k of them into this batch's result buffers
+            rc = refine_batch(flat, xq_dev, (const int64_t *)h->ws_cI.p, m, (int)kb, (int)k, (float *)dD[slot]->p, (int64_t *)dI[slot]->p, s, rev);
+            if (rc) return rc;
+        }
         if (!piped) {
             HIP_TRY(download(bi, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -812,4 +816,59 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
             rc = set_err(KNN_ERR_HIP, std::string("lsh_search: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     }
     return rc;
+}
+
+extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int64_t k, float *D_host, int64_t *I_host)
+{
+    if (!h) return set_err(KNN_ERR_INVALID, "lsh_search: null handle");
+    if (nq < 0 || k < 1) return set_err(KNN_ERR_INVALID, "lsh_search: bad shape");
+    if (k > KNN_MAX_K) return set_err(KNN_ERR_UNSUPPORTED, "lsh_search: k > 2048 is not supported");
+    if (nq == 0) return 0;
+    if (!q_host || !D_host || !I_host) return set_err(KNN_ERR_INVALID, "lsh_search: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->ntotal == 0) {
+        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = FLT_MAX; I_host[i] = -1; }
+        return 0;
+    }
+    RefineEvents none;
+    return lsh_search_batches(h, nullptr, q_host, nq, k, k, D_host, I_host, none);
+}
+
+// IndexRefineFlat(IndexLSH).search: IndexLSH::search for kb labels, IndexFlat::compute_distance_subset, reorder_2_heaps --
+// with the labels never leaving the device.  Locks: the LSH handle's, then the flat handle's.
+extern "C" int knn_lsh_search_refine(knn_lsh_s *h, knn_handle flat, const float *q_host, int64_t nq, int64_t kb, int64_t k, float *D_host,
+                                     int64_t *I_host)
+{
+    if (!h || !flat) return set_err(KNN_ERR_INVALID, "lsh_search_refine: null handle");
+    int rc = refine_check_shape(nq, kb, k, "lsh_search_refine");
+    if (rc) return rc;
+    if (nq == 0) return 0;
+    if (!q_host || !D_host || !I_host) return set_err(KNN_ERR_INVALID, "lsh_search_refine: null pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::lock_guard<std::mutex> lkf(flat->mu);
+    if ((rc = refine_check_flat(flat, "lsh_search_refine"))) return rc;
+    if (flat->device != h->device || flat->d != h->d || flat->ntotal != h->ntotal)
+        return set_err(KNN_ERR_INVALID, "lsh_search_refine: the base index (device " + std::to_string(h->device) + ", d " + std::to_string(h->d) + ", " +
+                                            std::to_string(h->ntotal) + " rows) and the refine index (device " + std::to_string(flat->device) + ", d " +
+                                            std::to_string(flat->d) + ", " + std::to_string(flat->ntotal) + " rows) do not hold the same rows");
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->ntotal == 0) {
+        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = flat->metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX; I_host[i] = -1; }
+        return 0;
+    }
+    HIP_TRY(hipStreamSynchronize(flat->stream)); // (the rows are read on the LSH handle's stream: whatever the flat handle's own stream still does to them first)
+    RefineEvents rev;
+    rc = lsh_search_batches(h, flat, q_host, nq, kb, k, D_host, I_host, rev);
+    if (rc) return rc;
+    return rev.sum(flat->refine_ms);
+}
+
+// IndexLSH::reset: the handle keeps its rotation, thresholds and the codes' allocation
+extern "C" int knn_lsh_reset(knn_lsh_s *h)
+{
+    if (!h) return set_err(KNN_ERR_INVALID, "lsh_reset: null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->ntotal = 0;
+    return 0;
 }

@@ -10,6 +10,8 @@ Reference call sites (konstin/knn-for-homology):
   .train / .add / .search           cath/search.py:22-24; seqvec_search/main.py:37-45
   IndexHNSWFlat(d, M, metric)       pfam/proteins_search.py:30-31 (hnsw.efSearch)
   IndexLSH(d, nbits)                seqvec_search/create_index.py:41; pfam/search.py:27
+  IndexRefineFlat(base)             (not called by the reference, which feeds its LSH shortlist to other
+                                    tools: seqvec_search/main.py:132, pfam/search.py:27-51) exact order for it
   write_index / read_index          pfam/proteins_search.py:40; seqvec_search/main.py:132
 
 Semantics kept: float32 C-contiguous 2-D inputs only (anything else raises, as the
@@ -365,6 +367,127 @@ class IndexHNSWFlat(Index):
             self._h = None
 
 
+class IndexRefineFlat(Index):
+    """faiss.IndexRefineFlat(base_index): ``search(x, k)`` asks the base index for ``k * k_factor`` labels per query,
+    scores exactly those rows against the float32 vectors of ``refine_index`` (an ``IndexFlat`` fed by the same ``add``
+    calls) and returns the best k with real scores, best first, equal scores by ascending id.
+
+    Inner-product scores are the bits ``IndexFlat.search`` returns; L2 scores are the sum of squared differences at
+    every batch size (FAISS's compute_distance_subset calls fvec_L2sqr per pair): the bits ``IndexFlat.search``
+    returns for fewer than 20 queries.  With an ``IndexLSH`` base the whole search is one library call and the
+    shortlist never leaves the GPU; any other base index of this module is searched first and its labels re-scored.
+
+    As in FAISS the refine index takes ``base_index.metric_type`` (``IndexLSH`` reports ``METRIC_L2``).  ``metric=`` is
+    a knn355 extra: it sets the refine index's metric, and the result is ordered by that metric (FAISS's generic
+    IndexRefine would order inner-product scores by the base's metric; that quirk is not reproduced).  A label of -1
+    (the base found fewer rows than asked for) never competes; FAISS 1.7.2 leaves the base's distance in its place."""
+
+    def __init__(self, base_index, metric=None):
+        if base_index.ntotal != 0:  # (FAISS: "base_index should be empty in the beginning")
+            raise RuntimeError("IndexRefineFlat: base_index should be empty in the beginning")
+        self.base_index = base_index
+        self.refine_index = IndexFlat(base_index.d, base_index.metric_type if metric is None else int(metric))
+        self._k_factor = 1.0
+
+    @property
+    def d(self):
+        return self.base_index.d
+
+    @property
+    def ntotal(self):
+        return self.base_index.ntotal
+
+    @property
+    def metric_type(self):
+        return self.base_index.metric_type
+
+    @property
+    def is_trained(self):
+        return self.base_index.is_trained
+
+    @property
+    def k_factor(self):
+        return self._k_factor
+
+    @k_factor.setter
+    def k_factor(self, value):
+        value = float(value)
+        if not value >= 1.0:
+            raise ValueError(f"IndexRefineFlat.k_factor must be >= 1, got {value!r}")
+        self._k_factor = value
+
+    def train(self, x):
+        self.base_index.train(x)
+
+    def add(self, x):
+        _check_matrix(x, self.d)
+        self.base_index.add(x)
+        self.refine_index.add(x)
+
+    def reset(self):
+        self.base_index.reset()
+        self.refine_index.reset()
+
+    def search(self, x, k):
+        base, flat = self.base_index, self.refine_index
+        _check_matrix(x, base.d)
+        k = int(k)
+        if k < 1:
+            raise AssertionError("k must be positive")
+        kb = int(np.float32(k) * np.float32(self._k_factor))  # (FAISS: idx_t(k * k_factor) with a float factor)
+        if base.d != flat.d or base.ntotal != flat.ntotal:
+            raise RuntimeError("IndexRefineFlat.search: base_index (d %d, %d rows) and refine_index (d %d, %d rows) do not hold "
+                               "the same rows" % (base.d, base.ntotal, flat.d, flat.ntotal))
+        L = _lib.lib()
+        from .lsh import IndexLSH
+        if isinstance(base, IndexLSH):
+            base._need_trained("search")
+            D = _lib.result_array((x.shape[0], k), np.float32)
+            I = _lib.result_array((x.shape[0], k), np.int64)
+            _lib.check(L.knn_lsh_search_refine(base._h, flat._h, x.ctypes.data, x.shape[0], kb, k, D.ctypes.data, I.ctypes.data))
+            return D, I
+        if not isinstance(base, (IndexFlat, IndexHNSWFlat)):
+            raise RuntimeError(f"IndexRefineFlat.search: unsupported base index type {type(base).__name__}")
+        _, labels = base.search(x, kb)
+        labels = np.ascontiguousarray(labels, np.int64)
+        D = _lib.result_array((x.shape[0], k), np.float32)
+        I = _lib.result_array((x.shape[0], k), np.int64)
+        _lib.check(L.knn_flat_refine(flat._h, x.ctypes.data, x.shape[0], labels.ctypes.data, kb, k, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def last_refine(self):
+        """knn355 extra: {"rescore_ms", "select_ms"}: HIP-event times of the last search's re-scoring and final selection"""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _lib.check(_lib.lib().knn_last_refine_ms(self.refine_index._h, ctypes.byref(a), ctypes.byref(b)))
+        return {"rescore_ms": a.value, "select_ms": b.value}
+
+    # ---- FAISS "IxRF" layout: header (the wrapper's metric = the base's), the base index's own block, the refine
+    # index's block ("IxF2" / "IxFI"), float k_factor (FAISS 1.7.2 index_write.cpp, restated from the published source;
+    # not verified against a FAISS binary).
+    def _write(self, f):
+        _w_header(f, b"IxRF", self.d, self.ntotal, self.metric_type, self.is_trained)
+        _write_any(f, self.base_index, None)
+        _write_any(f, self.refine_index, None)
+        f.write(_struct.pack("<f", self._k_factor))
+
+    @classmethod
+    def _read(cls, f):
+        d, ntotal, _metric = _r_header(f)
+        base = _read_index(f)
+        refine = _read_index(f)
+        (k_factor,) = _struct.unpack("<f", _r_exact(f, 4))
+        if not isinstance(refine, IndexFlat):
+            raise RuntimeError("read_index: IxRF refine index is not an IndexFlat")
+        if base.d != refine.d or base.ntotal != refine.ntotal or base.d != d or base.ntotal != ntotal:
+            raise RuntimeError("read_index: IxRF inner indexes disagree (header d=%d ntotal=%d, base d=%d ntotal=%d, refine d=%d ntotal=%d)"
+                               % (d, ntotal, base.d, base.ntotal, refine.d, refine.ntotal))
+        if not k_factor >= 1.0:
+            raise RuntimeError("read_index: IxRF k_factor %r" % (k_factor,))
+        idx = object.__new__(cls)
+        idx.base_index, idx.refine_index, idx._k_factor = base, refine, float(k_factor)
+        return idx
+
+
 # ---------------------------------------------------------------------------
 # write_index / read_index -- FAISS 1.7.2 binary layout (impl/index_write.cpp,
 # impl/index_read.cpp; restated from the published format, the FAISS sources are not
@@ -378,6 +501,7 @@ class IndexHNSWFlat(Index):
 #                    int entry_point, max_level, efConstruction, efSearch, upper_beam}
 #                    followed by the storage index ("IxFI"/"IxF2")
 #     "IxHe"         IndexLSH (see lsh.py)
+#     "IxRF"         IndexRefineFlat : base index block, refine index block ("IxFI"/"IxF2"), float k_factor
 # Reference call sites: pfam/proteins_search.py:39-40, seqvec_search/create_index.py:47,
 # pfam/search.py:32,34, seqvec_search/main.py:132.
 # ---------------------------------------------------------------------------
@@ -436,24 +560,28 @@ def write_index(index, fname, rows=None):
     if rows is not None and (rows.dtype != np.float32 or rows.shape != (index.ntotal, index.d) or not rows.flags.c_contiguous):
         raise RuntimeError("write_index: rows must be the index's float32 [ntotal, d] contents")
     with open(str(fname), "wb") as f:
-        if isinstance(index, IndexHNSWFlat):
-            levels, offsets, nbrs, cum, probas = index.graph()
-            p = index.hnsw._params()
-            _w_header(f, b"IHNf", index.d, index.ntotal, index.metric_type)
-            _w_vec(f, probas, np.float64)
-            _w_vec(f, cum, np.int32)
-            _w_vec(f, levels + 1, np.int32)
-            _w_vec(f, offsets, np.uint64)
-            _w_vec(f, nbrs, np.int32)
-            f.write(_struct.pack("<iiiii", int(p["entry_point"]), int(p["max_level"]), int(p["efConstruction"]),
-                                 int(p["efSearch"]), 1))
-            _write_flat(f, index.d, index.metric_type, rows if rows is not None else index.reconstruct_n(0, index.ntotal))
-        elif isinstance(index, IndexFlat):
-            _write_flat(f, index.d, index.metric_type, rows if rows is not None else index.reconstruct_n(0, index.ntotal))
-        elif hasattr(index, "_write"):
-            index._write(f)
-        else:
-            raise RuntimeError(f"write_index: unsupported index type {type(index).__name__}")
+        _write_any(f, index, rows)
+
+
+def _write_any(f, index, rows):
+    if isinstance(index, IndexHNSWFlat):
+        levels, offsets, nbrs, cum, probas = index.graph()
+        p = index.hnsw._params()
+        _w_header(f, b"IHNf", index.d, index.ntotal, index.metric_type)
+        _w_vec(f, probas, np.float64)
+        _w_vec(f, cum, np.int32)
+        _w_vec(f, levels + 1, np.int32)
+        _w_vec(f, offsets, np.uint64)
+        _w_vec(f, nbrs, np.int32)
+        f.write(_struct.pack("<iiiii", int(p["entry_point"]), int(p["max_level"]), int(p["efConstruction"]),
+                             int(p["efSearch"]), 1))
+        _write_flat(f, index.d, index.metric_type, rows if rows is not None else index.reconstruct_n(0, index.ntotal))
+    elif isinstance(index, IndexFlat):
+        _write_flat(f, index.d, index.metric_type, rows if rows is not None else index.reconstruct_n(0, index.ntotal))
+    elif hasattr(index, "_write"):
+        index._write(f)
+    else:
+        raise RuntimeError(f"write_index: unsupported index type {type(index).__name__}")
 
 
 def read_index(fname):
@@ -510,6 +638,8 @@ def _read_index(f):
     if fourcc == b"IxHe":
         from .lsh import IndexLSH
         return IndexLSH._read(f)
+    if fourcc == b"IxRF":
+        return IndexRefineFlat._read(f)
     raise RuntimeError(f"read_index: unsupported index type {fourcc!r}")
 
 

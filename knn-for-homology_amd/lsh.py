@@ -95,6 +95,10 @@ class IndexLSH(Index):
         _lib.check(_lib.lib().knn_lsh_search(self._h, x.ctypes.data, x.shape[0], k, D.ctypes.data, I.ctypes.data))
         return D, I
 
+    def reset(self):
+        """faiss.IndexLSH.reset: drops the rows; the rotation and trained thresholds stay"""
+        _lib.check(_lib.lib().knn_lsh_reset(self._h))
+
     def codes(self):
         out = np.empty((self.ntotal, self.code_size), np.uint8)
         _lib.check(_lib.lib().knn_lsh_get_codes(self._h, out.ctypes.data, self.code_size))
