@@ -2507,89 +2507,47 @@ static int hnsw_search_device(knn_hnsw_s *H, const float *q_host, int64_t nq, in
     const int64_t mb = std::min(nq, B);
     const int64_t nbatches = (nq + B - 1) / B;
     // Several batches: two sets of result buffers, and while batch b is walked the results of batch b - 1 go down on the
-    // device's copy stream (the reference's run, all-vs-all k = 1000: 200 MB per batch -- an eighth of the batch's time when it
-    // waited its turn on the search's own stream)
-    CopyPipes &cp = g_pipes[f->device & 63];
-    std::unique_lock<std::mutex> pipes(cp.mu, std::defer_lock);
-    const bool piped = nbatches > 1 && pipes.try_lock();
-    if (piped && !cp.h2d) {
-        HIP_TRY(hipStreamCreateWithFlags(&cp.h2d, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&cp.d2h, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipEventCreateWithFlags(&cp.ev_query[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&cp.ev_batch[i], hipEventDisableTiming));
-        }
-    }
+    // device's copy stream (ResultPipe; the reference's run, all-vs-all k = 1000: 200 MB per batch -- an eighth of the
+    // batch's time when it waited its turn on the search's own stream)
+    PipeLease lease;
+    rc = lease_pipes(f->device, nbatches > 1, lease);
+    if (rc) return rc;
+    const bool piped = lease.cp != nullptr;
     DevBuf *dD[2] = {&H->d_D, &H->d_D2}, *dI[2] = {&H->d_I, &H->d_I2};
     if (H->d_q.ensure((size_t)mb * f->dp * 4) || H->d_qn.ensure((size_t)mb * 4) || f->ws_tmp2.ensure((size_t)mb * f->d * 4) ||
         H->d_D.ensure((size_t)mb * k * 4) || H->d_I.ensure((size_t)mb * k * 8) || H->d_st2.ensure(64) ||
         (piped && (H->d_D2.ensure((size_t)mb * k * 4) || H->d_I2.ensure((size_t)mb * k * 8))))
         return set_err(KNN_ERR_HIP, "hnsw_search: out of device memory");
     hipStream_t s = f->stream;
-    hipEvent_t evc[2] = {nullptr, nullptr}, evd[2] = {nullptr, nullptr};
+    const ResultPipe rp{lease.cp, s, "hnsw_search: "};
     std::vector<unsigned long long> st((size_t)nbatches * 2, 0ull);
-    hipError_t e = hipSuccess;
-    if (piped)
-        for (int i = 0; i < 2 && e == hipSuccess; i++) {
-            e = hipEventCreateWithFlags(&evc[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&evd[i], hipEventDisableTiming);
-        }
+    // batch b: queries up, the pipeline above into the result buffers of `slot`, the walk's counters kept beside them
+    auto walk = [&](int64_t b, int slot) -> int {
+        const int64_t b0 = b * B, m = std::min(B, nq - b0);
+        int r = rp.hip(hipMemcpyAsync(f->ws_tmp2.p, q_host + b0 * f->d, (size_t)m * f->d * 4, hipMemcpyHostToDevice, s));
+        if (!r) r = pad_rows_dev((const float *)f->ws_tmp2.p, m, f->d, (float *)H->d_q.p, f->dp, s);
+        if (!r) r = norms_dev_impl((const float *)H->d_q.p, m, f->d, f->dp, (float *)H->d_qn.p, s);
+        if (!r)
+            r = hnsw_beam_pipeline(H, (const float *)H->d_q.p, (const float *)f->ws_tmp2.p, (const float *)H->d_qn.p, m, ef, (int)k,
+                                   (float *)dD[slot]->p, (int64_t *)dI[slot]->p, nullptr, s);
+        if (!r) r = rp.hip(hipMemcpyAsync((char *)H->d_st2.p + slot * 16, H->d_stats.p, 16, hipMemcpyDeviceToDevice, s));
+        return r;
+    };
     // results (and the walk's counters) of batch b: device -> host, on `on`
-    auto download = [&](int64_t b, hipStream_t on) -> hipError_t {
-        const int slot = piped ? (int)(b & 1) : 0;
+    auto copy = [&](int64_t b, int slot, hipStream_t on) -> hipError_t {
         const int64_t b0 = b * B, m = std::min(B, nq - b0);
         hipError_t r = hipMemcpyAsync(D_host + b0 * k, dD[slot]->p, (size_t)m * k * 4, hipMemcpyDeviceToHost, on);
         if (r == hipSuccess) r = hipMemcpyAsync(I_host + b0 * k, dI[slot]->p, (size_t)m * k * 8, hipMemcpyDeviceToHost, on);
         if (r == hipSuccess) r = hipMemcpyAsync(&st[(size_t)b * 2], (const char *)H->d_st2.p + slot * 16, 16, hipMemcpyDeviceToHost, on);
         return r;
     };
-    for (int64_t b = 0; b < nbatches && e == hipSuccess && rc == 0; b++) {
-        const int slot = piped ? (int)(b & 1) : 0;
-        const int64_t b0 = b * B, m = std::min(B, nq - b0);
-        if (piped && b >= 2) e = hipStreamWaitEvent(s, evd[slot], 0); // (the results of batch b - 2 have left these buffers)
-        if (e == hipSuccess) e = hipMemcpyAsync(f->ws_tmp2.p, q_host + b0 * f->d, (size_t)m * f->d * 4, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) break;
-        {
-            int64_t tot = m * f->dp;
-            unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535);
-            hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, (const float *)f->ws_tmp2.p, m, f->d, (float *)H->d_q.p, f->dp);
-            e = hipGetLastError();
-            if (e != hipSuccess) break;
-        }
-        rc = norms_dev_impl((const float *)H->d_q.p, m, f->d, f->dp, (float *)H->d_qn.p, s);
-        if (rc) break;
-        rc = hnsw_beam_pipeline(H, (const float *)H->d_q.p, (const float *)f->ws_tmp2.p, (const float *)H->d_qn.p, m, ef, (int)k,
-                                (float *)dD[slot]->p, (int64_t *)dI[slot]->p, nullptr, s);
-        if (rc) break;
-        e = hipMemcpyAsync((char *)H->d_st2.p + slot * 16, H->d_stats.p, 16, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) break;
-        if (!piped) {
-            e = download(b, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            continue;
-        }
-        e = hipEventRecord(evc[slot], s);
-        if (e == hipSuccess && b >= 1) { // (batch b is enqueued: the copy of batch b - 1 may block this thread as long as it likes)
-            e = hipStreamWaitEvent(cp.d2h, evc[slot ^ 1], 0);
-            if (e == hipSuccess) e = download(b - 1, cp.d2h);
-            if (e == hipSuccess) e = hipEventRecord(evd[slot ^ 1], cp.d2h);
-        }
+    for (int64_t b = 0; b < nbatches && !rc; b++) {
+        rc = rp.before(b);
+        if (!rc) rc = walk(b, rp.slot(b));
+        if (!rc) rc = rp.after(b, copy);
     }
-    if (piped) {
-        if (e == hipSuccess && rc == 0) {
-            const int slot = (int)((nbatches - 1) & 1);
-            e = hipStreamWaitEvent(cp.d2h, evc[slot], 0);
-            if (e == hipSuccess) e = download(nbatches - 1, cp.d2h);
-        }
-        (void)hipStreamSynchronize(cp.d2h);
-        (void)hipStreamSynchronize(s);
-        for (int i = 0; i < 2; i++) {
-            if (evc[i]) (void)hipEventDestroy(evc[i]);
-            if (evd[i]) (void)hipEventDestroy(evd[i]);
-        }
-    }
+    rc = rp.finish(rc, nbatches, copy);
     if (rc) return rc;
-    if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("hnsw_search: ") + hipGetErrorString(e));
     for (int64_t b = 0; b < nbatches; b++) {
         H->stat_pairs += (int64_t)st[(size_t)b * 2];
         H->stat_rounds += 1;
@@ -2610,7 +2568,7 @@ extern "C" int knn_hnsw_search(knn_hnsw_s *H, const float *q_host, int64_t nq, i
     const float pad = f->metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX;
     const int ef = (int)std::max<int64_t>(H->efSearch, k);
     if (H->g.ntotal() == 0) {
-        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = pad; I_host[i] = -1; }
+        fill_empty_host(D_host, I_host, nq * k, f->metric);
         return 0;
     }
     // the device beam serves rows of up to 1024 floats, beams of up to 1024 entries and 2^31 rows
@@ -2629,13 +2587,9 @@ extern "C" int knn_hnsw_search(knn_hnsw_s *H, const float *q_host, int64_t nq, i
         const int64_t m = std::min(B, nq - b0);
         hipStream_t s = f->stream;
         HIP_TRY(hipMemcpyAsync(f->ws_tmp2.p, q_host + b0 * f->d, (size_t)m * f->d * 4, hipMemcpyHostToDevice, s));
-        {
-            int64_t tot = m * f->dp;
-            unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535);
-            hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, (const float *)f->ws_tmp2.p, m, f->d, (float *)H->d_q.p, f->dp);
-            HIP_TRY(hipGetLastError());
-        }
-        int rc = norms_dev_impl((const float *)H->d_q.p, m, f->d, f->dp, (float *)H->d_qn.p, s);
+        int rc = pad_rows_dev((const float *)f->ws_tmp2.p, m, f->d, (float *)H->d_q.p, f->dp, s);
+        if (rc) return rc;
+        rc = norms_dev_impl((const float *)H->d_q.p, m, f->d, f->dp, (float *)H->d_qn.p, s);
         if (rc) return rc;
         std::vector<Walker> ws((size_t)m);
         for (int64_t i = 0; i < m; i++) {

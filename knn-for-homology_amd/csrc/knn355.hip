@@ -3503,6 +3503,14 @@ static int norms_dev_impl(const float *x, int64_t n, int d, int64_t stride, floa
     HIP_TRY(hipGetLastError());
     return 0;
 }
+// dst[n][dp] <- src[n][d], zero padded, on stream s (both on the device)
+static int pad_rows_dev(const float *src, int64_t n, int d, float *dst, int dp, hipStream_t s)
+{
+    const unsigned grid = (unsigned)std::min<int64_t>((n * dp + 255) / 256, 65535);
+    hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, src, n, d, dst, dp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 extern "C" int knn_normalize_l2_dev(float *x_dev, int64_t n, int32_t d, void *stream)
 {
@@ -3850,10 +3858,8 @@ static int add_dev_impl(knn_index_s *h, const float *x_dev, int64_t n, hipStream
     if (h->dp == h->d) {
         HIP_TRY(hipMemcpyAsync(dst, x_dev, (size_t)n * h->d * 4, hipMemcpyDeviceToDevice, s));
     } else {
-        int64_t total = n * h->dp;
-        unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65535);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, x_dev, n, h->d, dst, h->dp);
-        HIP_TRY(hipGetLastError());
+        int rc = pad_rows_dev(x_dev, n, h->d, dst, h->dp, s);
+        if (rc) return rc;
     }
     // norms are kept for both metrics: reconstruct/HNSW-L2 need them and they cost one pass
     int rc = norms_dev_impl(dst, n, h->d, h->dp, h->yn + h->ntotal, s);
@@ -4797,6 +4803,15 @@ __global__ void fill_empty_kernel(int64_t total, int metric, uint64_t *__restric
         I[i] = -1;
     }
 }
+// the same for results in host memory: D[n], I[n]
+static void fill_empty_host(float *D, int64_t *I, int64_t n, int metric)
+{
+    const float pad = metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX;
+    for (int64_t i = 0; i < n; i++) {
+        D[i] = pad;
+        I[i] = -1;
+    }
+}
 
 // q_dev: [nq][d] contiguous on device. D_dev/I_dev on device.
 static int search_dev_impl(knn_index_s *h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
@@ -4812,10 +4827,8 @@ static int search_dev_impl(knn_index_s *h, const float *q_dev, int64_t nq, int k
     const float *qp = q_dev;
     if (h->dp != h->d) {
         if (h->ws_q.ensure((size_t)nq * h->dp * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        int64_t tot = nq * h->dp;
-        unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, q_dev, nq, h->d, (float *)h->ws_q.p, h->dp);
-        HIP_TRY(hipGetLastError());
+        int rc = pad_rows_dev(q_dev, nq, h->d, (float *)h->ws_q.p, h->dp, s);
+        if (rc) return rc;
         qp = (const float *)h->ws_q.p;
     }
     return search_keys_impl(h, qp, nq, k, id_base, keys_dev, D_dev, I_dev, allow_stat, s);
@@ -5131,9 +5144,81 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
 struct CopyPipes {
     std::mutex mu;
     hipStream_t h2d = nullptr, d2h = nullptr;
-    hipEvent_t ev_query[2] = {nullptr, nullptr}, ev_batch[2] = {nullptr, nullptr};
+    // per result slot, for the holder of `mu` alone: the slot's queries are up, its batch is done on the search stream,
+    // its results have left the buffers
+    hipEvent_t ev_query[2] = {nullptr, nullptr}, ev_batch[2] = {nullptr, nullptr}, ev_left[2] = {nullptr, nullptr};
 };
 static CopyPipes g_pipes[64];
+
+// A caller's hold on its device's copy pipes: cp is null when the caller did not want them (`want`: its own rule, one batch
+// has nothing to overlap with) or another host search holds them; otherwise they are this caller's until the lease goes.
+// The streams and events are made on first use (the caller has set the device).
+struct PipeLease {
+    std::unique_lock<std::mutex> lock;
+    CopyPipes *cp = nullptr;
+};
+static int lease_pipes(int device, bool want, PipeLease &lease)
+{
+    CopyPipes &cp = g_pipes[device & 63];
+    lease.lock = std::unique_lock<std::mutex>(cp.mu, std::defer_lock);
+    if (!want || !lease.lock.try_lock()) return 0;
+    if (!cp.h2d) HIP_TRY(hipStreamCreateWithFlags(&cp.h2d, hipStreamNonBlocking));
+    if (!cp.d2h) HIP_TRY(hipStreamCreateWithFlags(&cp.d2h, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+        if (!cp.ev_query[i]) HIP_TRY(hipEventCreateWithFlags(&cp.ev_query[i], hipEventDisableTiming));
+        if (!cp.ev_batch[i]) HIP_TRY(hipEventCreateWithFlags(&cp.ev_batch[i], hipEventDisableTiming));
+        if (!cp.ev_left[i]) HIP_TRY(hipEventCreateWithFlags(&cp.ev_left[i], hipEventDisableTiming));
+    }
+    lease.cp = &cp;
+    return 0;
+}
+
+// The result download of a batched search whose batches follow one another on the search stream `s` (hnsw_search_device,
+// lsh_search_batches).  Piped (cp given): two sets of result buffers, and while batch b runs on `s` the results of batch
+// b - 1 go down on the copy stream, ordered by events alone -- this thread never waits inside the loop.  Not piped: one
+// set, every batch downloaded on `s` and waited for.  The caller's loop is
+//     for every batch b, while rc == 0: before(b); enqueue the batch into the buffers of slot(b); after(b, copy)
+//     return finish(rc, nbatches, copy)
+// with copy(b, slot, stream) -> hipError_t enqueueing the device-to-host copies of batch b.  Every HIP error is reported
+// under `who` ("lsh_search: ").
+struct ResultPipe {
+    CopyPipes *cp;
+    hipStream_t s;
+    const char *who;
+    int slot(int64_t b) const { return cp ? (int)(b & 1) : 0; }
+    int hip(hipError_t e) const { return e == hipSuccess ? 0 : set_err(KNN_ERR_HIP, std::string(who) + hipGetErrorString(e)); }
+    // the results of batch b - 2 have left the buffers batch b is about to write
+    int before(int64_t b) const { return cp && b >= 2 ? hip(hipStreamWaitEvent(s, cp->ev_left[b & 1], 0)) : 0; }
+    // batch b is enqueued: the copy of batch b - 1 may block this thread as long as it likes
+    template <typename Copy>
+    int after(int64_t b, Copy &&copy) const
+    {
+        if (!cp) {
+            int rc = hip(copy(b, 0, s));
+            return rc ? rc : hip(hipStreamSynchronize(s));
+        }
+        int rc = hip(hipEventRecord(cp->ev_batch[b & 1], s));
+        if (rc || b == 0) return rc;
+        rc = download(b - 1, copy);
+        return rc ? rc : hip(hipEventRecord(cp->ev_left[(b - 1) & 1], cp->d2h));
+    }
+    // rc: how the loop ended.  If well, the last batch goes down; then, whichever way it ended, BOTH streams are waited
+    // for: a download already queued writes into the caller's host arrays, and the lease is released on return.
+    template <typename Copy>
+    int finish(int rc, int64_t nbatches, Copy &&copy) const
+    {
+        if (!cp) return rc;
+        if (!rc) rc = download(nbatches - 1, copy);
+        const hipError_t e1 = hipStreamSynchronize(cp->d2h), e2 = hipStreamSynchronize(s);
+        return rc ? rc : hip(e1 != hipSuccess ? e1 : e2);
+    }
+    template <typename Copy>
+    int download(int64_t b, Copy &&copy) const
+    {
+        int rc = hip(hipStreamWaitEvent(cp->d2h, cp->ev_batch[b & 1], 0));
+        return rc ? rc : hip(copy(b, (int)(b & 1), cp->d2h));
+    }
+};
 
 // Search with results (and, unless q_host is null, queries) in host memory.  q_host == nullptr:
 // the queries are the index's own rows [self_row0, self_row0 + nq) -- already on the device and
@@ -5197,9 +5282,10 @@ static int host_search(knn_index_s *h, const float *q_host, int64_t self_row0, i
         if (h->ntotal > 0 && h->ev0 && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_ms += ms;
         return 0;
     };
-    CopyPipes &cp = g_pipes[h->device & 63];
-    std::unique_lock<std::mutex> pipes(cp.mu, std::defer_lock);
-    if (nbatches == 1 || !pipes.try_lock()) {
+    PipeLease lease;
+    rc = lease_pipes(h->device, nbatches > 1, lease);
+    if (rc) return rc;
+    if (!lease.cp) {
         h->last_ms = 0.f;
         for (int64_t b0 = 0; b0 < nq; b0 += QB) {
             rc = plain(b0, std::min(QB, nq - b0), true);
@@ -5207,14 +5293,7 @@ static int host_search(knn_index_s *h, const float *q_host, int64_t self_row0, i
         }
         return 0;
     }
-    if (!cp.h2d) {
-        HIP_TRY(hipStreamCreateWithFlags(&cp.h2d, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&cp.d2h, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipEventCreateWithFlags(&cp.ev_query[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&cp.ev_batch[i], hipEventDisableTiming));
-        }
-    }
+    CopyPipes &cp = *lease.cp;
     struct Download {
         std::thread th;
         hipError_t err = hipSuccess;
@@ -5317,23 +5396,13 @@ extern "C" int knn_flat_search_self(knn_handle h, int64_t row0, int64_t nrows, i
         h->last_ms = -1.f;
         // (a large result leaves in pieces while the later query tiles are still being served: the copy stream of the device,
         // if no other host search of this process is using it)
-        CopyPipes &cp = g_pipes[h->device & 63];
-        std::unique_lock<std::mutex> pipes(cp.mu, std::defer_lock);
-        hipStream_t d2h = nullptr;
         static const bool stream_off = getenv("KNN355_SELF_STREAM") && atoi(getenv("KNN355_SELF_STREAM")) == 0; // (A/B: the result in one piece behind the search)
-        if (!stream_off && (size_t)nrows * k * 12 >= ((size_t)dev_knob("KNN355_SELF_STREAM_MIN_MB", 32) << 20) && pipes.try_lock()) {
-            if (!cp.h2d) {
-                HIP_TRY(hipStreamCreateWithFlags(&cp.h2d, hipStreamNonBlocking));
-                HIP_TRY(hipStreamCreateWithFlags(&cp.d2h, hipStreamNonBlocking));
-                for (int i = 0; i < 2; i++) {
-                    HIP_TRY(hipEventCreateWithFlags(&cp.ev_query[i], hipEventDisableTiming));
-                    HIP_TRY(hipEventCreateWithFlags(&cp.ev_batch[i], hipEventDisableTiming));
-                }
-            }
-            d2h = cp.d2h;
+        {
+            PipeLease lease;
+            rc = lease_pipes(h->device, !stream_off && (size_t)nrows * k * 12 >= ((size_t)dev_knob("KNN355_SELF_STREAM_MIN_MB", 32) << 20), lease);
+            if (rc) return rc;
+            rc = self_search_symmetric(h, (int)k, (float *)h->ws_D.p, (int64_t *)h->ws_I.p, h->stream, D_host, I_host, lease.cp ? lease.cp->d2h : nullptr);
         }
-        rc = self_search_symmetric(h, (int)k, (float *)h->ws_D.p, (int64_t *)h->ws_I.p, h->stream, D_host, I_host, d2h);
-        if (pipes.owns_lock()) pipes.unlock();
         if (rc < 0) return rc;
         if (rc == 2) { // (the rows went out behind their groups' selections)
             HIP_TRY(hipStreamSynchronize(h->stream));
@@ -5751,13 +5820,9 @@ extern "C" int knn_gather_distances(knn_handle h, const float *q_host, int64_t n
         h->ws_I.ensure((size_t)np * 8) || h->ws_tmp.ensure((size_t)np * 4) || h->ws_D.ensure((size_t)np * 4))
         return set_err(KNN_ERR_HIP, "gather_distances: out of device memory");
     HIP_TRY(hipMemcpyAsync(h->ws_tmp2.p, q_host, (size_t)nq * h->d * 4, hipMemcpyHostToDevice, s));
-    {
-        int64_t tot = nq * h->dp;
-        unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, (const float *)h->ws_tmp2.p, nq, h->d, (float *)h->ws_q.p, h->dp);
-        HIP_TRY(hipGetLastError());
-    }
-    int rc = norms_dev_impl((const float *)h->ws_q.p, nq, h->d, h->dp, (float *)h->ws_qn.p, s);
+    int rc = pad_rows_dev((const float *)h->ws_tmp2.p, nq, h->d, (float *)h->ws_q.p, h->dp, s);
+    if (rc) return rc;
+    rc = norms_dev_impl((const float *)h->ws_q.p, nq, h->d, h->dp, (float *)h->ws_qn.p, s);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h->ws_I.p, cand_ids, (size_t)np * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->ws_tmp.p, pq.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));

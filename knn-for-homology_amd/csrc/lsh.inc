@@ -452,10 +452,8 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
         if (ms) HIP_TRY(hipEventRecord(ev[1], s));
         const float *xp = (const float *)h->ws_x.p;
         if (h->dp != h->d) {
-            int64_t tot = m * h->dp;
-            unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535);
-            hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, (const float *)h->ws_x.p, m, h->d, (float *)h->ws_xp.p, h->dp);
-            HIP_TRY(hipGetLastError());
+            int rc = pad_rows_dev((const float *)h->ws_x.p, m, h->d, (float *)h->ws_xp.p, h->dp, s);
+            if (rc) return rc;
             xp = (const float *)h->ws_xp.p;
         }
         if (xp_out) *xp_out = xp;
@@ -697,46 +695,16 @@ static int lsh_search_batches(knn_lsh_s *h, knn_index_s *flat, const float *q_ho
     const int64_t QB = flat ? std::min<int64_t>(16384, lsh_slab_rows(h)) : 16384;
     const int W = h->W;
     // Several batches (pfam/search.py searches every row, k = 1000): two sets of result buffers, and the results of batch
-    // b - 1 go down on the device's copy stream while batch b is scanned (see hnsw_search_device)
+    // b - 1 go down on the device's copy stream while batch b is scanned (ResultPipe)
     const int64_t nbatches = (nq + QB - 1) / QB;
-    CopyPipes &cp = g_pipes[h->device & 63];
-    std::unique_lock<std::mutex> pipes(cp.mu, std::defer_lock);
-    const bool piped = nbatches > 1 && pipes.try_lock();
-    if (piped && !cp.h2d) {
-        HIP_TRY(hipStreamCreateWithFlags(&cp.h2d, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&cp.d2h, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipEventCreateWithFlags(&cp.ev_query[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&cp.ev_batch[i], hipEventDisableTiming));
-        }
-    }
+    PipeLease lease;
+    int rc = lease_pipes(h->device, nbatches > 1, lease);
+    if (rc) return rc;
+    const ResultPipe rp{lease.cp, s, "lsh_search: "};
     DevBuf *dD[2] = {&h->ws_D, &h->ws_D2}, *dI[2] = {&h->ws_I, &h->ws_I2};
-    hipEvent_t evc[2] = {nullptr, nullptr}, evd[2] = {nullptr, nullptr};
-    struct EventGuard { // (the events of this call go with it, whichever way it returns)
-        hipEvent_t *a, *b;
-        ~EventGuard() { for (int i = 0; i < 2; i++) { if (a[i]) (void)hipEventDestroy(a[i]); if (b[i]) (void)hipEventDestroy(b[i]); } }
-    } guard{evc, evd};
-    if (piped)
-        for (int i = 0; i < 2; i++) {
-            HIP_TRY(hipEventCreateWithFlags(&evc[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&evd[i], hipEventDisableTiming));
-        }
-    auto download = [&](int64_t b, hipStream_t on) -> hipError_t {
-        const int slot = piped ? (int)(b & 1) : 0;
-        const int64_t c0 = b * QB, cm = std::min(QB, nq - c0);
-        hipError_t r = hipMemcpyAsync(D_host + c0 * k, dD[slot]->p, (size_t)cm * k * 4, hipMemcpyDeviceToHost, on);
-        if (r == hipSuccess) r = hipMemcpyAsync(I_host + c0 * k, dI[slot]->p, (size_t)cm * k * 8, hipMemcpyDeviceToHost, on);
-        return r;
-    };
-    // The batches as one unit: whichever way it ends -- a HIP error, an out-of-memory return -- the piped path below then waits
-    // for BOTH streams before this call returns: a download already queued on the copy stream writes into the caller's
-    // D_host / I_host, and the copy streams' mutex and this call's events are released on return (as hnsw_search_device).
-    auto batches = [&]() -> int {
-    for (int64_t b0 = 0; b0 < nq; b0 += QB) {
-        const int64_t m = std::min(QB, nq - b0);
-        const int64_t bi = b0 / QB;
-        const int slot = piped ? (int)(bi & 1) : 0;
-        if (piped && bi >= 2) HIP_TRY(hipStreamWaitEvent(s, evd[slot], 0)); // (the results of batch b - 2 have left these buffers)
+    // batch bi: queries encoded, scanned, selected (and refined) into the result buffers of `slot`
+    auto scan = [&](int64_t bi, int slot) -> int {
+        const int64_t b0 = bi * QB, m = std::min(QB, nq - b0);
         if (h->ws_q.ensure((size_t)m * W * 8)) return set_err(KNN_ERR_HIP, "lsh_search: out of device memory");
         const float *xq_dev = nullptr;
         int rc = lsh_encode_host_rows(h, q_host + b0 * h->d, m, (uint64_t *)h->ws_q.p, nullptr, 0, nullptr, &xq_dev);
@@ -790,32 +758,20 @@ static int lsh_search_batches(knn_lsh_s *h, knn_index_s *flat, const float *q_ho
             rc = refine_batch(flat, xq_dev, (const int64_t *)h->ws_cI.p, m, (int)kb, (int)k, (float *)dD[slot]->p, (int64_t *)dI[slot]->p, s, rev);
             if (rc) return rc;
         }
-        if (!piped) {
-            HIP_TRY(download(bi, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            continue;
-        }
-        HIP_TRY(hipEventRecord(evc[slot], s));
-        if (bi >= 1) { // (batch b is enqueued: the copy of batch b - 1 may block this thread as long as it likes)
-            HIP_TRY(hipStreamWaitEvent(cp.d2h, evc[slot ^ 1], 0));
-            HIP_TRY(download(bi - 1, cp.d2h));
-            HIP_TRY(hipEventRecord(evd[slot ^ 1], cp.d2h));
-        }
-    }
-    if (piped) {
-        const int slot = (int)((nbatches - 1) & 1);
-        HIP_TRY(hipStreamWaitEvent(cp.d2h, evc[slot], 0));
-        HIP_TRY(download(nbatches - 1, cp.d2h));
-    }
-    return 0;
+        return 0;
     };
-    int rc = batches();
-    if (piped) {
-        const hipError_t e1 = hipStreamSynchronize(cp.d2h), e2 = hipStreamSynchronize(s);
-        if (!rc && (e1 != hipSuccess || e2 != hipSuccess))
-            rc = set_err(KNN_ERR_HIP, std::string("lsh_search: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    auto copy = [&](int64_t bi, int slot, hipStream_t on) -> hipError_t {
+        const int64_t b0 = bi * QB, m = std::min(QB, nq - b0);
+        hipError_t r = hipMemcpyAsync(D_host + b0 * k, dD[slot]->p, (size_t)m * k * 4, hipMemcpyDeviceToHost, on);
+        if (r == hipSuccess) r = hipMemcpyAsync(I_host + b0 * k, dI[slot]->p, (size_t)m * k * 8, hipMemcpyDeviceToHost, on);
+        return r;
+    };
+    for (int64_t bi = 0; bi < nbatches && !rc; bi++) {
+        rc = rp.before(bi);
+        if (!rc) rc = scan(bi, rp.slot(bi));
+        if (!rc) rc = rp.after(bi, copy);
     }
-    return rc;
+    return rp.finish(rc, nbatches, copy);
 }
 
 extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int64_t k, float *D_host, int64_t *I_host)
@@ -828,7 +784,7 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
     std::lock_guard<std::mutex> lk(h->mu);
     HIP_TRY(hipSetDevice(h->device));
     if (h->ntotal == 0) {
-        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = FLT_MAX; I_host[i] = -1; }
+        fill_empty_host(D_host, I_host, nq * k, KNN_METRIC_L2); // (Hamming distances: smaller is better)
         return 0;
     }
     RefineEvents none;
@@ -854,7 +810,7 @@ extern "C" int knn_lsh_search_refine(knn_lsh_s *h, knn_handle flat, const float 
                                             std::to_string(flat->d) + ", " + std::to_string(flat->ntotal) + " rows) do not hold the same rows");
     HIP_TRY(hipSetDevice(h->device));
     if (h->ntotal == 0) {
-        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = flat->metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX; I_host[i] = -1; }
+        fill_empty_host(D_host, I_host, nq * k, flat->metric);
         return 0;
     }
     HIP_TRY(hipStreamSynchronize(flat->stream)); // (the rows are read on the LSH handle's stream: whatever the flat handle's own stream still does to them first)

@@ -383,10 +383,8 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
             xq = (const float *)h->ws_rq.p;
             if (dp != h->d) {
                 if (h->ws_q.ensure((size_t)m * dp * 4, h->done, s)) return set_err(KNN_ERR_HIP, "range_search: out of device memory");
-                const int64_t tot = m * dp;
-                hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 65535)), dim3(256), 0, s,
-                                   xq, m, h->d, (float *)h->ws_q.p, dp);
-                HIP_TRY(hipGetLastError());
+                int rc = pad_rows_dev(xq, m, h->d, (float *)h->ws_q.p, dp, s);
+                if (rc) return rc;
                 xq = (const float *)h->ws_q.p;
             }
             if (l2 && !diff) {

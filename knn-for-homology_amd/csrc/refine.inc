@@ -195,7 +195,7 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
             return set_err(KNN_ERR_INVALID, "flat_refine: label " + std::to_string(labels_host[i]) + " of query " + std::to_string(i / kb) +
                                                 " is outside the index (" + std::to_string(h->ntotal) + " rows)");
     if (h->ntotal == 0) {
-        for (int64_t i = 0; i < nq * k; i++) { D_host[i] = h->metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX; I_host[i] = -1; }
+        fill_empty_host(D_host, I_host, nq * k, h->metric);
         return 0;
     }
     HIP_TRY(hipSetDevice(h->device));
@@ -212,10 +212,7 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
         HIP_TRY(hipMemcpyAsync(h->ws_rfq.p, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
         const float *xq = (const float *)h->ws_rfq.p;
         if (h->dp != h->d) {
-            const int64_t tot = m * h->dp;
-            const unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 65535);
-            hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, (const float *)h->ws_rfq.p, m, h->d, (float *)h->ws_rfqp.p, h->dp);
-            HIP_TRY(hipGetLastError());
+            if ((rc = pad_rows_dev((const float *)h->ws_rfq.p, m, h->d, (float *)h->ws_rfqp.p, h->dp, s))) return rc;
             xq = (const float *)h->ws_rfqp.p;
         }
         HIP_TRY(hipMemcpyAsync(h->ws_rfI.p, labels_host + b0 * kb, (size_t)m * kb * 8, hipMemcpyHostToDevice, s));
