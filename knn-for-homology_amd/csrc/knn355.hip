@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../../include/knn355.h"
+#include "plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -812,14 +813,6 @@ struct ScanParams {
 __host__ __device__ __forceinline__ int64_t view_row(int64_t r, int row_mul, int vshift)
 {
     return ((r >> vshift) * row_mul << vshift) + (r & (((int64_t)1 << vshift) - 1));
-}
-// rows of the view with stride row_mul over a database of n rows
-static inline int64_t view_rows(int64_t n, int row_mul, int vshift)
-{
-    const int64_t B = (int64_t)1 << vshift, span = B * row_mul;
-    if (n <= 0) return 0;
-    const int64_t last = (n - 1) / span; // last block that starts inside the database
-    return last * B + std::min<int64_t>(B, n - last * span);
 }
 
 // ---- per-workgroup candidate lists shared by the scan kernels -------------------------
@@ -3941,34 +3934,6 @@ extern "C" int knn_flat_reconstruct(knn_handle h, int64_t i0, int64_t n, float *
     return 0;
 }
 
-// ---- search ---------------------------------------------------------------
-// A chunk hands on at most kslot = 1.25 k keys per query (k for k > 1536); the final selection
-// is exact.  The register select inside the scan kernels serves k <= 1536 (lists of <= 2048
-// keys, 32 per lane, so that 1.25 k + one tile fits); beyond that the workgroup sort takes
-// exactly k.
-static const int KNN_WAVE_SELECT_MAX_K = 2048;    // one wave selects a list: in registers up to ...
-// ... this k (2048-key lists), by probing a 4096-key list in memory beyond.  1.25 k keys + a tile of appends fit a 2048-key
-// list up to k = 1536, but the closer k gets the less room a cut leaves and the more often a list is cut: measured crossover
-// at k ~ 1400 (2 M rows x 1024 queries: k = 1400 43.4 ms either way, k = 1536 51.3 ms with 2048-key lists, 44.8 with 4096)
-static const int KNN_REGISTER_SELECT_MAX_K = 1400;
-// (developer build: integer knobs from the environment; the shipped library has the defaults compiled in)
-static int dev_knob(const char *name, int dflt)
-{
-#ifdef KNN355_DEV
-    if (getenv(name)) return atoi(getenv(name));
-#endif
-    (void)name;
-    return dflt;
-}
-static int knn_kslot(int k) { return k > KNN_WAVE_SELECT_MAX_K ? k : k + k / 4; }
-
-static int next_pow2_host(int n)
-{
-    int p = 64;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 // one workgroup per query: best k of its candidate keys (see select_topk_kernel).  tmp: scratch for the segment
 // pass of arrays longer than one workgroup's registers hold.
 static const int KNN_SELECT_SEG = 32768;
@@ -4039,22 +4004,6 @@ static int launch_select(SelectParams sp, hipStream_t s, DevBuf *tmp = nullptr)
     return 0;
 }
 
-struct ScanPlan {
-    int qt, dt, nqtiles, nchunks, cap, grid;
-    int npairs; // > 0: paired walk -- grid = nchunks = 2 npairs workgroups, tiles_base / tiles_rem split the tiles over the PAIRS
-    bool diff;  // squared L2 as the sum of squared differences (FAISS's small-batch formula), see flat_scan_kernel<..., DIFF>
-    int64_t chunk_rows;
-    int tiles_base, tiles_rem;
-    size_t lds;
-    const char *name;
-};
-
-
-// the difference build that serves a batch of nq < 20 queries: its width (a multiple of 4: two query pairs per thread half)
-// (no 4-query build: with two chains per thread it is bound by their dependent latency -- 6.9 ms per 10 M rows where the 8-query
-// build, four chains per thread, reads at the HBM rate: 6.25 ms)
-static int diff_build_width(int64_t nq) { return nq <= 8 ? 8 : (nq <= 12 ? 12 : (nq <= 16 ? 16 : 20)); }
-
 // Which pass of a prefiltered search (search_view_s16) a search_view call enqueues, and what that pass reads.  The default is
 // a plain search.
 struct S16Pass {
@@ -4065,220 +4014,63 @@ struct S16Pass {
     uint32_t *gate_count = nullptr;  // 2: counts the fallbacks taken (SelectParams::gate_count)
 };
 
-// one scan launch: plan.grid workgroups of 256 threads with plan.lds bytes of dynamic LDS
-static int launch_scan(void (*kern)(ScanParams), const ScanParams &p, const ScanPlan &plan, hipStream_t s)
+typedef void (*ScanKernel)(ScanParams);
+
+// a scan build's opt-in to lds bytes of dynamic LDS: once in front of the launch(es) of a search
+static int scan_lds_opt_in(ScanKernel kern, size_t lds)
 {
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(256), plan.lds, s, p);
+    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return 0;
+}
+
+// one scan launch: grid workgroups of 256 threads with lds bytes of dynamic LDS
+static int launch_scan(ScanKernel kern, const ScanParams &p, int grid, size_t lds, hipStream_t s)
+{
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+// the builds of one wave layout: fp32 or bf16 rows; one query tile (rows are read once, non-temporal staging loads) or several
 template <int WM, int WN, int TM, int TN>
-static int launch_scan_cfg(const knn_index_s *h, const S16Pass &pass, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
+static ScanKernel scan_build(bool l2, bool approx16, bool one_qtile)
 {
-    const bool l2 = h->metric == KNN_METRIC_L2;
-    if (pass.mode == 1) { // the 16-bit pass of a prefiltered search (search_view_s16)
-        if constexpr (WM == 4 && WN == 1 && TM == 2 && TN == 1) {
-            if (p.nqtiles != 1 || l2) return set_err(KNN_ERR_INVALID, "scan: the 16-bit prefilter serves one 32-query tile, inner product");
-            return launch_scan(flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>, p, plan, s);
-        }
-        return set_err(KNN_ERR_INVALID, "scan: the 16-bit prefilter has the 32-query build only");
+    if (approx16) {
+        if (one_qtile) return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, true, false, true>;
+        return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, false, false, true>;
     }
-    // one query tile: rows are read once, non-temporal staging loads
-    if constexpr (WM == 4 && TM == 2) {
-        if (plan.diff) {
-            // (builds for up to 8, 12, 16 and 19 queries: the vector work of a K step grows with the build's width -- up to 8
-            // queries scan at the speed of their HBM traffic)
-            switch (diff_build_width(p.nq)) {
-            case 8: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 8>, p, plan, s);
-            case 12: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 12>, p, plan, s);
-            case 16: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 16>, p, plan, s);
-            default: return launch_scan(flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 20>, p, plan, s);
-            }
-        }
+    if (one_qtile) return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true> : flat_scan_kernel<WM, WN, TM, TN, false, true>;
+    return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false> : flat_scan_kernel<WM, WN, TM, TN, false, false>;
+}
+
+// The flat_scan_kernel build that serves a launch: query tile qt, squared L2 or inner product, bf16 rows, one query tile or
+// several, the width of the difference build (0: none), the pass of a prefiltered search (S16Pass::mode).  nullptr with the
+// error set when no build serves the combination (scan_kernel_illegal, plan.h).
+static ScanKernel pick_scan_kernel(int qt, bool l2, bool approx16, bool one_qtile, int diff_width, int pass_mode)
+{
+    if (const char *why = scan_kernel_illegal(qt, l2, approx16, one_qtile, pass_mode)) {
+        set_err(KNN_ERR_INVALID, why);
+        return nullptr;
     }
-    void (*kern)(ScanParams) = nullptr;
-    if (h->approx16) {
-        if (p.nqtiles == 1) kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, true, false, true>;
-        else kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, false, false, true>;
-    } else if (p.nqtiles == 1) kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true> : flat_scan_kernel<WM, WN, TM, TN, false, true>;
-    else kern = l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false> : flat_scan_kernel<WM, WN, TM, TN, false, false>;
-    return launch_scan(kern, p, plan, s);
-}
-
-// the 256 x 256 tile (2 x 2 waves of 4 x 4 MFMA tiles, one workgroup per CU): plain fp32 rows, several query tiles per launch
-static int launch_scan_big(const knn_index_s *h, const S16Pass &pass, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
-{
-    if (h->approx16 || pass.mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 256-query tile serves plain fp32 rows");
-    return launch_scan(h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 4, 4, true, false> : flat_scan_kernel<2, 2, 4, 4, false, false>, p, plan, s);
-}
-
-// the builds on 16-query blocks (48 queries: 4 x 1 waves, 96: 2 x 2 waves; Q16 blocks per wave): one query tile per launch
-template <int WM, int WN, int TM, int Q16>
-static int launch_scan16(const knn_index_s *h, const S16Pass &pass, const ScanParams &p, const ScanPlan &plan, hipStream_t s)
-{
-    if (p.nqtiles != 1 || h->approx16 || pass.mode == 1) return set_err(KNN_ERR_INVALID, "scan: the 16-query-block builds serve one query tile of plain fp32 rows");
-    return launch_scan(h->metric == KNN_METRIC_L2 ? flat_scan_kernel<WM, WN, TM, 1, true, true, false, false, 0, Q16>
-                                                  : flat_scan_kernel<WM, WN, TM, 1, false, true, false, false, 0, Q16>,
-                       p, plan, s);
-}
-
-// knn_set_tuning rules that several plan decisions share
-// the statistical seed may run: seeding on, the exact seed not forced, the estimate not forbidden
-static bool stat_seed_allowed(const knn_index_s *h) { return !(h->flags & (KNN_TUNE_NO_SEED | KNN_TUNE_EXACT_SEED | KNN_TUNE_NO_STAT_SEED)); }
-// the tile-minimum seed may run: seeding on, neither the exact nor the statistical seed forced, the tile-minimum seed not forbidden
-static bool tile_min_seed_allowed(const knn_index_s *h)
-{
-    return !(h->flags & (KNN_TUNE_NO_SEED | KNN_TUNE_EXACT_SEED | KNN_TUNE_STAT_SEED | KNN_TUNE_NO_TILE_MIN_SEED));
-}
-
-// Does the 256 x 256 tile (flat_scan_kernel<2, 2, 4, 4>: one workgroup per CU) serve this search?  Its K loop keeps the matrix
-// pipe busier than two co-resident 128 x 128 workgroups do, but nothing hides its epilogues, a launch has half the
-// workgroups and four times the tile: it wants long chunks on every CU -- Pfam-sized batches, not CATH-sized ones.
-// KNN_TUNE_NO_BIG_TILE: never; KNN_TUNE_BIG_TILE: wherever a batch has more than 128 queries (tests, A/B).
-static bool big_tile_pays(const knn_index_s *h, int64_t nb, int64_t nq)
-{
-    if (h->approx16 || (h->flags & KNN_TUNE_NO_BIG_TILE) || nq <= 128) return false;
-    if (h->flags & KNN_TUNE_BIG_TILE) return nb >= 1024;
-    if (nb < 65536) return false; // (never a seed sample's own scan)
-    const int64_t cus = std::max(1, h->num_cus);
-    const int64_t work = ((nq + 255) / 256) * ((nb + 255) / 256); // 256 x 256 tiles of the search
-    // (24 tiles per CU: 1 M rows x 512 queries 8.27 against 8.78 ms, 500 k x 1024 8.16 against 8.47, 400 k x 1024 7.11 against 7.3,
-    // 200 k x 2048 6.73 against 6.80 -- the bound was 32 until late in round 5.)
-    // (from ONE wide query tile on: 10 M rows x 256 / 512 / 768 / 1024 / 1536 queries 38.1 / 79.1 / 117.6 / 152.4 / 234.4 ms against
-    // 41.4 / 89.4 / 130.8 / 172.0 / 248.8 on the 128 x 128 tile, one box; until late in round 5 the bound was 2048)
-    return nq >= dev_knob("KNN355_BIG_MIN_NQ", 256) && work >= (int64_t)dev_knob("KNN355_BIG_MIN_TILES_PER_CU", 24) * cus;
-}
-
-static void make_plan(const knn_index_s *h, int64_t nb, int64_t nq, int k, bool seeded, ScanPlan &pl, bool allow_pairs = false, bool allow_big = true)
-{
-    int qt = h->force_qt;
-    // (48 and 96: the 16-query-block builds, one query tile per launch only -- a forced one is honoured if it holds the batch)
-    if ((qt == 48 || qt == 96) && (nq > qt || h->approx16)) qt = 0;
-    if (qt == 256 && (h->approx16 || nq <= 128)) qt = 0; // (the 256 x 256 tile: plain fp32 rows, more than one 128-query tile of queries)
-    if (qt != 32 && qt != 48 && qt != 64 && qt != 96 && qt != 128 && qt != 256) {
-        qt = nq <= 32 ? 32 : (nq <= 64 ? 64 : 128);
-        if (!h->approx16 && !(h->flags & KNN_TUNE_NO_Q16)) { // (KNN_TUNE_NO_Q16: without the 16-query-block builds)
-            if (nq > 32 && nq <= 48) qt = 48;
-            else if (nq > 64 && nq <= 96) qt = 96;
-        }
-        if (allow_big && big_tile_pays(h, nb, nq)) qt = 256;
+    switch (qt) {
+    case 256: return l2 ? flat_scan_kernel<2, 2, 4, 4, true, false> : flat_scan_kernel<2, 2, 4, 4, false, false>;
+    case 128: return scan_build<2, 2, 2, 2>(l2, approx16, one_qtile);
+    // (16-query blocks, three per wave)
+    case 96: return l2 ? flat_scan_kernel<2, 2, 2, 1, true, true, false, false, 0, 3> : flat_scan_kernel<2, 2, 2, 1, false, true, false, false, 0, 3>;
+    case 48: return l2 ? flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 0, 3> : flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 3>;
+    case 64: return scan_build<2, 2, 2, 1>(l2, approx16, one_qtile);
     }
-    // FAISS's squared L2 for fewer than 20 queries: the sum of squared differences (KNN_TUNE_NORM_L2: the norm formula throughout).
-    // FAISS decides on the batch its caller handed over, so a piece of a larger batch (the last block of 16384 queries, the
-    // remainder behind the full query tiles) keeps the formula of the whole.
-    const bool small_batch = (h->batch_nq ? h->batch_nq : nq) < 20 && nq < 20;
-    if (h->metric == KNN_METRIC_L2 && small_batch && !h->approx16 && !(h->flags & KNN_TUNE_NORM_L2)) qt = 32; // (the difference build exists for the 32-query tile only)
-    pl.qt = qt;
-    pl.dt = (qt == 32 || qt == 48 || qt == 256) ? 256 : 128;
-    pl.diff = h->metric == KNN_METRIC_L2 && small_batch && qt == 32 && !h->approx16 && !(h->flags & KNN_TUNE_NORM_L2);
-    pl.name = pl.diff ? "flat_scan_q32_d256_l2diff"
-                      : (qt == 256 ? "flat_scan_q256_d256" : qt == 128 ? "flat_scan_q128_d128" : (qt == 96 ? "flat_scan_q96_d128" : (qt == 64 ? "flat_scan_q64_d128" : (qt == 48 ? "flat_scan_q48_d256" : "flat_scan_q32_d256"))));
-    pl.nqtiles = (int)((nq + qt - 1) / qt);
-    pl.cap = next_pow2_host(2 * k + pl.dt);
-    if (pl.cap < 512) pl.cap = 512;
-    // (the 256 x 256 tile: nothing hides a cut of its 256 lists on four waves -- 220 us, a K loop's worth: room for three tiles
-    // of appends between cuts)
-    if (qt == 256 && pl.cap < 1024) pl.cap = 1024;
-    int regsel_max = KNN_REGISTER_SELECT_MAX_K;
-#ifdef KNN355_DEV
-    if (getenv("KNN355_REGSEL_MAX_K")) regsel_max = atoi(getenv("KNN355_REGSEL_MAX_K")); // (developer build: where the 4096-key lists take over)
-#endif
-    if (k <= regsel_max) pl.cap = std::min(pl.cap, 2048); // register select: <= 32 keys per lane
-    else if (k <= KNN_WAVE_SELECT_MAX_K) pl.cap = std::min(pl.cap, 4096);  // wave_select_mem: 1.25 k + a tile of appends fit
-    const int64_t ntiles = (nb + pl.dt - 1) / pl.dt;
-    pl.npairs = 0;
-    if (allow_pairs && pl.nqtiles == 1 && qt != 256 && h->force_chunks <= 0 && !(h->flags & KNN_TUNE_NO_PAIRS) && ntiles >= (int64_t)dev_knob("KNN355_PAIR_MIN_TILES", 64)) {
-        // one query tile, plenty of tiles: two workgroups per CU, paired (see flat_scan_kernel): each pair shares a
-        // contiguous range of ~ ntiles / CUs tiles (at least two: fewer pairs than CUs on a small database)
-        pl.npairs = (int)std::min<int64_t>(std::max(1, h->num_cus), ntiles / 2);
-        pl.nchunks = 2 * pl.npairs;
-        pl.grid = pl.nchunks;
-        pl.tiles_base = (int)(ntiles / pl.npairs);
-        pl.tiles_rem = (int)(ntiles % pl.npairs);
-        pl.chunk_rows = (int64_t)(pl.tiles_base + (pl.tiles_rem ? 1 : 0)) * pl.dt;
-        pl.lds = std::max((size_t)2 * (pl.dt + pl.qt) * 128, (size_t)pl.cap * 8) + (size_t)qt * 12 + 16 + (size_t)pl.dt * 4 + (size_t)qt * 8;
-        return;
+    if (pass_mode == 1) return flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>; // the 16-bit pass of a prefiltered search (search_view_s16)
+    // (difference builds for up to 8, 12, 16 and 19 queries: the vector work of a K step grows with the build's width -- up to 8
+    // queries scan at the speed of their HBM traffic)
+    switch (diff_width) {
+    case 0: break;
+    case 8: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 8>;
+    case 12: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 12>;
+    case 16: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 16>;
+    default: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 20>;
     }
-    // workgroups resident per CU: two, or the one 256 x 256 workgroup
-    const int per_cu = qt == 256 ? 1 : 2;
-    int64_t want = h->force_chunks > 0 ? h->force_chunks : (512 * per_cu + pl.nqtiles - 1) / pl.nqtiles;
-    // an unseeded chunk should see enough rows to amortise its threshold warm-up; a seeded pass
-    // starts with good thresholds and a tiny view (a seed sample) just wants parallelism
-    int64_t min_tiles = std::max<int64_t>(2, (4 * (int64_t)k + pl.dt - 1) / pl.dt);
-    if (h->force_chunks <= 0 && !seeded && nb >= 8192) want = std::min(want, std::max<int64_t>(1, ntiles / min_tiles));
-    want = std::max<int64_t>(1, std::min(want, ntiles));
-    // bound the candidate-list workspace (<= 2 GiB)
-    const size_t per_wg = (size_t)qt * pl.cap * 8;
-    int64_t max_wgs = std::max<int64_t>(pl.nqtiles, (int64_t)((2ull << 30) / per_wg));
-    const int64_t want_max = std::max<int64_t>(1, std::min(ntiles, max_wgs / pl.nqtiles));
-    want = std::min(want, want_max);
-    if (h->force_chunks <= 0) {
-        // wave quantisation: workgroups run in rounds of (2 per CU); pick the chunk count near
-        // `want` that minimises rounds x tiles-per-chunk (14433 x 14433: 9 chunks = 2 full
-        // rounds of 13 tiles beat 10 chunks = 2.2 rounds of 12)
-        const int64_t slots = per_cu * (int64_t)std::max(1, h->num_cus);
-        int64_t best = want, best_cost = INT64_MAX;
-        for (int64_t c = std::max<int64_t>(1, want / 2); c <= std::min(want_max, want + want / 2 + 1); c++) {
-            const int64_t rounds = (pl.nqtiles * c + slots - 1) / slots;
-            // per chunk: its tiles + about half a tile of fixed work (prologue, cutting the lists
-            // and writing the survivors) -- 1.25 M rows x 32 queries: 489 chunks of 10 tiles in
-            // one round beat 977 chunks of 5 tiles in two
-            const int64_t cost = rounds * (2 * ((ntiles + c - 1) / c) + 1);
-            if (cost < best_cost || (cost == best_cost && c > best)) { best = c; best_cost = cost; }
-        }
-        want = best;
-    }
-    int64_t tiles_per = (ntiles + want - 1) / want;
-    // balanced split: the first (ntiles mod nchunks) chunks walk one tile more.  (A uniform chunk length left the
-    // last chunk short -- 14433 rows in 9 chunks: 8 x 13 tiles + 9 -- and the two rounds of workgroups took 13 + 13
-    // tile times; 5 x 13 + 4 x 12 takes 13 + 12.)
-    pl.nchunks = (int)((ntiles + tiles_per - 1) / tiles_per);
-    pl.tiles_base = (int)(ntiles / pl.nchunks);
-    pl.tiles_rem = (int)(ntiles % pl.nchunks);
-    pl.chunk_rows = (int64_t)(pl.tiles_base + (pl.tiles_rem ? 1 : 0)) * pl.dt; // (the longest chunk)
-    pl.grid = pl.nqtiles * pl.nchunks;
-    pl.lds = std::max((size_t)2 * (pl.dt + pl.qt) * 128, (size_t)pl.cap * 8) + (size_t)qt * 12 + 16 + (size_t)pl.dt * 4 + (size_t)qt * 8; // (+ s_pub)
-}
-
-// Seed stride of a view with nb rows: a power of two s such that the sample (every s-th 8-row block)
-// has about max(2 * chunk_rows, 64 k) rows (and at most nb/8).  The sample is searched first,
-// exactly; its k-th score bounds the global k-th from above, so every chunk of the main pass
-// starts with a tight threshold and appends about chunk_rows * k / sample_rows <= k/2
-// candidates per query instead of warming up (and compacting) on its own.
-static int seed_stride(int64_t nb, int k, int64_t chunk_rows)
-{
-    const int64_t target = std::min<int64_t>(std::max<int64_t>(2 * chunk_rows, 64 * (int64_t)k), nb / 8);
-    int s = 8;
-    while ((int64_t)s * 2 * target <= nb && s < (1 << 20)) s *= 2;
-    return s;
-}
-
-// Statistical seed (batch regime).  The exact seed above needs a sample of >= k rows whose k-th
-// score is a PROVEN bound of the global k-th: with k = 301 of 14433 rows no affordable sample gives a
-// useful one, every chunk warms up on its own and half of all scores go through the candidate lists.
-// Instead: T = the j-th best score of a sample of S rows, j << k chosen so that, were the sample
-// drawn at random, fewer than k of the N rows beat T with probability <= 1e-9 per query
-// (P[Binomial(S, k/N) >= j] <= 1e-9).  Every chunk filters with T from its first tile on (about
-// j N / S candidates per query instead of ~ chunks x k (1 + ln(rows per chunk / k))).  T is only
-// an estimate, so the result is VERIFIED: the final selection checks that the k-th score it found is
-// <= T -- then at least k rows beat T, all of them were candidates, and the result is exact.  A
-// query that fails the check raises a flag and the search is redone without the estimate (the
-// caller must be able to wait for the flag: synchronous entry points only).
-static int stat_seed_rank(int64_t S, int64_t N, int k)
-{
-    if (S < 64 || N <= 0 || k >= N) return -1;
-    const double pr = (double)k / (double)N, eps = 1e-9;
-    // smallest j with P[Bin(S, pr) >= j] <= eps: walk the pmf upwards, accumulating the lower tail
-    const double lp = log(pr), lq = log1p(-pr);
-    double cdf = 0.0;
-    const int64_t jmax = std::min<int64_t>(S, k);
-    for (int64_t i = 0; i <= jmax; i++) {
-        if (1.0 - cdf <= eps) return i >= 1 ? (int)i : 1; // P[X >= i] = 1 - P[X <= i-1]
-        cdf += exp(lgamma((double)S + 1.0) - lgamma((double)i + 1.0) - lgamma((double)(S - i) + 1.0) + (double)i * lp + (double)(S - i) * lq);
-    }
-    return -1; // would need more than min(S, k) sample hits: no statistical seed
+    return scan_build<4, 1, 2, 1>(l2, approx16, one_qtile);
 }
 
 // where the result of a (view) search goes
@@ -4299,20 +4091,14 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
                        int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag = nullptr,
                        const S16Pass &pass = S16Pass());
 
-// approximate keys the 16-bit pass hands to the re-scoring tail: room for the window above the k-th (fp16 on normalised
-// rows: a few percent of k beyond it at 10 M rows, k = 100)
-static int s16_kprime(int k) { return std::min(KNN_WAVE_SELECT_MAX_K, std::max(2 * k, k + 64)); }
-
-// Does a search of the view take the prefiltered path?  A one-query-tile streaming search (the 32-query build) by inner
-// product over an index whose fp16 copies cover every row, from nb >= 2^18 rows on (below that the fp32 scan's fixed costs
-// dominate and the tail's launches would not pay).  Batch, symmetric, difference, HNSW and range searches never do.
-static bool s16_eligible(const knn_index_s *h, const S16Pass &pass, int64_t nb, int64_t nq, int k, int row_mul, int level, const SearchOut &out)
+// what the planner (plan.h) reads from a handle
+static PlanCtx plan_ctx(const knn_index_s *h)
 {
-    if (h->scan16 != 1 || !h->s16_ok->load() || !h->s16_rows || pass.mode || level != 0 || row_mul != 1 || out.seed_cnt) return false;
-    if (h->metric != KNN_METRIC_INNER_PRODUCT || h->approx16 || (h->flags & KNN_TUNE_NO_SCAN16)) return false;
-    if (nq < 1 || nq > 32 || (h->force_qt != 0 && h->force_qt != 32) || s16_kprime(k) <= k) return false; // (k' = k: no room for a window)
-    if ((size_t)h->dp * 4 + 64 > 65536) return false; // (rescore16_kernel holds the query in LDS, no opt-in beyond 64 KB)
-    return nb >= (1 << 18) || (h->flags & KNN_TUNE_SCAN16_ANY_NB);
+    PlanCtx c;
+    c.metric = h->metric; c.approx16 = h->approx16;
+    c.flags = h->flags; c.force_qt = h->force_qt; c.force_chunks = h->force_chunks;
+    c.num_cus = h->num_cus; c.batch_nq = h->batch_nq; c.pub_rounds_force = h->pub_rounds_force; c.ntotal = h->ntotal;
+    return c;
 }
 
 // One prefiltered search, six launches on the caller's stream, no host wait:
@@ -4377,122 +4163,14 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
                        int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag, const S16Pass &pass)
 {
     const int64_t nb = view_rows(h->ntotal, row_mul, vshift);
-    if (s16_eligible(h, pass, nb, nq, k, row_mul, level, out)) return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
-    ScanPlan pl;
-    const bool allow_pairs = !h->approx16; // (the bf16 build has no one-query-tile streaming case worth pairing)
-    // the statistical seed may serve this search (its caller checks the verification flag)
-    const bool stat_ok = allow_stat && level == 0 && row_mul == 1 && stat_seed_allowed(h);
-    // (the 256 x 256 tile needs the statistical seed -- see below -- so only callers that can check its verification flag get it)
-    const bool allow_big = stat_ok || (h->flags & KNN_TUNE_BIG_TILE);
-    make_plan(h, nb, nq, k, true, pl, allow_pairs, allow_big);
+    const PlanCtx c = plan_ctx(h);
+    if (h->scan16 == 1 && h->s16_ok->load() && h->s16_rows && !out.seed_cnt && s16_eligible(c, pass.mode, nb, nq, k, row_mul, level, h->dp))
+        return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
     if (level >= knn_index_s::MAX_LEVELS) return set_err(KNN_ERR_INVALID, "search: seed recursion too deep");
-    // Exact seeding pays when the sample that gives every chunk a tight threshold (about two chunks'
-    // worth of rows, at least 64 k) is a small fraction of the view: the streaming regime (few
-    // queries, huge database, hundreds of chunks).  KNN_TUNE_NO_SEED turns all seeding off, KNN_TUNE_EXACT_SEED
-    // forces the exact seed, KNN_TUNE_STAT_SEED forces the statistical one, KNN_TUNE_NO_STAT_SEED forbids it (tests).
-    bool seed = nb >= 512 * (int64_t)k && std::max<int64_t>(2 * pl.chunk_rows, 64 * (int64_t)k) <= nb / 32;
-    if (h->flags & KNN_TUNE_EXACT_SEED) seed = nb >= 8192 && nb >= 32 * (int64_t)k;
-    if (h->flags & (KNN_TUNE_NO_SEED | KNN_TUNE_STAT_SEED)) seed = false;
-    // (the 256 x 256 tile under a caller that can check the verification flag: the statistical estimate from every 256th row
-    // instead of an exact search of every 32nd -- 10 M rows x 512 / 768 / 1536 queries 0.854 / 0.869 / 0.858 of the MFMA peak with
-    // the exact seed where 1024 / 2048 queries, which the rule above leaves to the estimate, reach 0.887; the exact seed stays
-    // the fallback when no rank qualifies)
-    const bool exact_ok = seed;
-    if (seed && pl.qt == 256 && stat_ok) seed = false;
-    int sstride = seed ? seed_stride(nb, k, pl.chunk_rows) : 0;
-    int seed_j = k, seed_stat = 0, svshift = vshift;
-    double expect_n = 0; // typical candidates per query at the final selection (0: unknown, assume the capacity)
-    if (!seed && stat_ok) {
-        // statistical seed: single rows, every 32nd (every 16th of a small database, every 64th of a
-        // large one): a few percent of the work, one round of workgroups at CATH size
-        int st = nb >= (1 << 20) ? 64 : (nb >= 8192 ? 32 : 16);
-        // The 256 x 256 tile (one workgroup per CU) ALWAYS wants the estimate, and from a sparser sample: nothing on the CU hides
-        // an unseeded chunk's warm-up -- every score appended until the lists first fill, a stale bound for the ~25 tiles up to
-        // the next cut (10 % of the scores pass: the sparse epilogue's lanes run out of slots and the tiles are filtered the
-        // dense way), cuts of 256 lists on four waves -- Pfam-sized k = 100: 52.2 ms per 16384-query launch unseeded, 48.1
-        // seeded; and the sample pass is what the seed costs: 1.93 ms per launch with every 32nd row, a quarter of that with
-        // every 128th, for twice the candidates (0.8 % of the scores instead of 0.4 %: the epilogue does not notice).
-        ScanPlan un;
-        make_plan(h, nb, nq, k, false, un, false, allow_big);
-        const bool big = un.qt == 256;
-        if (big) st *= k <= 256 ? 4 : 2;
-#ifdef KNN355_DEV
-        if (getenv("KNN355_STAT_STRIDE")) st = atoi(getenv("KNN355_STAT_STRIDE")); // (developer build: the statistical sample's stride)
-#endif
-        const bool force = (h->flags & KNN_TUNE_STAT_SEED) != 0;
-        const int64_t S = view_rows(nb, st, 0);
-        const int j = stat_seed_rank(S, nb, k);
-        if (j > 0 && (force || (nq >= dev_knob("KNN355_STAT_MIN_NQ", 65) && nb >= 8192))) {
-            // worth it only if it removes most of the candidates an unseeded pass would collect
-            // (an unseeded chunk appends every score until its list first fills, cap - dt keys, whatever k is; then about
-            // k more per e-fold of rows)
-            const double warm = std::min<double>((double)un.cap - un.dt, (double)un.chunk_rows);
-            const double unseeded = (double)un.nchunks * std::max(warm, k * (1.0 + log(std::max(1.0, (double)un.chunk_rows / k))));
-            const double seeded = (double)j * (double)nb / (double)S;
-            // ... and if those candidates are a sizeable share of all scores (Pfam-sized k = 100: 5 % of the scores go
-            // through the lists, an unseeded scan loses ~5 % to them and the sample pass would cost 3 %: not worth it;
-            // k = 1000: 17 %, CATH-sized k = 301: 50 %)
-            if (force || big || (seeded <= 0.5 * unseeded && unseeded >= 0.08 * (double)nb)) {
-                sstride = st;
-                seed_j = j;
-                seed_stat = 1;
-                svshift = 0;
-                expect_n = 1.3 * seeded + 1.25 * k; // (the bound's rank is in [j, 1.25 j]) + the sample's own rows
-            }
-        }
-        if (!seed_stat && exact_ok) { // (no estimate after all: the exact seed the rule had chosen)
-            seed = true;
-            sstride = seed_stride(nb, k, pl.chunk_rows);
-        }
-    }
-    // Tile-minimum seed (see flat_scan_kernel): where the exact seed would run a sample pass first, a launch with enough
-    // chunks seeds itself -- each chunk publishes its first tiles' best key per query, the k-th smallest published key
-    // is the bound.  Needs: the 32- or 64-query tile, plain fp32 rows, enough publications for k (<= 4096 of them).
-    // KNN_TUNE_NO_TILE_MIN_SEED: never.  (The 128-query tile of a one-query-tile launch was tried: 100 k rows x 128 queries 0.66 -> 0.38 ms
-    // where no sample pass exists, but the code in that build cost its other launches 2-14 % -- 1.25 M rows 2.80 -> 3.20 ms;
-    // such batches are searched as two 64-query pieces instead, see search_keys_impl.)
-    int pub_rounds = 0, pub_m = 1;
-    const bool pub_shape = tile_min_seed_allowed(h) && !h->approx16 && pl.qt <= 64 && pl.cap >= 2 * pl.dt && pl.tiles_base >= (pl.npairs ? dev_knob("KNN355_PUB_MIN_TILES_PAIRED", 2) : 4);
-    if (seed && pub_shape) {
-        for (int r = 2; r >= 1; r--) // (one round if it gives enough publications)
-            if ((int64_t)r * pl.nchunks <= 2048 && (int64_t)r * pl.nchunks >= 2 * (int64_t)k + 64 && r < pl.tiles_base) pub_rounds = r;
-        if (h->pub_rounds_force > 0 && (int64_t)h->pub_rounds_force * pl.nchunks <= 2048 && h->pub_rounds_force < pl.tiles_base &&
-            (int64_t)h->pub_rounds_force * pl.nchunks >= (int64_t)k + 32)
-            pub_rounds = h->pub_rounds_force;
-    }
-    if (!pub_rounds && pub_shape && !h->pub_rounds_force && nb >= 16 * (int64_t)k && k <= KNN_WAVE_SELECT_MAX_K) {
-        // A k beyond what one key per workgroup supports (512 workgroups, two rounds: k <= 480): every WAVE publishes the
-        // best key of its own rows of the first tile -- 4 keys per workgroup and query with the 32-query tile, 2 with the
-        // 64-query one, all of different rows, no reduction across the waves.  The k-th smallest of P such keys sits near the
-        // -P ln(1 - k / P) / (P x rows per wave) quantile (k = 1000, P = 2048: 1372 of 131 k sampled rows; 2 M rows x 32
-        // queries: 2.30 ms unseeded -- every workgroup warming up its own 1000 best -- against 1.45 at k = 100).
-        const int wm = (pl.qt == 32 || pl.qt == 48) ? 4 : 2;
-        for (int r = 2; r >= 1; r--) { // (one round if it gives enough publications; 4096 keys are selected by probing them in memory)
-            const int64_t P = (int64_t)r * wm * pl.nchunks;
-            if (P <= 4096 && P >= (int64_t)k + k / 4 + 32 && r < pl.tiles_base) {
-                pub_rounds = r;
-                pub_m = wm;
-            }
-        }
-    }
-    if (pass.mode == 2 && !pub_rounds) sstride = 0; // (a gated fallback runs no sample pass: its memsets could not be gated)
-    if (pub_rounds) {
-        sstride = 0;
-        // the bound sits near the k / (publications x tile rows) quantile; the first tile(s) of every chunk are filtered
-        // again at the end of the chunk
-        expect_n = 2.0 * (double)k * (double)nb / ((double)pub_rounds * pl.nchunks * pl.dt) + 2.0 * k + 64;
-        if (pub_m > 1) {
-            const double P = (double)pub_rounds * pub_m * pl.nchunks;
-            expect_n = 1.3 * (-P * log(1.0 - (double)k / P)) * (double)nb / ((double)pub_rounds * pl.nchunks * pl.dt) + 2.0 * k + 64;
-        }
-    }
-    if (!sstride && !pub_rounds) make_plan(h, nb, nq, k, level > 0, pl, allow_pairs && level == 0, allow_big); // a seed sample is small: parallelism over warm-up
-    // Most keys a chunk hands on per query.  Chunks of a single tile (a seed sample, a tiny database)
-    // hand on ALL their candidates: cutting 32 lists of one tile down to 1.25 k at the end of the only
-    // tile is serial work per workgroup that the final selection does anyway, one workgroup per query.
-    int kslot = knn_kslot(k);
-    if (pl.chunk_rows == pl.dt && pl.dt > kslot && pl.dt <= pl.cap - pl.dt && k <= KNN_WAVE_SELECT_MAX_K) kslot = pl.dt;
-    const int qcap = pl.nchunks * kslot + (sstride ? k + std::max(k >> 2, 32) : 0); // (a seed sample hands on up to kmax keys)
+    const SearchPlan plan = plan_search(c, nb, nq, k, level, row_mul, allow_stat, pass.mode);
+    const ScanPlan &pl = plan.pl;
+    const int sstride = plan.sstride, svshift = plan.svshift < 0 ? vshift : plan.svshift, seed_stat = plan.seed_stat;
+    const int pub_rounds = plan.pub_rounds, pub_m = plan.pub_m, qcap = plan.qcap;
     LevelBufs &lb = h->ws_level[level];
     uint64_t reset_sig = 0; // != 0: this search's final selection resets the level's state for a successor of the same shape
     const size_t nslots = (size_t)pl.nqtiles * pl.qt;
@@ -4507,12 +4185,9 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         // running threshold the main pass starts from
         SearchOut so;
         so.keys = qlist; so.keys_stride = qcap; so.keys_fill = 0;
-        so.seed_cnt = qcnt; so.seed_gthr = gthr; so.seed_qthr = qthr; so.seed_j = seed_j; so.seed_stat = seed_stat;
+        so.seed_cnt = qcnt; so.seed_gthr = gthr; so.seed_qthr = qthr; so.seed_j = plan.seed_j; so.seed_stat = seed_stat;
         so.seed_nslots = (int64_t)nslots;
-        // a statistical seed needs the sample's best ~1.25 j rows only (its bound has rank <= 1.25 j, and only rows that
-        // beat the bound are handed on): the sample is searched with that k, not the caller's
-        const int k_sample = seed_stat ? std::min(k, seed_j + std::max(seed_j >> 2, 8) + 8) : k;
-        rc = search_view(h, q_dev, xn, nq, k_sample, id_base, row_mul * sstride, svshift, level + 1, so, false, s, reset_flag, pass);
+        rc = search_view(h, q_dev, xn, nq, plan.k_sample, id_base, row_mul * sstride, svshift, level + 1, so, false, s, reset_flag, pass);
         if (rc) return rc;
     } else {
         const int64_t nn = std::max<int64_t>((int64_t)nslots, nq);
@@ -4572,8 +4247,8 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     p.row_mul = row_mul;
     p.vshift = sstride ? svshift : vshift;
     p.skip_mask = sstride ? sstride - 1 : -1;
-    p.kslot = kslot;
-    p.sparse_epi = !(sstride && !seed_stat) && !pub_rounds; // (not exactly seeded: a statistical estimate, or no seed at all)
+    p.kslot = plan.kslot;
+    p.sparse_epi = plan.sparse_epi;
     p.pub = pub_rounds ? (uint64_t *)lb.pub.p : nullptr;
     p.arrive = pub_rounds ? (uint32_t *)lb.arrive.p : nullptr;
     p.pub_rounds = pub_rounds;
@@ -4582,15 +4257,14 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     p.pair_ctr = pl.npairs ? (uint32_t *)lb.pair_ctr.p : nullptr;
     p.npairs = pl.npairs;
     if (pl.diff) {
-        // (the build launch_scan_cfg picks: up to 4, 12 or 20 queries)
-        const int dnq = diff_build_width(nq);
+        const int dnq = diff_build_width(nq); // (the build pick_scan_kernel picks)
         if (h->ws_qdiff.ensure((size_t)dnq * h->dp * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         const int64_t tot = (int64_t)dnq * h->dp;
         hipLaunchKernelGGL(diff_interleave_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, q_dev, nq, h->dp, dnq, (float *)h->ws_qdiff.p);
         HIP_TRY(hipGetLastError());
         p.xq_diff = (const float *)h->ws_qdiff.p;
     }
-    if (pl.nqtiles > 1 && !h->approx16 && pl.tiles_base >= 2 && pl.qt != 256 && !(h->flags & KNN_TUNE_NO_TURNS)) { // (turn taking: batch launches with real chunks, two workgroups per CU)
+    if (plan.cu_turn) {
         if (h->ws_turn.ensure(2048 * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         if (h->turn_zeroed != h->ws_turn.p) { // (once per allocation: a fill in front of every launch was 10 us of idle GPU per CATH-sized search)
             HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
@@ -4598,12 +4272,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         }
         p.cu_turn = (uint32_t *)h->ws_turn.p;
     }
-    // the pool: about a tenth of every pair's tiles (none with KNN_TUNE_NO_POOL)
-    p.pool_tiles = pl.npairs && !(h->flags & KNN_TUNE_NO_POOL) ? std::min(std::max(1, (pl.tiles_base + 5) / 10), pl.tiles_base / 4) : 0;
-#ifdef KNN355_DEV
-    if (p.pool_tiles && getenv("KNN355_POOL_PCT")) // (developer build: the pool's share of every pair's range, in percent)
-        p.pool_tiles = std::min(std::max(1, pl.tiles_base * atoi(getenv("KNN355_POOL_PCT")) / 100), pl.tiles_base - 2);
-#endif
+    p.pool_tiles = plan.pool_tiles;
     if (pub_rounds) {
         if (h->ws_defer.ensure((size_t)pl.grid * pl.qt * pl.dt * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
         p.defer = (float *)h->ws_defer.p;
@@ -4629,30 +4298,22 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         h->nlaunches++;
         HIP_TRY(hipEventRecord(h->ev0, s));
     }
-    if (pl.qt == 256) rc = launch_scan_big(h, pass, p, pl, s);
-    else if (pl.qt == 128) rc = launch_scan_cfg<2, 2, 2, 2>(h, pass, p, pl, s);
-    else if (pl.qt == 96) rc = launch_scan16<2, 2, 2, 3>(h, pass, p, pl, s);
-    else if (pl.qt == 48) rc = launch_scan16<4, 1, 2, 3>(h, pass, p, pl, s);
-    else if (pl.qt == 64) rc = launch_scan_cfg<2, 2, 2, 1>(h, pass, p, pl, s);
-    else rc = launch_scan_cfg<4, 1, 2, 1>(h, pass, p, pl, s);
+    const ScanKernel kern = pick_scan_kernel(pl.qt, h->metric == KNN_METRIC_L2, h->approx16, pl.nqtiles == 1, pl.diff ? diff_build_width(nq) : 0, pass.mode);
+    if (!kern) return KNN_ERR_INVALID;
+    rc = scan_lds_opt_in(kern, pl.lds);
+    if (!rc) rc = launch_scan(kern, p, pl.grid, pl.lds, s);
     if (rc) return rc;
     if (top) {
         HIP_TRY(hipEventRecord(h->ev1, s));
         h->last_kernel = pass.mode == 1 ? std::string(pl.name) + "_f16x" : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
         h->last_seed_stride = pub_rounds ? -pub_rounds * pub_m : sstride; // (negative: tile-minimum seed, keys per workgroup and query)
-        h->last_seed_stat = seed_stat ? seed_j : 0;
+        h->last_seed_stat = seed_stat ? plan.seed_j : 0;
         h->last_sample_rows = sstride ? view_rows(nb, sstride, p.vshift) : 0;
     }
     // final selection: every query's candidates (seed list + the chunks' survivors) -> sorted top-k
     SelectParams sp = {};
     sp.in = qlist; sp.in_stride = qcap; sp.cnt = qcnt; sp.cap = qcap;
-    if (expect_n <= 0 && sstride && !seed_stat) {
-        // exact seed: the sample's k-th score admits about k rows per sample-sized slice of the rest of the view
-        const double S = (double)view_rows(nb, sstride, p.vshift);
-        expect_n = 1.5 * (double)k * (double)nb / std::max(1.0, S) + 1.25 * k;
-    }
-    if (expect_n <= 0) expect_n = (double)qcap;
-    sp.n_expect = (int)std::min<double>(std::min<double>((double)qcap, expect_n), (double)nb); // (never more than the view has rows)
+    sp.n_expect = select_expect_n(plan, nb, k, sstride ? view_rows(nb, sstride, p.vshift) : 0);
     sp.nq = nq; sp.k = k; sp.metric = h->metric;
     sp.out_keys = out.keys; sp.out_stride = out.keys ? out.keys_stride : 0; sp.out_fill = out.keys_fill;
     sp.D = out.D; sp.I = out.I;
@@ -4709,65 +4370,7 @@ static int search_keys_impl(knn_index_s *h, const float *q_dev, int64_t nq, int 
         HIP_TRY(hipGetLastError());
         q_dev = (const float *)h->ws_q16.p;
     }
-    // Many queries: blocks of 16384 (128 query tiles), one launch each.  A launch keeps two workgroups per CU in flight;
-    // with 128 query tiles those share 4 chunks of rows and their 64 MB of query tiles stay in the Infinity Cache, with
-    // 1563 query tiles (200 k queries at once) 512 different query tiles are streamed beside ONE chunk and the last of
-    // 3.05 rounds of workgroups runs almost alone (200 k x 200 k x 1024: 0.79 -> 0.83 of the fp32 MFMA peak).  The
-    // verification flag of a statistically seeded search is cleared by the first block only: it accumulates.
-    const int64_t QB = 16384;
-    const int64_t nblocks = nq > QB + QB / 2 ? (nq + QB - 1) / QB : 1;
-    // The remainder behind the full 128-query tiles.  A query tile costs its whole width whatever it holds: on a database
-    // that is streamed from HBM 129 queries took two passes of the 128-query build (10 M rows: 39.2 ms; 128 queries: 20.9).
-    // The remainder is searched on its own with the narrowest build that holds it -- <= 32 queries: the streaming build
-    // (7.1 ms per 10 M rows), <= 64: the 64-query build (11.6), a batch of 65..96: both (18.4-18.9 ms against 20.2-20.5 for
-    // one 128-query pass).  Queries are independent, so the pieces return what one launch would.  Small databases keep one launch (the
-    // pieces' own seeds and selections cost more than a padded tile saves).
-    struct Piece {
-        int64_t q0, m;
-    };
-    std::vector<Piece> pieces;
-    const bool split = h->ntotal >= (1 << 18) && !h->force_qt && !(h->flags & KNN_TUNE_NO_REMAINDER_SPLIT);
-    // A database of 32 k .. 262 k rows has no sample pass to seed a 128-query launch with, and the 64-query build seeds
-    // itself: a batch of 65..128 queries goes as two 64-query pieces (100 k rows x 100 queries: 0.56 -> 0.41 ms) -- unless the
-    // statistical seed can serve the one launch (synchronous callers) and k is large: from k ~ 200 on the one seeded
-    // 128-query launch is ahead (100 k rows x 128 queries, k = 1000: 0.53 ms against 0.85 in pieces; k = 100: 0.49 against 0.44).
-    const bool split_small = !split && h->ntotal >= (1 << 15) && nq > 64 && nq <= 128 && !h->force_qt && !h->force_chunks && !h->approx16 &&
-                             tile_min_seed_allowed(h) && !(h->flags & KNN_TUNE_NO_REMAINDER_SPLIT) &&
-                             (k <= 200 || !allow_stat || (h->flags & KNN_TUNE_NO_STAT_SEED));
-    for (int64_t b = 0; b < nblocks; b++) {
-        int64_t q0 = b * QB, m = nblocks == 1 ? nq : std::min(QB, nq - q0);
-        if (split_small) {
-            pieces.push_back({q0, 64});
-            pieces.push_back({q0 + 64, m - 64});
-            continue;
-        }
-        int64_t full = m / 128 * 128;
-        const int64_t r = m - full;
-        // A batch the 256 x 256 tile serves (big_tile_pays; synchronous callers: it needs the statistical seed) whose full tiles
-        // end in half a 256-query tile: that half goes with the remainder, on the 128 x 128 tile -- 10 M rows x 640 queries:
-        // 512 on the wide tile + 128 on the narrow one, not three wide query tiles of which one is half empty.
-        const bool may_big = (allow_stat && stat_seed_allowed(h)) || (h->flags & KNN_TUNE_BIG_TILE);
-        if (split && may_big && !h->force_chunks && full % 256 == 128 && full >= 384 && big_tile_pays(h, h->ntotal, full - 128)) {
-            pieces.push_back({q0, full - 128});
-            q0 += full - 128;
-            m -= full - 128;
-            full = 128;
-        }
-        // (round 4: 33..48 and 65..96 queries have builds of their own width -- 16-query blocks, make_plan -- so a remainder of
-        // up to 96 queries is one piece: 10 M rows x 80 queries: 18.7 ms as 64 + 16, ~16 as one 96-query pass)
-        const bool q96 = !h->approx16 && !(h->flags & KNN_TUNE_NO_Q16);
-        if (!split || m <= 64 || r == 0 || r > 96 || (r > 64 && full && !q96) || (!full && q96)) { // (without the 96-query build: 65..96 behind full tiles cost two narrow passes what the padded tile does)
-            pieces.push_back({q0, m});
-            continue;
-        }
-        if (full) pieces.push_back({q0, full});
-        if (r > 64 && !q96) {
-            pieces.push_back({q0 + full, 64});
-            pieces.push_back({q0 + full + 64, r - 64});
-        } else {
-            pieces.push_back({q0 + full, r});
-        }
-    }
+    const std::vector<Piece> pieces = plan_pieces(plan_ctx(h), nq, k, allow_stat);
     for (size_t b = 0; b < pieces.size(); b++) {
         const int64_t q0 = pieces[b].q0, m = pieces[b].m;
         SearchOut out;
@@ -4925,35 +4528,6 @@ extern "C" int knn_merge_keys_dev(knn_handle h, const uint64_t *keys_dev, int32_
 // and k <= 1536.  Returns 1 when it ran (D_dev / I_dev hold all n x k results, the verification flag is still to be
 // read by the caller), 0 when the plain path should be used, < 0 on error.
 // will self_search_symmetric take this search?  (asked BEFORE the caller sets aside device memory for the whole n x k result)
-// The statistical sample of a symmetric self-search: every 64th row from 131 072 rows on (Pfam-sized k = 100 / 1000 340.0 / 356.8 ms
-// against 348.7 / 366.2 with every 32nd -- the sample pass is 6 % of that search --, 100 k rows 89.2 against 90.8, 60 k rows and
-// fewer: within 1 % either way; CATH-sized: 3.06 against 2.87 ms; until late in round 5 the step to 64 came at 2^20 rows).  ONE
-// function: the rank j and the sample it is taken from must belong together (a rank worked out for a sparser sample is too tight
-// a bound on a denser one: every verification fails and the plain path repeats the search).
-static int sym_stat_stride(int64_t n)
-{
-    int st = n >= (1 << 17) ? 64 : 32;
-#ifdef KNN355_DEV
-    if (getenv("KNN355_STAT_STRIDE")) st = atoi(getenv("KNN355_STAT_STRIDE"));
-#endif
-    return st;
-}
-
-static bool self_search_symmetric_eligible(const knn_index_s *h, int k, int *j_out = nullptr, int *qcap_out = nullptr)
-{
-    const int64_t n = h->ntotal;
-    if (n < dev_knob("KNN355_SYM_MIN_N", 3000) || k > KNN_REGISTER_SELECT_MAX_K || k >= n || !stat_seed_allowed(h) || (h->flags & KNN_TUNE_NO_SYM) || h->force_qt || h->force_chunks || h->approx16) return false;
-    const int st = sym_stat_stride(n);
-    const int64_t S = view_rows(n, st, 0);
-    const int j = stat_seed_rank(S, n, k);
-    if (j <= 0) return false;
-    const double expect = 1.3 * (double)j * (double)n / (double)S + 1.25 * k;
-    const int qcap = (int)std::min<double>(((int64_t)(2.0 * expect) + 1024 + 63) / 64 * 64, 1 << 20);
-    if ((double)n * qcap * 8.0 > 24.0 * (1u << 30)) return false;
-    if (j_out) *j_out = j;
-    if (qcap_out) *qcap_out = qcap;
-    return true;
-}
 
 // D_host / I_host / d2h given and the result large: the query tiles are served in SYM_GROUPS launches of consecutive tiles, each
 // followed by the final selection of ITS rows -- a row's candidates are complete once every query tile up to its own has been
@@ -4966,7 +4540,8 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
 {
     const int64_t n = h->ntotal;
     int j = 0, qcap = 0;
-    if (!self_search_symmetric_eligible(h, k, &j, &qcap)) return 0;
+    const PlanCtx c = plan_ctx(h);
+    if (!self_search_symmetric_eligible(c, k, &j, &qcap)) return 0;
     const int st = sym_stat_stride(n);
     const int64_t S = view_rows(n, st, 0);
     const double expect = 1.3 * (double)j * (double)n / (double)S + 1.25 * k;
@@ -4974,7 +4549,9 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
     // (tile shape, list capacity, LDS.  256-row tiles only on demand, KNN_TUNE_BIG_TILE: the symmetric launch filters every tile
     // twice and executes half the flops per row pair, its epilogue weighs twice as much beside the K loop -- Pfam-sized
     // k = 100 / 1000: 372.7 / 392.6 ms on 256-row tiles against 349.7 / 377.4 on 128-row tiles, one box)
-    make_plan(h, n, n, k, true, pl, false, (h->flags & KNN_TUNE_BIG_TILE) != 0);
+    PlanOpts po;
+    po.seeded = true; po.allow_big = (h->flags & KNN_TUNE_BIG_TILE) != 0;
+    make_plan(c, n, n, k, po, pl);
     if (pl.qt != pl.dt || (pl.qt != 128 && pl.qt != 256)) return 0;
     const int TS = pl.qt; // square tiles of 128 rows (two workgroups per CU) or 256 rows (one: flat_scan_kernel<2, 2, 4, 4>, large indexes)
     const int T = (int)((n + TS - 1) / TS);
@@ -5064,11 +4641,12 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
         p.cu_turn = (uint32_t *)h->ws_turn.p;
     }
     // + thresholds, per-half counts and bases of the tile's rows (+ 8 KB of slots for the 128-row tile's sparse epilogue, see lds_main in the kernel)
-    const size_t lds = pl.lds + (size_t)(2 + 2) * pl.dt * 4 + (TS == 128 ? (size_t)73728 - std::max((size_t)2 * (pl.dt + pl.qt) * 128, (size_t)pl.cap * 8) : 0)
+    const size_t lds = scan_lds_bytes(pl.qt, pl.dt, pl.cap, TS == 128 ? 73728 : 0) + (size_t)(2 + 2) * pl.dt * 4
                        + (size_t)dev_knob("KNN355_LDS_PAD", 0); // (developer build: more LDS than a second workgroup leaves room for = one workgroup per CU)
     void (*kern)(ScanParams) = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 2, 2, true, false, true> : flat_scan_kernel<2, 2, 2, 2, false, false, true>;
     if (TS == 256) kern = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 4, 4, true, false, true> : flat_scan_kernel<2, 2, 4, 4, false, false, true>;
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    rc = scan_lds_opt_in(kern, lds);
+    if (rc) return rc;
     {
         const int slot = (int)(h->nlaunches % knn_index_s::RING);
         if (!h->ring0[slot]) {
@@ -5098,8 +4676,8 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
         for (size_t i0 = g0; i0 < g1; i0 += (size_t)max_wgs) {
             const size_t cnt = std::min<size_t>((size_t)max_wgs, g1 - i0);
             p.sym_items = (const SymItem *)h->ws_sym.p + i0;
-            hipLaunchKernelGGL(kern, dim3((unsigned)cnt), dim3(256), lds, s, p);
-            HIP_TRY(hipGetLastError());
+            rc = launch_scan(kern, p, (int)cnt, lds, s);
+            if (rc) return rc;
         }
         if (g == groups - 1) HIP_TRY(hipEventRecord(h->ev1, s));
         const int64_t r0 = std::min<int64_t>(n, (int64_t)T * g / groups * TS), r1 = std::min<int64_t>(n, (int64_t)T * (g + 1) / groups * TS);
@@ -5389,7 +4967,7 @@ extern "C" int knn_flat_search_self(knn_handle h, int64_t row0, int64_t nrows, i
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     if (row0 < 0 || nrows < 0 || row0 + nrows > h->ntotal) return set_err(KNN_ERR_INVALID, "search_self: row range out of bounds");
-    if (row0 == 0 && nrows == h->ntotal && (size_t)nrows * k * 12 <= ((size_t)16 << 30) && self_search_symmetric_eligible(h, (int)k)) {
+    if (row0 == 0 && nrows == h->ntotal && (size_t)nrows * k * 12 <= ((size_t)16 << 30) && self_search_symmetric_eligible(plan_ctx(h), (int)k)) {
         // every row against every row: half the score tiles suffice (self_search_symmetric)
         HIP_TRY(hipSetDevice(h->device));
         if (h->ws_D.ensure((size_t)nrows * k * 4) || h->ws_I.ensure((size_t)nrows * k * 8)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
