@@ -733,12 +733,6 @@ __device__ __attribute__((noinline)) void published_bound(const uint64_t *pub, i
 // ---------------------------------------------------------------------------
 // scan kernel
 // ---------------------------------------------------------------------------
-// Symmetric all-vs-all (the queries ARE the database rows): workgroup w multiplies query tile qtile with the
-// database tiles [jt0, jt0 + jcount), all of them on or above the diagonal; see flat_scan_kernel<..., SYM>.
-struct SymItem {
-    int qtile, jt0, jcount;
-};
-
 struct ScanParams {
     const float *xb;   // [nb][dp] database rows, zero padded to dp
     const float *yn;   // [nb] squared norms (L2 only)
@@ -761,7 +755,7 @@ struct ScanParams {
     int vshift;        // log2 of the view's block size (3: blocks of 8 rows, 0: single rows)
     int skip_mask;     // >= 0: rows whose block b has (b & skip_mask) == 0 belong to the seed sample, skip them
     int kslot;         // most keys a chunk hands on per query: k + k/4
-    const struct SymItem *sym_items; // symmetric all-vs-all launch: the work of each workgroup (see flat_scan_kernel)
+    const struct SymItem *sym_items; // symmetric all-vs-all launch: the work of each workgroup (plan.h; see flat_scan_kernel)
     int *fail;         // symmetric launch: set when a candidate array overflows
     // tile-minimum seed (streaming regime, see flat_scan_kernel): after each of its first pub_rounds tiles a workgroup
     // publishes every query's best key of that tile; the k-th smallest published key bounds the global k-th
@@ -4073,6 +4067,41 @@ static ScanKernel pick_scan_kernel(int qt, bool l2, bool approx16, bool one_qtil
     return scan_build<4, 1, 2, 1>(l2, approx16, one_qtile);
 }
 
+// the build of a symmetric launch (SymPlan): square tiles of ts = 128 or 256 rows
+static ScanKernel pick_sym_kernel(int ts, bool l2)
+{
+    if (ts == 128) return l2 ? flat_scan_kernel<2, 2, 2, 2, true, false, true> : flat_scan_kernel<2, 2, 2, 2, false, false, true>;
+    return l2 ? flat_scan_kernel<2, 2, 4, 4, true, false, true> : flat_scan_kernel<2, 2, 4, 4, false, false, true>;
+}
+
+// opens a timed launch on s: the next pair of the ring of timing events becomes ev0 / ev1, ev0 is recorded; the caller records
+// ev1 behind its launch(es)
+static int open_timed_launch(knn_index_s *h, hipStream_t s)
+{
+    const int slot = (int)(h->nlaunches % knn_index_s::RING);
+    if (!h->ring0[slot]) {
+        HIP_TRY(hipEventCreate(&h->ring0[slot]));
+        HIP_TRY(hipEventCreate(&h->ring1[slot]));
+    }
+    h->ev0 = h->ring0[slot];
+    h->ev1 = h->ring1[slot];
+    h->nlaunches++;
+    HIP_TRY(hipEventRecord(h->ev0, s));
+    return 0;
+}
+
+// the words the two workgroups of a CU take turns with (ScanParams::cu_turn), all zero
+static int zeroed_turn_words(knn_index_s *h, hipStream_t s, uint32_t **words)
+{
+    if (h->ws_turn.ensure(2048 * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
+    if (h->turn_zeroed != h->ws_turn.p) { // (once per allocation: a fill in front of every launch was 10 us of idle GPU per CATH-sized search)
+        HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
+        h->turn_zeroed = h->ws_turn.p;
+    }
+    *words = (uint32_t *)h->ws_turn.p;
+    return 0;
+}
+
 // where the result of a (view) search goes
 struct SearchOut {
     uint64_t *keys = nullptr; // sorted keys, k per query
@@ -4264,14 +4293,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         HIP_TRY(hipGetLastError());
         p.xq_diff = (const float *)h->ws_qdiff.p;
     }
-    if (plan.cu_turn) {
-        if (h->ws_turn.ensure(2048 * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        if (h->turn_zeroed != h->ws_turn.p) { // (once per allocation: a fill in front of every launch was 10 us of idle GPU per CATH-sized search)
-            HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
-            h->turn_zeroed = h->ws_turn.p;
-        }
-        p.cu_turn = (uint32_t *)h->ws_turn.p;
-    }
+    if (plan.cu_turn && (rc = zeroed_turn_words(h, s, &p.cu_turn))) return rc;
     p.pool_tiles = plan.pool_tiles;
     if (pub_rounds) {
         if (h->ws_defer.ensure((size_t)pl.grid * pl.qt * pl.dt * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
@@ -4287,17 +4309,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         g_trace_grid = pl.grid;
     }
 #endif
-    if (top) {
-        const int slot = (int)(h->nlaunches % knn_index_s::RING);
-        if (!h->ring0[slot]) {
-            HIP_TRY(hipEventCreate(&h->ring0[slot]));
-            HIP_TRY(hipEventCreate(&h->ring1[slot]));
-        }
-        h->ev0 = h->ring0[slot];
-        h->ev1 = h->ring1[slot];
-        h->nlaunches++;
-        HIP_TRY(hipEventRecord(h->ev0, s));
-    }
+    if (top && (rc = open_timed_launch(h, s))) return rc;
     const ScanKernel kern = pick_scan_kernel(pl.qt, h->metric == KNN_METRIC_L2, h->approx16, pl.nqtiles == 1, pl.diff ? diff_build_width(nq) : 0, pass.mode);
     if (!kern) return KNN_ERR_INVALID;
     rc = scan_lds_opt_in(kern, pl.lds);
@@ -4334,7 +4346,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
 }
 
 // queries [nq][dp] already on device (padded); writes sorted keys [nq][k] and/or D/I.
-// allow_stat: the caller reads the fail flag once the stream has drained (search_failed) and repeats
+// allow_stat: the caller reads the fail flag once the stream has drained (wait_search) and repeats
 // the search with allow_stat = false if it is set.
 // The batch a caller handed over, for as long as the search works through it in pieces (the outermost scope wins).
 struct BatchScope {
@@ -4437,10 +4449,11 @@ static int search_dev_impl(knn_index_s *h, const float *q_dev, int64_t nq, int k
     return search_keys_impl(h, qp, nq, k, id_base, keys_dev, D_dev, I_dev, allow_stat, s);
 }
 
-// after the stream has drained: did a statistically seeded search fail its verification?
-static int search_failed(knn_index_s *h, bool *failed)
+// waits for the search on s; then: did a statistically seeded search fail its verification?
+static int wait_search(knn_index_s *h, hipStream_t s, bool *failed)
 {
     *failed = false;
+    HIP_TRY(hipStreamSynchronize(s));
     if (!h->ws_flag.p || h->ntotal == 0) return 0;
     int flag = 0;
     HIP_TRY(hipMemcpy(&flag, h->ws_flag.p, 4, hipMemcpyDeviceToHost));
@@ -4472,9 +4485,8 @@ extern "C" int knn_flat_search_dev(knn_handle h, const float *q_dev, int64_t nq,
     rc = search_dev_impl(h, q_dev, nq, (int)k, D_dev, I_dev, nullptr, 0, sync, s);
     if (rc) return rc;
     if (sync) {
-        HIP_TRY(hipStreamSynchronize(s));
         bool failed = false;
-        rc = search_failed(h, &failed);
+        rc = wait_search(h, s, &failed);
         if (rc) return rc;
         if (failed) {
             rc = search_dev_impl(h, q_dev, nq, (int)k, D_dev, I_dev, nullptr, 0, false, s);
@@ -4527,35 +4539,22 @@ extern "C" int knn_merge_keys_dev(knn_handle h, const uint64_t *keys_dev, int32_
 // seed (the rows of a database tile have no candidate list of their own in that kernel, only their compact arrays)
 // and k <= 1536.  Returns 1 when it ran (D_dev / I_dev hold all n x k results, the verification flag is still to be
 // read by the caller), 0 when the plain path should be used, < 0 on error.
-// will self_search_symmetric take this search?  (asked BEFORE the caller sets aside device memory for the whole n x k result)
-
-// D_host / I_host / d2h given and the result large: the query tiles are served in SYM_GROUPS launches of consecutive tiles, each
+//
+// D_host / I_host / d2h given and the result large: the query tiles are served in sp.groups launches of consecutive tiles, each
 // followed by the final selection of ITS rows -- a row's candidates are complete once every query tile up to its own has been
 // served (tile (I, J), J >= I, scores rows I against J and J against I) -- and by their download on the copy stream d2h, which
 // then overlaps the launches of the later groups (Pfam-sized k = 1000: 2.4 GB of results, 0.15 s behind a 0.38 s search;
 // CATH-sized k = 301: 52 MB, 1.3 ms on the wire behind a 2.5 ms search, in four groups).
 // Returns 2 then (the caller waits for d2h and checks the verification flag), 1 when the results are in D_dev / I_dev only.
+// Every decision is plan_self_symmetric's and sym_work_table's (plan.h).
 static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I_dev, hipStream_t s, float *D_host = nullptr,
                                  int64_t *I_host = nullptr, hipStream_t d2h = nullptr)
 {
     const int64_t n = h->ntotal;
-    int j = 0, qcap = 0;
-    const PlanCtx c = plan_ctx(h);
-    if (!self_search_symmetric_eligible(c, k, &j, &qcap)) return 0;
-    const int st = sym_stat_stride(n);
-    const int64_t S = view_rows(n, st, 0);
-    const double expect = 1.3 * (double)j * (double)n / (double)S + 1.25 * k;
-    ScanPlan pl;
-    // (tile shape, list capacity, LDS.  256-row tiles only on demand, KNN_TUNE_BIG_TILE: the symmetric launch filters every tile
-    // twice and executes half the flops per row pair, its epilogue weighs twice as much beside the K loop -- Pfam-sized
-    // k = 100 / 1000: 372.7 / 392.6 ms on 256-row tiles against 349.7 / 377.4 on 128-row tiles, one box)
-    PlanOpts po;
-    po.seeded = true; po.allow_big = (h->flags & KNN_TUNE_BIG_TILE) != 0;
-    make_plan(c, n, n, k, po, pl);
-    if (pl.qt != pl.dt || (pl.qt != 128 && pl.qt != 256)) return 0;
-    const int TS = pl.qt; // square tiles of 128 rows (two workgroups per CU) or 256 rows (one: flat_scan_kernel<2, 2, 4, 4>, large indexes)
-    const int T = (int)((n + TS - 1) / TS);
-    const size_t nslots = (size_t)T * TS;
+    SymPlan sp;
+    if (!plan_self_symmetric(plan_ctx(h), k, D_host && I_host && d2h, sp)) return 0;
+    const int qcap = sp.qcap, groups = sp.groups;
+    const size_t nslots = (size_t)sp.tiles * sp.ts;
     LevelBufs &lb = h->ws_level[0];
     lb.clean_sig = 0; // (this search leaves the level's state in its own shape)
     if (lb.qlist.ensure((size_t)n * qcap * 8) || lb.qcnt.ensure((size_t)n * 4) || lb.gthr.ensure(nslots * 4) || lb.qthr.ensure((size_t)n * 4) ||
@@ -4564,146 +4563,89 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
     uint64_t *qlist = (uint64_t *)lb.qlist.p;
     uint32_t *qcnt = (uint32_t *)lb.qcnt.p, *gthr = (uint32_t *)lb.gthr.p, *qthr = (uint32_t *)lb.qthr.p;
     const float *xn = h->metric == KNN_METRIC_L2 ? h->yn : nullptr; // the queries are the rows: their norms are the row norms
-    // 0. work table: workgroup = (query tile I, a run of database tiles J >= I).  The run length that minimises
-    //    rounds x (tiles + half a tile of fixed work), two workgroups per CU.  The table depends on (tiles, CUs) only: it
-    //    stays on the device between searches (uploading it between the sample pass and the main launch cost a host
-    //    round trip -- 35 us of idle GPU -- per search).
-    const int64_t slots = (TS == 256 ? 1 : 2) * (int64_t)std::max(1, h->num_cus);
-    constexpr int SYM_GROUPS = 8;
-    // (eight groups for gigabytes of result; four from 32 MB on -- CATH-sized, 113 query tiles, 52 MB: cath.search end to end
-    // 5.03 -> 4.43 ms with four, 4.62 with five, 4.94 with eight: every group is a launch with its own tail and selection)
-    const int want_groups = std::min(SYM_GROUPS, std::max(2, dev_knob("KNN355_SELF_GROUPS", (size_t)n * k * 12 >= ((size_t)256 << 20) && T >= 16 * SYM_GROUPS ? SYM_GROUPS : 4)));
-    const bool stream_out = D_host && I_host && d2h && (size_t)n * k * 12 >= ((size_t)dev_knob("KNN355_SELF_STREAM_MIN_MB", 32) << 20) && T >= 16 * want_groups;
-    const int groups = stream_out ? want_groups : 1;
-    if (h->sym_tiles != T || h->sym_ts != TS || h->sym_groups != groups || !h->ws_sym.p) {
-        // (the run length of each group by itself: a group is a launch, and a short one -- the later groups of a CATH-sized
-        // index -- fills the slots only with short runs)
-        std::vector<SymItem> items;
-        h->sym_gstart.assign(1, 0);
-        int first_tp = 16;
-        for (int g = 0; g < groups; g++) { // (query tiles [T g / groups, T (g + 1) / groups): equal shares of the RESULT; the first group is the longest)
-            const int I0 = (int)((int64_t)T * g / groups), I1 = (int)((int64_t)T * (g + 1) / groups);
-            int best_tp = 16;
-            int64_t best_cost = INT64_MAX;
-            for (int tp = dev_knob("KNN355_SYM_MIN_TP", 1); tp <= 96; tp++) {
-                int64_t wgs = 0;
-                for (int I = I0; I < I1; I++) wgs += (T - I + tp - 1) / tp;
-                const int64_t rounds = (wgs + slots - 1) / slots;
-                const int64_t cost = rounds * (2 * tp + 1);
-                if (cost < best_cost || (cost == best_cost && tp > best_tp)) { best_cost = cost; best_tp = tp; }
-            }
-            if (g == 0) first_tp = best_tp;
-            const size_t at = items.size();
-            for (int I = I0; I < I1; I++)
-                for (int j0 = I; j0 < T; j0 += best_tp) items.push_back({I, j0, std::min(best_tp, T - j0)});
-            // long runs first: the short tails of every query tile fill the last round
-            std::stable_sort(items.begin() + at, items.end(), [](const SymItem &a, const SymItem &b) { return a.jcount > b.jcount; });
-            h->sym_gstart.push_back((int64_t)items.size());
-        }
-        const int best_tp = first_tp;
+    // 0. the work table.  It depends on (tiles, groups, CUs) only: it stays on the device between searches (uploading it between
+    //    the sample pass and the main launch cost a host round trip -- 35 us of idle GPU -- per search).
+    if (h->sym_tiles != sp.tiles || h->sym_ts != sp.ts || h->sym_groups != groups || !h->ws_sym.p) {
+        const SymTable t = sym_work_table(sp.tiles, groups, sp.slots);
         h->sym_tiles = -1;
-        if (h->ws_sym.ensure(items.size() * sizeof(SymItem), h->done, s)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
-        HIP_TRY(hipMemcpyAsync(h->ws_sym.p, items.data(), items.size() * sizeof(SymItem), hipMemcpyHostToDevice, s));
+        if (h->ws_sym.ensure(t.items.size() * sizeof(SymItem), h->done, s)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
+        HIP_TRY(hipMemcpyAsync(h->ws_sym.p, t.items.data(), t.items.size() * sizeof(SymItem), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s)); // (the table is a local vector)
-        h->sym_tiles = T;
-        h->sym_ts = TS;
+        h->sym_tiles = sp.tiles;
+        h->sym_ts = sp.ts;
         h->sym_groups = groups;
-        h->sym_run = best_tp;
-        h->sym_items = (int64_t)items.size();
+        h->sym_run = t.first_run;
+        h->sym_items = (int64_t)t.items.size();
+        h->sym_gstart = t.gstart;
     }
-    const int best_tp = h->sym_run;
     const size_t nitems = (size_t)h->sym_items;
     // 1. the sample pass (every row is a query, the strided sample is the database): thresholds + the sample's own candidates
     SearchOut so;
     so.keys = qlist; so.keys_stride = qcap; so.keys_fill = 0;
-    so.seed_cnt = qcnt; so.seed_gthr = gthr; so.seed_qthr = qthr; so.seed_j = j; so.seed_stat = 1; so.seed_nslots = (int64_t)nslots;
-    const int k_sample = std::min(k, j + std::max(j >> 2, 8) + 8);
-    int rc = search_view(h, h->xb, xn, n, k_sample, 0, st, 0, 1, so, false, s, (int *)h->ws_flag.p);
+    so.seed_cnt = qcnt; so.seed_gthr = gthr; so.seed_qthr = qthr; so.seed_j = sp.j; so.seed_stat = 1; so.seed_nslots = (int64_t)nslots;
+    int rc = search_view(h, h->xb, xn, n, sp.k_sample, 0, sp.st, 0, 1, so, false, s, (int *)h->ws_flag.p);
     if (rc) return rc;
-    const size_t per_wg = (size_t)pl.qt * pl.cap * 8;
-    const int64_t max_wgs = std::max<int64_t>(slots, (int64_t)((2ull << 30) / per_wg));
-    if (h->ws_lists.ensure((size_t)std::min<int64_t>((int64_t)nitems, max_wgs) * per_wg)) return set_err(KNN_ERR_HIP, "search_self: out of device memory (candidate lists)");
+    if (h->ws_lists.ensure((size_t)std::min<int64_t>((int64_t)nitems, sp.max_wgs) * sp.ts * sp.pl.cap * 8)) return set_err(KNN_ERR_HIP, "search_self: out of device memory (candidate lists)");
     ScanParams p = {};
     p.xb = h->xb; p.yn = h->yn; p.xq = h->xb; p.xn = xn;
-    p.nb = n; p.nq = n; p.dp = h->dp; p.k = k; p.cap = pl.cap;
-    p.nqtiles = T; p.nchunks = 1; p.tiles_base = 0; p.tiles_rem = 0;
+    p.nb = n; p.nq = n; p.dp = h->dp; p.k = k; p.cap = sp.pl.cap;
+    p.nqtiles = sp.tiles; p.nchunks = 1; p.tiles_base = 0; p.tiles_rem = 0;
     p.lists = (uint64_t *)h->ws_lists.p; p.gthr = gthr;
     p.qlist = qlist; p.qcnt = qcnt; p.qcap = qcap;
-    p.id_base = 0; p.row_mul = 1; p.vshift = 0; p.skip_mask = st - 1;
+    p.id_base = 0; p.row_mul = 1; p.vshift = 0; p.skip_mask = sp.st - 1;
     p.kslot = knn_kslot(k);
     p.fail = (int *)h->ws_flag.p;
-    if (!(h->flags & KNN_TUNE_NO_TURNS) && TS == 128) {
-        if (h->ws_turn.ensure(2048 * 4)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
-        if (h->turn_zeroed != h->ws_turn.p) {
-            HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
-            h->turn_zeroed = h->ws_turn.p;
-        }
-        p.cu_turn = (uint32_t *)h->ws_turn.p;
-    }
-    // + thresholds, per-half counts and bases of the tile's rows (+ 8 KB of slots for the 128-row tile's sparse epilogue, see lds_main in the kernel)
-    const size_t lds = scan_lds_bytes(pl.qt, pl.dt, pl.cap, TS == 128 ? 73728 : 0) + (size_t)(2 + 2) * pl.dt * 4
-                       + (size_t)dev_knob("KNN355_LDS_PAD", 0); // (developer build: more LDS than a second workgroup leaves room for = one workgroup per CU)
-    void (*kern)(ScanParams) = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 2, 2, true, false, true> : flat_scan_kernel<2, 2, 2, 2, false, false, true>;
-    if (TS == 256) kern = h->metric == KNN_METRIC_L2 ? flat_scan_kernel<2, 2, 4, 4, true, false, true> : flat_scan_kernel<2, 2, 4, 4, false, false, true>;
-    rc = scan_lds_opt_in(kern, lds);
+    if (sp.cu_turn && (rc = zeroed_turn_words(h, s, &p.cu_turn))) return rc;
+    const ScanKernel kern = pick_sym_kernel(sp.ts, h->metric == KNN_METRIC_L2);
+    rc = scan_lds_opt_in(kern, sp.lds);
+    if (!rc) rc = open_timed_launch(h, s);
     if (rc) return rc;
-    {
-        const int slot = (int)(h->nlaunches % knn_index_s::RING);
-        if (!h->ring0[slot]) {
-            HIP_TRY(hipEventCreate(&h->ring0[slot]));
-            HIP_TRY(hipEventCreate(&h->ring1[slot]));
-        }
-        h->ev0 = h->ring0[slot];
-        h->ev1 = h->ring1[slot];
-        h->nlaunches++;
-        HIP_TRY(hipEventRecord(h->ev0, s));
-    }
 #ifdef KNN355_TRACE
     if (g_trace_buf.ensure((size_t)nitems * 128 * 8)) return set_err(KNN_ERR_HIP, "trace: out of device memory");
     HIP_TRY(hipMemsetAsync(g_trace_buf.p, 0, (size_t)nitems * 128 * 8, s));
     p.trace = (unsigned long long *)g_trace_buf.p;
     p.ablate = getenv("KNN355_ABLATE") ? atoi(getenv("KNN355_ABLATE")) : 0;
-    g_trace_grid = (int)std::min<size_t>(nitems, (size_t)max_wgs);
+    g_trace_grid = (int)std::min<size_t>(nitems, (size_t)sp.max_wgs);
 #endif
     // 2 + 3. the launches, each followed by the final selection of the rows it completes (verified against the sample's bound)
-    hipEvent_t gev[SYM_GROUPS] = {};
+    hipEvent_t gev[SYM_MAX_GROUPS] = {};
     struct GroupEvents { // (the events of this call go with it, whichever way it returns -- ADVICE r4)
         hipEvent_t *e;
-        ~GroupEvents() { for (int i = 0; i < SYM_GROUPS; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
+        ~GroupEvents() { for (int i = 0; i < SYM_MAX_GROUPS; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
     } gev_guard{gev};
     for (int g = 0; g < groups; g++) {
         const size_t g0 = (size_t)h->sym_gstart[(size_t)g], g1 = (size_t)h->sym_gstart[(size_t)g + 1];
-        for (size_t i0 = g0; i0 < g1; i0 += (size_t)max_wgs) {
-            const size_t cnt = std::min<size_t>((size_t)max_wgs, g1 - i0);
+        for (size_t i0 = g0; i0 < g1; i0 += (size_t)sp.max_wgs) {
+            const size_t cnt = std::min<size_t>((size_t)sp.max_wgs, g1 - i0);
             p.sym_items = (const SymItem *)h->ws_sym.p + i0;
-            rc = launch_scan(kern, p, (int)cnt, lds, s);
+            rc = launch_scan(kern, p, (int)cnt, sp.lds, s);
             if (rc) return rc;
         }
         if (g == groups - 1) HIP_TRY(hipEventRecord(h->ev1, s));
-        const int64_t r0 = std::min<int64_t>(n, (int64_t)T * g / groups * TS), r1 = std::min<int64_t>(n, (int64_t)T * (g + 1) / groups * TS);
-        SelectParams sp = {};
-        sp.in = qlist + (size_t)r0 * qcap; sp.in_stride = qcap; sp.cnt = qcnt + r0; sp.cap = qcap;
-        sp.n_expect = (int)std::min<double>((double)qcap, expect);
-        sp.nq = r1 - r0; sp.k = k; sp.metric = h->metric;
-        sp.D = D_dev + (size_t)r0 * k; sp.I = I_dev + (size_t)r0 * k;
-        sp.qthr = qthr + r0; sp.fail = (int *)h->ws_flag.p;
-        rc = launch_select(sp, s, &h->ws_tmp);
+        const int64_t r0 = sym_group_row0(sp, n, g), r1 = sym_group_row0(sp, n, g + 1);
+        SelectParams sel = {};
+        sel.in = qlist + (size_t)r0 * qcap; sel.in_stride = qcap; sel.cnt = qcnt + r0; sel.cap = qcap;
+        sel.n_expect = sp.n_expect;
+        sel.nq = r1 - r0; sel.k = k; sel.metric = h->metric;
+        sel.D = D_dev + (size_t)r0 * k; sel.I = I_dev + (size_t)r0 * k;
+        sel.qthr = qthr + r0; sel.fail = (int *)h->ws_flag.p;
+        rc = launch_select(sel, s, &h->ws_tmp);
         if (rc) return rc;
-        if (stream_out) {
+        if (groups > 1) {
             HIP_TRY(hipEventCreateWithFlags(&gev[g], hipEventDisableTiming));
             HIP_TRY(hipEventRecord(gev[g], s));
         }
     }
-    h->last_kernel = TS == 256 ? "flat_scan_q256_d256_sym" : "flat_scan_q128_d128_sym"; h->last_qt = TS; h->last_dt = TS; h->last_chunks = best_tp; h->last_grid = (int)nitems;
-    h->last_seed_stride = st; h->last_seed_stat = j; h->last_sample_rows = S;
+    h->last_kernel = sp.name; h->last_qt = sp.ts; h->last_dt = sp.ts; h->last_chunks = h->sym_run; h->last_grid = (int)nitems;
+    h->last_seed_stride = sp.st; h->last_seed_stat = sp.j; h->last_sample_rows = sp.S;
     if (h->done) (void)hipEventRecord(h->done, s); // (everything this search enqueued on the handle's buffers: see DevBuf::ensure)
     h->sym_searches++;
-    if (!stream_out) return 1;
+    if (groups == 1) return 1;
     // the downloads, group by group behind their selections (everything above is enqueued: a copy into pageable memory may
     // block this thread as long as it likes)
     hipError_t e = hipSuccess;
     for (int g = 0; g < groups; g++) {
-        const int64_t r0 = std::min<int64_t>(n, (int64_t)T * g / groups * TS), r1 = std::min<int64_t>(n, (int64_t)T * (g + 1) / groups * TS);
+        const int64_t r0 = sym_group_row0(sp, n, g), r1 = sym_group_row0(sp, n, g + 1);
         if (e == hipSuccess) e = hipStreamWaitEvent(d2h, gev[g], 0);
         if (e == hipSuccess && r1 > r0) e = hipMemcpyAsync(D_host + (size_t)r0 * k, D_dev + (size_t)r0 * k, (size_t)(r1 - r0) * k * 4, hipMemcpyDeviceToHost, d2h);
         if (e == hipSuccess && r1 > r0) e = hipMemcpyAsync(I_host + (size_t)r0 * k, I_dev + (size_t)r0 * k, (size_t)(r1 - r0) * k * 8, hipMemcpyDeviceToHost, d2h);
@@ -4982,36 +4924,26 @@ extern "C" int knn_flat_search_self(knn_handle h, int64_t row0, int64_t nrows, i
             rc = self_search_symmetric(h, (int)k, (float *)h->ws_D.p, (int64_t *)h->ws_I.p, h->stream, D_host, I_host, lease.cp ? lease.cp->d2h : nullptr);
         }
         if (rc < 0) return rc;
-        if (rc == 2) { // (the rows went out behind their groups' selections)
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            bool failed = false;
-            rc = search_failed(h, &failed);
+        // (0: the plan left the search to the plain path after all, which also repeats a search whose verification failed: a
+        // threshold estimate was too tight or a candidate array overflowed)
+        bool failed = true;
+        if (rc > 0) {
+            const bool downloaded = rc == 2; // (the rows went out behind their groups' selections)
+            rc = wait_search(h, h->stream, &failed);
             if (rc) return rc;
-            if ((size_t)nrows * k * 12 > ((size_t)1 << 30)) { // (gigabytes of result staging are not kept with the handle)
-                h->ws_D.release();
-                h->ws_I.release();
-            }
-            if (!failed) return 0;
-            // a threshold estimate was too tight or a candidate array overflowed: the plain path repeats the search
-        } else if (rc == 1) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            bool failed = false;
-            rc = search_failed(h, &failed);
-            if (rc) return rc;
-            if (!failed) {
+            if (!failed && !downloaded) {
                 HIP_TRY(hipMemcpyAsync(D_host, h->ws_D.p, (size_t)nrows * k * 4, hipMemcpyDeviceToHost, h->stream));
                 HIP_TRY(hipMemcpyAsync(I_host, h->ws_I.p, (size_t)nrows * k * 8, hipMemcpyDeviceToHost, h->stream));
                 HIP_TRY(hipStreamSynchronize(h->stream));
-                if ((size_t)nrows * k * 12 > ((size_t)1 << 30)) { // (gigabytes of result staging are not kept with the handle)
-                    h->ws_D.release();
-                    h->ws_I.release();
-                }
-                return 0;
             }
-            // a threshold estimate was too tight or a candidate array overflowed: the plain path repeats the search
         }
-        h->ws_D.release(); // (host_search works in batches: it takes what it needs)
-        h->ws_I.release();
+        // the results' staging stays with the handle for the next search unless it is gigabytes, or host_search follows: that
+        // works in batches and takes what it needs
+        if (failed || (size_t)nrows * k * 12 > ((size_t)1 << 30)) {
+            h->ws_D.release();
+            h->ws_I.release();
+        }
+        if (!failed) return 0;
     }
     return host_search(h, nullptr, row0, nrows, k, D_host, I_host);
 }
@@ -5030,9 +4962,8 @@ extern "C" int knn_flat_search_self_dev(knn_handle h, int64_t k, float *D_dev, i
     rc = self_search_symmetric(h, (int)k, D_dev, I_dev, s);
     if (rc < 0) return rc;
     if (rc == 1) {
-        HIP_TRY(hipStreamSynchronize(s));
         bool failed = false;
-        rc = search_failed(h, &failed);
+        rc = wait_search(h, s, &failed);
         if (rc) return rc;
         if (!failed) return 0;
     }
@@ -5043,9 +4974,8 @@ extern "C" int knn_flat_search_self_dev(knn_handle h, int64_t k, float *D_dev, i
         for (int attempt = 0; attempt < 2; attempt++) { // (statistical seed first, plain if its verification fails)
             rc = search_keys_impl(h, h->xb + (size_t)b0 * h->dp, m, (int)k, 0, nullptr, D_dev + b0 * k, I_dev + b0 * k, attempt == 0, s);
             if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(s));
             bool failed = false;
-            rc = search_failed(h, &failed);
+            rc = wait_search(h, s, &failed);
             if (rc) return rc;
             if (!failed) break;
         }

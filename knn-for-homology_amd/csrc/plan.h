@@ -1,7 +1,8 @@
-// The flat search's planner: which build of flat_scan_kernel runs, over how many chunks, with which seed, and how a batch is
-// cut into pieces.  Plain host arithmetic on (nb, nq, k, metric, flags, num_cus): no HIP header, no handle -- knn355.hip
-// copies what the rules read into a PlanCtx (plan_ctx) and launches what plan_pieces / plan_search return; plan_check.cpp
-// runs the same rules on a machine without a GPU.
+// The planners of the flat search, the symmetric self-search and the range scan: which kernel build runs, over how many chunks
+// or runs of tiles, with which seed, with how much LDS, and how a batch is cut into pieces.  Plain host arithmetic on (nb, nq,
+// k, metric, flags, num_cus): no HIP header, no handle -- knn355.hip copies what the rules read into a PlanCtx (plan_ctx) and
+// launches what plan_pieces / plan_search / plan_self_symmetric / plan_range return; plan_check.cpp runs the same rules on a
+// machine without a GPU.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -503,11 +504,36 @@ static std::vector<Piece> plan_pieces(const PlanCtx &c, int64_t nq, int k, bool 
     return pieces;
 }
 
+// ---- symmetric self-search ---------------------------------------------------
+// Symmetric all-vs-all (the queries ARE the database rows): workgroup w multiplies query tile qtile with the
+// database tiles [jt0, jt0 + jcount), all of them on or above the diagonal; see flat_scan_kernel<..., SYM>.
+struct SymItem {
+    int qtile, jt0, jcount;
+};
+
+static const int SYM_MAX_GROUPS = 8;
+
+// Everything self_search_symmetric decides before it allocates and launches.
+struct SymPlan {
+    ScanPlan pl;      // tile shape and list capacity (pl.lds and pl.name are the plain build's: see lds, name)
+    int ts, tiles;    // square tiles of ts rows (128: two workgroups per CU; 256: one, flat_scan_kernel<2, 2, 4, 4>), tiles of them
+    int st;           // the statistical sample: every st-th row ...
+    int64_t S;        // ... S rows ...
+    int j;            // ... whose j-th best score is the bound (stat_seed_rank) ...
+    int k_sample;     // ... searched with this k (the sample's best ~1.25 j rows, as plan_search does)
+    int qcap;         // capacity of a row's compact candidate array
+    int n_expect;     // candidates per row the final selections should expect
+    int64_t slots;    // workgroups resident on the device
+    int64_t max_wgs;  // workgroups per launch: their candidate lists stay below 2 GB
+    int groups;       // launches of consecutive query tiles, each followed by its rows' selection; > 1: the result streams out
+    bool cu_turn;
+    size_t lds;
+    const char *name; // the introspection's name of the kernel
+};
+
 // The statistical sample of a symmetric self-search: every 64th row from 131 072 rows on (Pfam-sized k = 100 / 1000 340.0 / 356.8 ms
 // against 348.7 / 366.2 with every 32nd -- the sample pass is 6 % of that search --, 100 k rows 89.2 against 90.8, 60 k rows and
-// fewer: within 1 % either way; CATH-sized: 3.06 against 2.87 ms; until late in round 5 the step to 64 came at 2^20 rows).  ONE
-// function: the rank j and the sample it is taken from must belong together (a rank worked out for a sparser sample is too tight
-// a bound on a denser one: every verification fails and the plain path repeats the search).
+// fewer: within 1 % either way; CATH-sized: 3.06 against 2.87 ms; until late in round 5 the step to 64 came at 2^20 rows).
 static int sym_stat_stride(int64_t n)
 {
     int st = n >= (1 << 17) ? 64 : 32;
@@ -517,7 +543,11 @@ static int sym_stat_stride(int64_t n)
     return st;
 }
 
-static bool self_search_symmetric_eligible(const PlanCtx &c, int k, int *j_out = nullptr, int *qcap_out = nullptr)
+// Will the symmetric launch take this self-search?  (knn_flat_search_self asks BEFORE it sets aside device memory for the whole
+// n x k result.)  Fills the sample's half of the plan, in ONE place: the rank j, the sample it is taken from and what the
+// selections expect must belong together (a rank worked out for a sparser sample is too tight a bound on a denser one: every
+// verification fails and the plain path repeats the search).
+static bool self_search_symmetric_eligible(const PlanCtx &c, int k, SymPlan *out = nullptr)
 {
     const int64_t n = c.ntotal;
     if (n < dev_knob("KNN355_SYM_MIN_N", 3000) || k > KNN_REGISTER_SELECT_MAX_K || k >= n || !stat_seed_allowed(c) || (c.flags & KNN_TUNE_NO_SYM) || c.force_qt || c.force_chunks || c.approx16) return false;
@@ -528,9 +558,128 @@ static bool self_search_symmetric_eligible(const PlanCtx &c, int k, int *j_out =
     const double expect = 1.3 * (double)j * (double)n / (double)S + 1.25 * k;
     const int qcap = (int)std::min<double>(((int64_t)(2.0 * expect) + 1024 + 63) / 64 * 64, 1 << 20);
     if ((double)n * qcap * 8.0 > 24.0 * (1u << 30)) return false;
-    if (j_out) *j_out = j;
-    if (qcap_out) *qcap_out = qcap;
+    if (out) {
+        out->st = st; out->S = S; out->j = j; out->qcap = qcap;
+        out->n_expect = (int)std::min<double>((double)qcap, expect);
+    }
     return true;
+}
+
+// Dynamic LDS of a symmetric workgroup: the plain layout with at least 72 KB of lds_main on the 128-row tile (8 KB of slots
+// for its sparse epilogue, see lds_main in the kernel) + thresholds, per-half counts and bases of the database tile's rows
+// (s_thr2, s_cnt2, s_base2).
+static size_t scan_lds_bytes_sym(int qt, int dt, int cap) { return scan_lds_bytes(qt, dt, cap, qt == 128 ? 73728 : 0) + (size_t)(2 + 2) * dt * 4; }
+
+// The plan of a self-search of every row against every row; false where the plain path must serve it.  can_stream: the caller
+// gave host arrays and holds the copy stream.
+static bool plan_self_symmetric(const PlanCtx &c, int k, bool can_stream, SymPlan &sp)
+{
+    if (!self_search_symmetric_eligible(c, k, &sp)) return false;
+    const int64_t n = c.ntotal;
+    ScanPlan &pl = sp.pl;
+    // (tile shape, list capacity.  256-row tiles only on demand, KNN_TUNE_BIG_TILE: the symmetric launch filters every tile
+    // twice and executes half the flops per row pair, its epilogue weighs twice as much beside the K loop -- Pfam-sized
+    // k = 100 / 1000: 372.7 / 392.6 ms on 256-row tiles against 349.7 / 377.4 on 128-row tiles, one box)
+    PlanOpts po;
+    po.seeded = true; po.allow_big = (c.flags & KNN_TUNE_BIG_TILE) != 0;
+    make_plan(c, n, n, k, po, pl);
+    if (pl.qt != pl.dt || (pl.qt != 128 && pl.qt != 256)) return false;
+    sp.ts = pl.qt;
+    sp.tiles = (int)((n + sp.ts - 1) / sp.ts);
+    sp.k_sample = std::min(k, sp.j + std::max(sp.j >> 2, 8) + 8);
+    sp.slots = (sp.ts == 256 ? 1 : 2) * (int64_t)std::max(1, c.num_cus);
+    sp.max_wgs = std::max<int64_t>(sp.slots, (int64_t)((2ull << 30) / ((size_t)pl.qt * pl.cap * 8)));
+    // (eight groups for gigabytes of result; four from 32 MB on -- CATH-sized, 113 query tiles, 52 MB: cath.search end to end
+    // 5.03 -> 4.43 ms with four, 4.62 with five, 4.94 with eight: every group is a launch with its own tail and selection)
+    const size_t result_bytes = (size_t)n * k * 12;
+    const int want_groups = std::min(SYM_MAX_GROUPS, std::max(2, dev_knob("KNN355_SELF_GROUPS", result_bytes >= ((size_t)256 << 20) && sp.tiles >= 16 * SYM_MAX_GROUPS ? SYM_MAX_GROUPS : 4)));
+    const bool stream_out = can_stream && result_bytes >= ((size_t)dev_knob("KNN355_SELF_STREAM_MIN_MB", 32) << 20) && sp.tiles >= 16 * want_groups;
+    sp.groups = stream_out ? want_groups : 1;
+    sp.cu_turn = !(c.flags & KNN_TUNE_NO_TURNS) && sp.ts == 128;
+    sp.lds = scan_lds_bytes_sym(pl.qt, pl.dt, pl.cap) + (size_t)dev_knob("KNN355_LDS_PAD", 0); // (developer build: more LDS than a second workgroup leaves room for = one workgroup per CU)
+    sp.name = sp.ts == 256 ? "flat_scan_q256_d256_sym" : "flat_scan_q128_d128_sym";
+    return true;
+}
+
+// first row of group g's query tiles: group g serves rows [sym_group_row0(g), sym_group_row0(g + 1)) -- equal shares of the RESULT
+static int64_t sym_group_row0(const SymPlan &sp, int64_t n, int g) { return std::min<int64_t>(n, (int64_t)sp.tiles * g / sp.groups * sp.ts); }
+
+// The work table of a symmetric launch: workgroup = (query tile I, a run of database tiles J >= I), group after group
+// (gstart[g] .. gstart[g + 1]: the items of group g, the launch that serves query tiles [tiles g / groups, tiles (g + 1) /
+// groups); the first group is the longest).  It depends on (tiles, groups, slots) only.
+struct SymTable {
+    std::vector<SymItem> items;
+    std::vector<int64_t> gstart;
+    int first_run; // the first group's run length (introspection)
+};
+
+static SymTable sym_work_table(int tiles, int groups, int64_t slots)
+{
+    SymTable t;
+    t.gstart.assign(1, 0);
+    t.first_run = 16;
+    for (int g = 0; g < groups; g++) {
+        const int I0 = (int)((int64_t)tiles * g / groups), I1 = (int)((int64_t)tiles * (g + 1) / groups);
+        // the run length that minimises rounds x (tiles + half a tile of fixed work), of each group by itself: a group is a
+        // launch, and a short one -- the later groups of a CATH-sized index -- fills the slots only with short runs
+        int best_tp = 16;
+        int64_t best_cost = INT64_MAX;
+        for (int tp = dev_knob("KNN355_SYM_MIN_TP", 1); tp <= 96; tp++) {
+            int64_t wgs = 0;
+            for (int I = I0; I < I1; I++) wgs += (tiles - I + tp - 1) / tp;
+            const int64_t rounds = (wgs + slots - 1) / slots;
+            const int64_t cost = rounds * (2 * tp + 1);
+            if (cost < best_cost || (cost == best_cost && tp > best_tp)) { best_cost = cost; best_tp = tp; }
+        }
+        if (g == 0) t.first_run = best_tp;
+        const size_t at = t.items.size();
+        for (int I = I0; I < I1; I++)
+            for (int j0 = I; j0 < tiles; j0 += best_tp) t.items.push_back({I, j0, std::min(best_tp, tiles - j0)});
+        // long runs first: the short tails of every query tile fill the last round
+        std::stable_sort(t.items.begin() + at, t.items.end(), [](const SymItem &a, const SymItem &b) { return a.jcount > b.jcount; });
+        t.gstart.push_back((int64_t)t.items.size());
+    }
+    return t;
+}
+
+// ---- range scan ---------------------------------------------------------------
+struct RangePlan {
+    int qt, dt, nqtiles, nchunks, tiles_base, tiles_rem, grid;
+    bool diff;
+    size_t lds;
+    const char *name;
+};
+
+// One block of nq queries of a range search.  The tile: 32 queries x 256 rows for small batches (a 10 M-row scan of 32 queries
+// is HBM-bound; a 128-wide tile would do 4x its matrix work), 128 x 128 for large ones; the difference build is the 32-query tile.
+static RangePlan plan_range(const PlanCtx &c, int64_t nq)
+{
+    RangePlan pl;
+    // FAISS's small-batch rule, as make_plan applies it: the caller's whole batch decides the formula, for every block
+    pl.diff = c.metric == KNN_METRIC_L2 && c.batch_nq < 20;
+    const bool wide = !pl.diff && nq > 64;
+    pl.qt = wide ? 128 : 32;
+    pl.dt = wide ? 128 : 256;
+    pl.nqtiles = (int)((nq + pl.qt - 1) / pl.qt);
+    const int64_t tiles = (c.ntotal + pl.dt - 1) / pl.dt;
+    // about two workgroups per CU, contiguous rows per chunk
+    pl.nchunks = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (2 * (int64_t)c.num_cus + pl.nqtiles - 1) / pl.nqtiles));
+    pl.tiles_base = (int)(tiles / pl.nchunks);
+    pl.tiles_rem = (int)(tiles % pl.nchunks);
+    pl.grid = pl.nqtiles * pl.nchunks;
+    const size_t stage = (size_t)(pl.dt + pl.qt) * 128 * 2, park = (size_t)pl.qt * (pl.dt + 1) * 4;
+    pl.lds = std::max(stage, park) + (size_t)pl.dt * 4 + (size_t)pl.qt * 4;
+    pl.name = pl.diff ? "range_scan_q32_d256_diff" : (wide ? "range_scan_q128_d128" : "range_scan_q32_d256");
+    return pl;
+}
+
+static const size_t KNN_RANGE_STAGE_BYTES = (size_t)192 << 20; // staging segments of one block (12 bytes per entry)
+
+// entries of a staging segment: the block's share of the budget per (query, chunk), never more than a chunk's rows
+static int64_t range_segcap(const RangePlan &pl, int64_t nq)
+{
+    const int64_t chunk_rows = (int64_t)(pl.tiles_base + (pl.tiles_rem ? 1 : 0)) * pl.dt;
+    return std::max<int64_t>(1, std::min<int64_t>(chunk_rows, (int64_t)(KNN_RANGE_STAGE_BYTES / 12) / (nq * pl.nchunks)));
 }
 
 // Which flat_scan_kernel build serves a launch is pick_scan_kernel's choice (knn355.hip) from (query tile, metric, bf16 rows,

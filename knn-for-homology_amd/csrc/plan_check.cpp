@@ -1,12 +1,21 @@
-// The flat search's planner (plan.h) on a machine without a GPU:
+// The planners of plan.h on a machine without a GPU:
 //   plan_check cases   reads lines "nb nq k metric flags force_qt force_chunks batch_nq allow_stat [approx16]" from stdin and prints,
 //                      for each, the pieces of the batch and the plan of every piece (tests/plan_cases.py, tests/test_plan_cpu.py)
+//   plan_check sym     reads lines "n k metric flags can_stream [force_qt]": the symmetric self-search's plan and work table --
+//                      "plain", or kernel ts tiles st S j qcap k_sample n_expect groups gstart[0..groups] first_run items lds
+//                      max_wgs and the 64-bit FNV-1a hash of the items' integers
+//   plan_check range   reads lines "n nq metric batch": the range scan's plan of one block of nq queries -- kernel qt dt nqtiles
+//                      nchunks tiles_base tiles_rem grid diff lds segcap
 //   plan_check sweep   walks a grid of shapes and flags and exits non-zero on a broken invariant
 // The device has 256 CUs in both.  Built with the host compiler and -fsanitize=address,undefined (make plan_check).
 #include "plan.h"
 
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include <set>
+#include <string>
+#include <tuple>
 
 static const int MAX_LEVELS = 8; // (knn_index_s::MAX_LEVELS: levels of seed recursion)
 
@@ -79,21 +88,83 @@ static int run_cases()
     return 0;
 }
 
+static int run_sym()
+{
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long n;
+        int k, metric, flags, can_stream, force_qt = 0;
+        if (sscanf(line, "%lld %d %d %d %d %d", &n, &k, &metric, &flags, &can_stream, &force_qt) < 5) {
+            if (line[0] == '\n' || line[0] == '#') continue;
+            fprintf(stderr, "plan_check: bad case line: %s", line);
+            return 2;
+        }
+        SymPlan sp;
+        if (!plan_self_symmetric(make_ctx(n, n, metric, flags, force_qt, 0, 0, false), k, can_stream != 0, sp)) {
+            printf("plain\n");
+            continue;
+        }
+        const SymTable t = sym_work_table(sp.tiles, sp.groups, sp.slots);
+        uint64_t hash = 0xcbf29ce484222325ull;
+        for (const SymItem &it : t.items)
+            for (int v : {it.qtile, it.jt0, it.jcount})
+                for (int b = 0; b < 4; b++) hash = (hash ^ (((uint32_t)v >> (8 * b)) & 0xff)) * 0x100000001b3ull;
+        printf("%s %d %d %d %lld %d %d %d %d %d", sp.name, sp.ts, sp.tiles, sp.st, (long long)sp.S, sp.j, sp.qcap, sp.k_sample, sp.n_expect, sp.groups);
+        for (int64_t g : t.gstart) printf(" %lld", (long long)g);
+        printf(" %d %zu %zu %lld %016llx\n", t.first_run, t.items.size(), sp.lds, (long long)sp.max_wgs, (unsigned long long)hash);
+    }
+    return 0;
+}
+
+static int run_range()
+{
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long n, nq, batch;
+        int metric;
+        if (sscanf(line, "%lld %lld %d %lld", &n, &nq, &metric, &batch) < 4) {
+            if (line[0] == '\n' || line[0] == '#') continue;
+            fprintf(stderr, "plan_check: bad case line: %s", line);
+            return 2;
+        }
+        const RangePlan p = plan_range(make_ctx(n, nq, metric, 0, 0, 0, batch, false), nq);
+        printf("%s %d %d %d %d %d %d %d %d %zu %lld\n", p.name, p.qt, p.dt, p.nqtiles, p.nchunks, p.tiles_base, p.tiles_rem, p.grid, (int)p.diff, p.lds,
+               (long long)range_segcap(p, nq));
+    }
+    return 0;
+}
+
 static long long g_checked = 0, g_broken = 0;
-#define INVARIANT(cond)                                                                                                                  \
-    do {                                                                                                                                 \
-        if (!(cond)) {                                                                                                                   \
-            if (g_broken++ < 20)                                                                                                         \
-                fprintf(stderr, "broken: %s  [nb %lld view %lld nq %lld k %d metric %d flags %d qt %d approx16 %d stat %d level %d: %s grid %d chunks %d]\n", #cond, \
-                        (long long)c.ntotal, (long long)nb, (long long)nq, k, c.metric, c.flags, c.force_qt, (int)c.approx16, (int)allow_stat, level, p.name, p.grid, p.nchunks); \
-        }                                                                                                                                \
+static void broken(const char *what, const std::string &where)
+{
+    if (g_broken++ < 20) fprintf(stderr, "broken: %s  [%s]\n", what, where.c_str());
+}
+// (where: the checking function's description of the plan at hand)
+#define INVARIANT(cond)                       \
+    do {                                      \
+        if (!(cond)) broken(#cond, where());  \
     } while (0)
+
+static std::string describe(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static std::string describe(const char *fmt, ...)
+{
+    char buf[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
 
 // one search_view call and the sample levels below it
 static void check_view(const PlanCtx &c, int64_t nb, int64_t nq, int k, int level, int row_mul, int vshift, bool allow_stat)
 {
     const SearchPlan s = plan_search(c, nb, nq, k, level, row_mul, allow_stat, 0);
     const ScanPlan &p = s.pl;
+    const auto where = [&] {
+        return describe("nb %lld view %lld nq %lld k %d metric %d flags %d qt %d approx16 %d stat %d level %d: %s grid %d chunks %d", (long long)c.ntotal, (long long)nb,
+                        (long long)nq, k, c.metric, c.flags, c.force_qt, (int)c.approx16, (int)allow_stat, level, p.name, p.grid, p.nchunks);
+    };
     g_checked++;
     const int64_t ntiles = (nb + p.dt - 1) / p.dt;
     INVARIANT(level < MAX_LEVELS);
@@ -134,6 +205,60 @@ static void check_batch(const PlanCtx &c, int64_t nq, int k, bool allow_stat)
     }
 }
 
+// the symmetric self-search: every tile pair (I, J >= I) is served exactly once, by the group that owns query tile I
+static void check_sym(const PlanCtx &c, int k, bool can_stream)
+{
+    SymPlan sp;
+    if (!plan_self_symmetric(c, k, can_stream, sp)) return;
+    const int64_t n = c.ntotal;
+    const int T = sp.tiles, G = sp.groups;
+    const auto where = [&] {
+        return describe("self-search n %lld k %d metric %d flags %d can_stream %d: %s tiles %d groups %d", (long long)n, k, c.metric, c.flags, (int)can_stream, sp.name, T, G);
+    };
+    g_checked++;
+    INVARIANT(sp.j > 0 && sp.qcap > 0 && sp.n_expect > 0 && sp.n_expect <= sp.qcap && sp.k_sample <= k);
+    INVARIANT(sp.lds <= 160 * 1024);
+    INVARIANT(sp.max_wgs >= sp.slots);
+    INVARIANT(G >= 1 && G <= SYM_MAX_GROUPS && (G == 1 || can_stream));
+    // (the table and the row ranges depend on these four only: each distinct table is built and checked once)
+    static std::set<std::tuple<int64_t, int, int, int64_t>> seen;
+    if (!seen.insert(std::make_tuple(n, sp.ts, G, sp.slots)).second) return;
+    const SymTable t = sym_work_table(T, G, sp.slots);
+    INVARIANT((int)t.gstart.size() == G + 1 && t.gstart[0] == 0 && t.gstart[(size_t)G] == (int64_t)t.items.size());
+    INVARIANT(sym_group_row0(sp, n, 0) == 0 && sym_group_row0(sp, n, G) == n); // the groups' row ranges [row0(g), row0(g + 1)) tile [0, n)
+    std::vector<int> next((size_t)T); // per query tile: where its runs so far end (the stable sort keeps a tile's runs of one length in order)
+    for (int I = 0; I < T; I++) next[(size_t)I] = I;
+    for (int g = 0; g < G; g++) {
+        const int64_t i0 = t.gstart[(size_t)g], i1 = t.gstart[(size_t)g + 1];
+        INVARIANT(i0 <= i1 && i1 <= (int64_t)t.items.size());
+        if (i0 > i1 || i1 > (int64_t)t.items.size()) return;
+        // group g owns the query tiles whose rows it selects and downloads
+        const int I0 = (int)((sym_group_row0(sp, n, g) + sp.ts - 1) / sp.ts), I1 = (int)((sym_group_row0(sp, n, g + 1) + sp.ts - 1) / sp.ts);
+        INVARIANT(I0 <= I1);
+        for (int64_t i = i0; i < i1; i++) {
+            const SymItem &it = t.items[(size_t)i];
+            INVARIANT(it.qtile >= I0 && it.qtile < I1);
+            if (it.qtile < 0 || it.qtile >= T) return;
+            // the runs of a query tile start at the tile and touch end to start
+            INVARIANT(it.jcount >= 1 && it.jt0 == next[(size_t)it.qtile] && it.jt0 + it.jcount <= T);
+            next[(size_t)it.qtile] = it.jt0 + it.jcount;
+            INVARIANT(i == i0 || t.items[(size_t)i - 1].jcount >= it.jcount); // inside a group jcount does not rise
+        }
+    }
+    for (int I = 0; I < T; I++) INVARIANT(next[(size_t)I] == T); // ... and end at `tiles`
+}
+
+static void check_range(const PlanCtx &c, int64_t nq)
+{
+    const RangePlan p = plan_range(c, nq);
+    const auto where = [&] { return describe("range n %lld nq %lld metric %d: %s grid %d chunks %d", (long long)c.ntotal, (long long)nq, c.metric, p.name, p.grid, p.nchunks); };
+    g_checked++;
+    INVARIANT((int64_t)p.tiles_base * p.nchunks + p.tiles_rem == (c.ntotal + p.dt - 1) / p.dt);
+    INVARIANT(p.grid == p.nqtiles * p.nchunks);
+    INVARIANT(p.lds <= 160 * 1024);
+    INVARIANT(range_segcap(p, nq) >= 1);
+}
+
 static int run_sweep()
 {
     const int64_t nbs[] = {1, 255, 256, 257, 1023, 4096, 8192, 16385, 1 << 15, 1 << 18, (1 << 18) + 1, 1250000, 10000000, 2147483647};
@@ -153,7 +278,8 @@ static int run_sweep()
                             for (int allow_stat = 0; allow_stat < 2; allow_stat++)
                                 check_batch(make_ctx(nb, nq, metric, flags, qt, 0, 0, false), nq, k, allow_stat != 0);
     // beside the issue's grid: the bf16 index of HNSW's coarse entry scan (no entry point reaches its introspection from outside),
-    // a forced chunk count, a piece of a larger batch, and the symmetric self-search's launch
+    // a forced chunk count, a piece of a larger batch; the symmetric self-search of every eligible (n, k, flags, can_stream) and
+    // the range scan of every (n, nq, metric)
     for (int64_t nb : nbs)
         for (int64_t nq : nqs)
             for (int k : ks)
@@ -161,20 +287,10 @@ static int run_sweep()
                     check_batch(make_ctx(nb, nq, metric, 0, 0, 0, 0, true), nq, k, false);
                     check_batch(make_ctx(nb, nq, metric, 0, 0, 3, 0, false), nq, k, true);
                     check_batch(make_ctx(nb, nq, metric, 0, 0, 0, 100, false), nq, k, true);
-                    for (int flags : {0, (int)KNN_TUNE_BIG_TILE}) {
-                        const PlanCtx c = make_ctx(nb, nb, metric, flags, 0, 0, 0, false);
-                        int j = 0, qcap = 0;
-                        if (nq != 1 || !self_search_symmetric_eligible(c, k, &j, &qcap)) continue;
-                        ScanPlan p;
-                        PlanOpts po;
-                        po.seeded = true; po.allow_big = flags != 0;
-                        make_plan(c, nb, nb, k, po, p);
-                        g_checked++;
-                        const bool allow_stat = true;
-                        const int level = 0;
-                        INVARIANT(j > 0 && qcap > 0);
-                        INVARIANT(scan_lds_bytes(p.qt, p.dt, p.cap, p.qt == 128 ? 73728 : 0) + (size_t)4 * p.dt * 4 <= 160 * 1024);
-                    }
+                    if (nq == 1) // (a self-search has no query count of its own)
+                        for (int flags : flagset)
+                            for (int can_stream = 0; can_stream < 2; can_stream++) check_sym(make_ctx(nb, nb, metric, flags, 0, 0, 0, false), k, can_stream != 0);
+                    check_range(make_ctx(nb, nq, metric, 0, 0, 0, 0, false), nq);
                 }
     printf("plan_check sweep: %lld plans checked, %lld broken\n", g_checked, g_broken);
     return g_broken ? 1 : 0;
@@ -183,7 +299,9 @@ static int run_sweep()
 int main(int argc, char **argv)
 {
     if (argc == 2 && !strcmp(argv[1], "cases")) return run_cases();
+    if (argc == 2 && !strcmp(argv[1], "sym")) return run_sym();
+    if (argc == 2 && !strcmp(argv[1], "range")) return run_range();
     if (argc == 2 && !strcmp(argv[1], "sweep")) return run_sweep();
-    fprintf(stderr, "usage: plan_check cases < lines | plan_check sweep\n");
+    fprintf(stderr, "usage: plan_check cases|sym|range < lines | plan_check sweep\n");
     return 2;
 }

@@ -279,36 +279,9 @@ __global__ __launch_bounds__(256) void range_pick_kernel(const float *__restrict
 // host side
 // ---------------------------------------------------------------------------
 static const int64_t KNN_RANGE_QB = 16384;                   // queries per block at most
-static const size_t KNN_RANGE_STAGE_BYTES = (size_t)192 << 20; // staging segments of one block (12 bytes per entry)
 static const size_t KNN_RANGE_OUT_BYTES = (size_t)192 << 20;   // contiguous results on the device per copy-out (at least one query's)
 
-struct RangePlan {
-    int qt, dt, nqtiles, nchunks, tiles_base, tiles_rem, grid;
-    bool diff;
-    size_t lds;
-    const char *name;
-};
-
-// the tile: 32 queries x 256 rows for small batches (a 10 M-row scan of 32 queries is HBM-bound; a 128-wide tile would do
-// 4x its matrix work), 128 x 128 for large ones; the difference build is the 32-query tile
-static void range_make_plan(const knn_index_s *h, int64_t nq, bool diff, RangePlan &pl)
-{
-    const bool wide = !diff && nq > 64;
-    pl.diff = diff;
-    pl.qt = wide ? 128 : 32;
-    pl.dt = wide ? 128 : 256;
-    pl.nqtiles = (int)((nq + pl.qt - 1) / pl.qt);
-    const int64_t tiles = (h->ntotal + pl.dt - 1) / pl.dt;
-    // about two workgroups per CU, contiguous rows per chunk
-    pl.nchunks = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (2 * (int64_t)h->num_cus + pl.nqtiles - 1) / pl.nqtiles));
-    pl.tiles_base = (int)(tiles / pl.nchunks);
-    pl.tiles_rem = (int)(tiles % pl.nchunks);
-    pl.grid = pl.nqtiles * pl.nchunks;
-    const size_t stage = (size_t)(pl.dt + pl.qt) * 128 * 2, park = (size_t)pl.qt * (pl.dt + 1) * 4;
-    pl.lds = std::max(stage, park) + (size_t)pl.dt * 4 + (size_t)pl.qt * 4;
-    pl.name = diff ? "range_scan_q32_d256_diff" : (wide ? "range_scan_q128_d128" : "range_scan_q32_d256");
-}
-
+// one launch of a block's plan (plan_range, plan.h)
 static int range_launch(knn_index_s *h, const RangeParams &p, const RangePlan &pl, hipStream_t s)
 {
     const bool l2 = h->metric == KNN_METRIC_L2;
@@ -316,15 +289,8 @@ static int range_launch(knn_index_s *h, const RangeParams &p, const RangePlan &p
     if (pl.diff) kern = range_scan_kernel<4, 1, 2, 1, true, true>;
     else if (pl.qt == 128) kern = l2 ? range_scan_kernel<2, 2, 2, 2, true, false> : range_scan_kernel<2, 2, 2, 2, false, false>;
     else kern = l2 ? range_scan_kernel<4, 1, 2, 1, true, false> : range_scan_kernel<4, 1, 2, 1, false, false>;
-    const int slot = (int)(h->nlaunches % knn_index_s::RING);
-    if (!h->ring0[slot]) {
-        HIP_TRY(hipEventCreate(&h->ring0[slot]));
-        HIP_TRY(hipEventCreate(&h->ring1[slot]));
-    }
-    h->ev0 = h->ring0[slot];
-    h->ev1 = h->ring1[slot];
-    h->nlaunches++;
-    HIP_TRY(hipEventRecord(h->ev0, s));
+    const int rc = open_timed_launch(h, s);
+    if (rc) return rc;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
     hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(256), pl.lds, s, p);
     HIP_TRY(hipGetLastError());
@@ -357,8 +323,7 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const bool l2 = h->metric == KNN_METRIC_L2;
-    // FAISS's small-batch rule, as make_plan applies it: the caller's whole batch decides the formula, for every block
-    const bool diff = l2 && h->batch_nq < 20;
+    const PlanCtx c = plan_ctx(h);
     const int dp = h->dp;
     RangeParams p;
     memset(&p, 0, sizeof(p));
@@ -374,6 +339,7 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
     for (int64_t b0 = 0; b0 < nq; b0 += KNN_RANGE_QB) {
         const int64_t m = std::min(KNN_RANGE_QB, nq - b0);
         h->range_qblocks++;
+        const RangePlan pl = plan_range(c, m);
         // the block's queries on the device, zero padded to dp, and their squared norms
         const float *xq, *xn = nullptr;
         if (q_host) {
@@ -387,21 +353,16 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
                 if (rc) return rc;
                 xq = (const float *)h->ws_q.p;
             }
-            if (l2 && !diff) {
+            if (l2 && !pl.diff) {
                 int rc = norms_dev_impl(xq, m, h->d, dp, (float *)h->ws_rqn.p, s);
                 if (rc) return rc;
                 xn = (const float *)h->ws_rqn.p;
             }
         } else {
             xq = h->xb + (size_t)(self_row0 + b0) * dp;
-            if (l2 && !diff) xn = h->yn + self_row0 + b0; // (the stored norms: the same chain as norm_rows_kernel over these rows)
+            if (l2 && !pl.diff) xn = h->yn + self_row0 + b0; // (the stored norms: the same chain as norm_rows_kernel over these rows)
         }
-        RangePlan pl;
-        range_make_plan(h, m, diff, pl);
-        const int64_t pairs = m * pl.nchunks;
-        const int64_t chunk_rows = (int64_t)(pl.tiles_base + (pl.tiles_rem ? 1 : 0)) * pl.dt;
-        // staging segments: the block's share of the budget per (query, chunk), never more than a chunk's rows
-        const int64_t segcap = std::max<int64_t>(1, std::min<int64_t>(chunk_rows, (int64_t)(KNN_RANGE_STAGE_BYTES / 12) / pairs));
+        const int64_t pairs = m * pl.nchunks, segcap = range_segcap(pl, m);
         if (h->ws_rsegD.ensure((size_t)pairs * segcap * 4, h->done, s) || h->ws_rsegI.ensure((size_t)pairs * segcap * 8, h->done, s) ||
             h->ws_rcnt.ensure((size_t)pairs * 4 * 2, h->done, s))
             return set_err(KNN_ERR_HIP, "range_search: out of device memory");
