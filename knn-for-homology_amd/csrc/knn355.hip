@@ -3129,49 +3129,97 @@ __global__ __launch_bounds__(64) void scan16_queries_kernel(const float *__restr
     }
 }
 
-// The tail of a 16-bit prefiltered search, one workgroup per query.  ak[q]: the exact top-kp of the approximate keys, sorted.
-// With t = the k-th of them and B = B_q, every row of the exact top-k has an approximate score <= t + 2B; all those rows are
-// among the kp if the kp-th approximate score is above t + 2B (or the kp hold fewer real rows) -- otherwise fail[q] = 1 and the
-// gated fp32 search behind this launch redoes the search.  The rows inside the window are scored with the contract's chain
-// (pair_distance_kernel's order) into exact keys ok[q][0 .. kp) (KEY_PAD elsewhere); their top-k is the search's result.
+// The tail of a 16-bit prefiltered search, one workgroup per (query, slice of RS16_ROWS of its k' keys).  ak[q]: the exact
+// top-kp of the approximate keys, sorted.  With t = the k-th of them and B = B_q, every row of the exact top-k has an
+// approximate score <= t + 2B; all those rows are among the kp if the kp-th approximate score is above t + 2B (or the kp hold
+// fewer real rows) -- otherwise fail[q] = 1 and the gated fp32 search behind this launch redoes the search.  Every slice derives
+// that check from the same four words, so all slices of a query agree; slice 0 writes fail[q] and counts the query's window
+// for sstat[0].  The rows inside the window are scored with the contract's chain (pair_distance_kernel's order) into exact keys
+// ok[q][0 .. kp) (KEY_PAD elsewhere); their top-k is the search's result.
+//   fetching  the 256 threads read a slab of RS16_SLAB floats of each of the slice's rows together, 16 contiguous bytes per
+//             lane (a 4 KB row is one fully coalesced load instruction), all rows' loads in flight at once, into LDS
+//   chain     lane r < RS16_ROWS then runs row r's chain out of LDS, one accumulator carried across the slabs.  The row pitch
+//             is the slab + 4 floats: the 16 lanes' ds_read_b128 of one column fall on 16 different 16-byte bank slots
+constexpr int RS16_ROWS = 16, RS16_SLAB = 1024;
+static inline int rescore16_slab(int dp) { return dp < RS16_SLAB ? dp : RS16_SLAB; }
+// dynamic LDS: the query's slab + RS16_ROWS padded row slabs (69888 bytes from dp = 1024 on: the launch opts in)
+static inline size_t rescore16_lds(int dp) { return ((size_t)rescore16_slab(dp) + (size_t)RS16_ROWS * (rescore16_slab(dp) + 4)) * 4; }
+
 __global__ __launch_bounds__(256) void rescore16_kernel(const uint64_t *__restrict__ ak, int kp, int k, const float *__restrict__ Bq,
                                                         const uint32_t *__restrict__ pfail, uint32_t *__restrict__ fail,
                                                         const float *__restrict__ xb, int dp, const float *__restrict__ xq, uint32_t id_base,
                                                         uint64_t *__restrict__ ok, uint32_t *__restrict__ sstat)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *sq = (float *)smem; // [dp] the query
-    __shared__ int s_fail, s_cnt;
-    __shared__ double s_lim;
+    const int sl0 = dp < RS16_SLAB ? dp : RS16_SLAB, pitch = sl0 + 4;
+    float *sq = (float *)smem; // [sl0] the query's slab
+    float *sy = sq + sl0;      // [RS16_ROWS][pitch] the rows' slabs
+    __shared__ int s_cnt;
     const int tid = threadIdx.x;
     const int64_t q = blockIdx.x;
-    for (int i = tid; i < dp; i += 256) sq[i] = xq[(size_t)q * dp + i];
+    const int j0 = (int)blockIdx.y * RS16_ROWS;
     const uint64_t *a = ak + (size_t)q * kp;
-    if (tid == 0) {
-        int f = pfail[q] != 0u;
-        double lim = INFINITY;
+    // the window check (uniform: every thread of every slice computes it from the same words)
+    bool f = pfail[q] != 0u;
+    double lim = INFINITY;
+    {
         const uint64_t tk = a[k - 1], last = a[kp - 1];
         if (!f && tk != KEY_PAD) {
             lim = (double)ord2f((uint32_t)(tk >> 32)) + 2.0 * (double)Bq[q];
-            if (last != KEY_PAD && !(lim < (double)ord2f((uint32_t)(last >> 32)))) f = 1;
+            if (last != KEY_PAD && !(lim < (double)ord2f((uint32_t)(last >> 32)))) f = true;
         }
-        s_fail = f;
-        s_lim = lim;
-        s_cnt = 0;
-        fail[q] = (uint32_t)f;
     }
-    __syncthreads();
-    const bool f = s_fail != 0;
-    const double lim = s_lim;
-    int cnt = 0;
-    for (int j = tid; j < kp; j += 256) {
-        const uint64_t key = a[j];
-        uint64_t out = KEY_PAD;
-        if (!f && key != KEY_PAD && (double)ord2f((uint32_t)(key >> 32)) <= lim) {
-            const float *y = xb + (size_t)((uint32_t)key - id_base) * dp;
-            float acc = 0.0f;
+    auto inside = [&](uint64_t key) -> bool { return !f && key != KEY_PAD && (double)ord2f((uint32_t)(key >> 32)) <= lim; };
+    if (blockIdx.y == 0) { // (uniform) the query's flag, and its window over all slices for the search's largest
+        if (tid == 0) {
+            fail[q] = f ? 1u : 0u;
+            s_cnt = 0;
+        }
+        __syncthreads();
+        int cnt = 0;
+        for (int j = tid; j < kp; j += 256) cnt += inside(a[j]) ? 1 : 0;
+        cnt = wave_sum(cnt);
+        if ((tid & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
+        __syncthreads();
+        if (tid == 0 && !f) atomicMax(&sstat[0], (uint32_t)s_cnt);
+    }
+    // this slice's rows (uniform)
+    uint32_t mask = 0;
+    uint64_t mykey = KEY_PAD; // lane r < RS16_ROWS of every wave: key j0 + r
+#pragma unroll
+    for (int r = 0; r < RS16_ROWS; r++) {
+        const uint64_t key = j0 + r < kp ? a[j0 + r] : KEY_PAD;
+        if (inside(key)) mask |= 1u << r;
+        if (r == (tid & 63)) mykey = key;
+    }
+    if (!mask) { // (uniform) nothing of the window in this slice
+        if (tid < RS16_ROWS && j0 + tid < kp) ok[(size_t)q * kp + j0 + tid] = KEY_PAD;
+        return;
+    }
+    const bool mine = tid < RS16_ROWS && ((mask >> tid) & 1u);
+    const int c = tid * 4;
+    float acc = 0.0f;
+    for (int s0 = 0; s0 < dp; s0 += RS16_SLAB) {
+        const int sl = dp - s0 < RS16_SLAB ? dp - s0 : RS16_SLAB; // (a multiple of 32, like dp)
+        if (s0) __syncthreads(); // (the chains have read the slab before)
+        if (c < sl) {
+            f32x4 v[RS16_ROWS];
+#pragma unroll
+            for (int r = 0; r < RS16_ROWS; r++)
+                if ((mask >> r) & 1u) { // (uniform)
+                    const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mykey, r) - id_base;
+                    v[r] = *(const f32x4 *)(xb + (size_t)row * dp + s0 + c);
+                }
+            *(f32x4 *)(sq + c) = *(const f32x4 *)(xq + (size_t)q * dp + s0 + c);
+#pragma unroll
+            for (int r = 0; r < RS16_ROWS; r++)
+                if ((mask >> r) & 1u) *(f32x4 *)(sy + r * pitch + c) = v[r];
+        }
+        __syncthreads();
+        if (mine) {
+            const float *y = sy + tid * pitch;
 #pragma unroll 4
-            for (int k0 = 0; k0 < dp; k0 += 8) {
+            for (int k0 = 0; k0 < sl; k0 += 8) {
                 const f32x4 q0 = *(const f32x4 *)(sq + k0), q1 = *(const f32x4 *)(sq + k0 + 4);
                 const f32x4 y0 = *(const f32x4 *)(y + k0), y1 = *(const f32x4 *)(y + k0 + 4);
 #pragma unroll
@@ -3180,15 +3228,16 @@ __global__ __launch_bounds__(256) void rescore16_kernel(const uint64_t *__restri
                     acc = __builtin_fmaf(q1[m], y1[m], acc);
                 }
             }
-            const float v = -acc + 0.0f;
-            out = ((uint64_t)f2ord(v) << 32) | (uint32_t)key;
-            cnt++;
         }
-        ok[(size_t)q * kp + j] = out;
     }
-    if (cnt) atomicAdd(&s_cnt, cnt);
-    __syncthreads();
-    if (tid == 0 && !f) atomicMax(&sstat[0], (uint32_t)s_cnt);
+    if (tid < RS16_ROWS && j0 + tid < kp) {
+        uint64_t out = KEY_PAD;
+        if (mine) {
+            const float v = -acc + 0.0f;
+            out = ((uint64_t)f2ord(v) << 32) | (uint32_t)mykey;
+        }
+        ok[(size_t)q * kp + j0 + tid] = out;
+    }
 }
 
 // ===========================================================================
@@ -4134,7 +4183,8 @@ static PlanCtx plan_ctx(const knn_index_s *h)
 //   scan16_queries_kernel   fp16 queries, exponents, bounds B_q, the per-query fallback flags
 //   16-bit pass             the streaming scan machinery on the fp16 copies with k' = s16_kprime(k): the exact top-k'
 //                           of the approximate scores (state reset, flat_scan_q32_d256_f16x, selection)
-//   rescore16_kernel        the window check and the exact scores of the rows inside the window
+//   rescore16_kernel        the window check and the exact scores of the rows inside the window: a grid of (query, 16 of its
+//                           k' keys), every row fetched by a whole workgroup with coalesced 16-byte loads
 //   selection               the exact top-k of those -> D / I or keys, exactly as the fp32 search writes them
 //   gated fp32 search       state reset, scan, selection of the plain search, each returning at once unless some query's
 //                           flag is set -- then it overwrites the output with the plain search's bits
@@ -4164,8 +4214,10 @@ static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, 
     f16.qexp = qexp;
     int rc = search_view(h, (const float *)q16, nullptr, nq, kp, id_base, 1, vshift, 0, ao, false, s, reset_flag, f16);
     if (rc) return rc;
-    hipLaunchKernelGGL(rescore16_kernel, dim3((unsigned)nq), dim3(256), (size_t)h->dp * 4, s, (const uint64_t *)h->ws_s16ak.p, kp, k, Bq, pfail, rfail,
-                       h->xb, h->dp, q_dev, id_base, (uint64_t *)h->ws_s16ok.p, sstat);
+    const size_t rlds = rescore16_lds(h->dp);
+    HIP_TRY(hipFuncSetAttribute((const void *)rescore16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); // (above 64 KB from dp = 1024 on)
+    hipLaunchKernelGGL(rescore16_kernel, dim3((unsigned)nq, (unsigned)((kp + RS16_ROWS - 1) / RS16_ROWS)), dim3(256), rlds, s, (const uint64_t *)h->ws_s16ak.p,
+                       kp, k, Bq, pfail, rfail, h->xb, h->dp, q_dev, id_base, (uint64_t *)h->ws_s16ok.p, sstat);
     HIP_TRY(hipGetLastError());
     SelectParams sp = {};
     sp.in = (const uint64_t *)h->ws_s16ok.p; sp.in_stride = kp; sp.n_fixed = kp; sp.cap = kp; sp.n_expect = kp;

@@ -264,7 +264,7 @@ static bool s16_eligible(const PlanCtx &c, int pass_mode, int64_t nb, int64_t nq
     if (pass_mode || level != 0 || row_mul != 1) return false;
     if (c.metric != KNN_METRIC_INNER_PRODUCT || c.approx16 || (c.flags & KNN_TUNE_NO_SCAN16)) return false;
     if (nq < 1 || nq > 32 || (c.force_qt != 0 && c.force_qt != 32) || s16_kprime(k) <= k) return false; // (k' = k: no room for a window)
-    if ((size_t)dp * 4 + 64 > 65536) return false; // (rescore16_kernel holds the query in LDS, no opt-in beyond 64 KB)
+    if ((size_t)dp * 4 + 64 > 65536) return false; // (the widest row the path has served: rescore16_kernel walks a row in 1024-float slabs, its LDS does not grow with dp)
     return nb >= (1 << 18) || (c.flags & KNN_TUNE_SCAN16_ANY_NB);
 }
 
