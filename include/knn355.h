@@ -235,7 +235,8 @@ int64_t knn_hnsw_ntotal(knn_hnsw_handle h);
 knn_handle knn_hnsw_storage(knn_hnsw_handle h);
 void knn_hnsw_free(knn_hnsw_handle h);
 /* graph tables for write_index / read_index: levels[n], offsets[n+1], nbrs[nslots]
- * (-1 = empty), cum_nb[nlevels_tab] (slots below each level), assign_probas */
+ * (-1 = empty), cum_nb[nlevels_tab] (slots below each level), assign_probas.  A list ends at its
+ * first -1 (FAISS's walk stops there): what an imported level-0 list holds behind one is dropped */
 int knn_hnsw_graph_sizes(knn_hnsw_handle h, int64_t *ntotal, int64_t *nslots, int32_t *nlevels_tab);
 int knn_hnsw_graph_export(knn_hnsw_handle h, int32_t *levels, int64_t *offsets, int32_t *nbrs,
                           int32_t *cum_nb, double *assign_probas);

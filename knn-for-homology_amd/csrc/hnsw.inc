@@ -2669,12 +2669,17 @@ extern "C" int knn_hnsw_graph_import(knn_hnsw_s *H, int64_t ntotal, const int32_
         }
         g.nbrs[i] = nbrs[i] < 0 ? HNSW_EMPTY : (uint32_t)nbrs[i];
     }
-    for (int64_t i = 0; i < ntotal; i++) { // (an imported list may have holes: the fill is the position of the first one)
-        const uint32_t *l = g.list(i, 0);
+    // (an imported list may have holes: the fill is the position of the first one, as in FAISS, whose walk stops at the
+    // first -1.  What lies behind it is not part of the list and is dropped here: the device beam reads a level-0 list as
+    // one whole row and tells links from empty slots by value, so ids left behind a hole would be walked on the device and
+    // not on the host)
+    for (int64_t i = 0; i < ntotal; i++) {
+        uint32_t *l = g.list(i, 0);
         const int cap = g.nb_neighbors(0);
         int have = 0;
         while (have < cap && l[have] != HNSW_EMPTY) have++;
         g.cnt0[i] = (uint8_t)have;
+        for (int c = have; c < cap; c++) l[c] = HNSW_EMPTY;
     }
     // the walk starts at (entry_point, max_level): both must describe a node of this graph
     const bool empty_ok = ntotal == 0 && entry_point == -1;

@@ -258,14 +258,31 @@ int orc_flat_search(const float *xb, int64_t nb, const float *xq, int64_t nq, in
 
 /*
  * Distances for explicit (query, row) pairs -- the HNSW candidate path.
- * out[p] = IP: <q,y>;  L2: max(0, nrm(q)+nrm(y)-2<q,y>)
+ * out[p] = IP: <q,y>;  L2: max(0, nrm(q)+nrm(y)-2<q,y>), or under orc_set_l2_mode(2) the difference form (one chain,
+ * acc = fmaf(t, t, acc), t = q[k] - y[k], k in the dot product's order) -- what the HNSW index returns at every batch size
  */
+static float orc_l2_diff(const float *x, const float *y, int d)
+{
+    float acc = 0.0f;
+    for (int k0 = 0; k0 < d; k0 += 8)
+        for (int j = 0; j < 8; j++) {
+            const int k = k0 + P8[j];
+            const float t = k < d ? x[k] - y[k] : 0.0f;
+            acc = fmaf(t, t, acc);
+        }
+    return acc + 0.0f;
+}
+
 void orc_pair_distances(const float *xb, const float *xq, int d, int metric, int64_t npairs,
                         const int64_t *qidx, const int64_t *ridx, float *out)
 {
 #pragma omp parallel for schedule(static)
     for (int64_t p = 0; p < npairs; p++) {
         const float *q = xq + qidx[p] * (int64_t)d, *y = xb + ridx[p] * (int64_t)d;
+        if (metric == ORC_METRIC_L2 && g_l2_mode == 2) {
+            out[p] = orc_l2_diff(q, y, d);
+            continue;
+        }
         float ip = orc_dot(q, y, d);
         if (metric == ORC_METRIC_INNER_PRODUCT) out[p] = ip;
         else {

@@ -111,7 +111,15 @@ class Oracle:
             raise RuntimeError("orc_flat_search failed")
         return D, I
 
-    def pair_distances(self, xb, xq, qidx, ridx, metric):
+    def pair_distances(self, xb, xq, qidx, ridx, metric, l2_mode: int = 0):
+        """l2_mode 2: squared L2 as the sum of squared differences (the HNSW index's formula); otherwise the norm formula"""
+        self.lib.orc_set_l2_mode(int(l2_mode))
+        try:
+            return self._pair_distances(xb, xq, qidx, ridx, metric)
+        finally:
+            self.lib.orc_set_l2_mode(0)
+
+    def _pair_distances(self, xb, xq, qidx, ridx, metric):
         xb, bp = self._f32(xb)
         xq, qp = self._f32(xq)
         qidx = np.ascontiguousarray(qidx, np.int64)

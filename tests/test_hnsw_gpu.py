@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from hnsw_reference import assert_output_contract
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +47,7 @@ def test_fixture_exact_when_ef_exceeds_ntotal(gpu_faiss, oracle):
 
 
 @pytest.mark.parametrize("metric", [0, 1])
-def test_recall_and_distance_bits(gpu_faiss, metric):
+def test_recall_and_distance_bits(gpu_faiss, oracle, metric):
     n, d, nq = 20000, 256, 1000
     x = _clustered(n, d, 200, 21)
     gpu_faiss.normalize_L2(x)
@@ -69,6 +70,7 @@ def test_recall_and_distance_bits(gpu_faiss, metric):
         for j, v in zip(I[qi].tolist(), D[qi].view(np.uint32).tolist()):
             if j in ref:
                 assert ref[j] == v
+    assert_output_contract(D, I, x, x[:nq], metric, n, oracle)
     # order: best first, ties by id
     if metric == 0:
         assert (np.diff(D, axis=1) <= 0).all()
@@ -83,7 +85,7 @@ def test_recall_and_distance_bits(gpu_faiss, metric):
 
 
 @pytest.mark.parametrize("metric", [0, 1])
-def test_entry_modes_and_host_walk_agree_in_quality(gpu_faiss, metric, monkeypatch):
+def test_entry_modes_and_host_walk_agree_in_quality(gpu_faiss, oracle, metric, monkeypatch):
     """Three ways to walk the same graph: coarse exact entry scan + device beam (default), greedy descent + device beam
     (set_entry(0)), and the host beam of round 1.  All return flat-exact distances for the rows they find and reach the
     same recall within two points; the default must not be the worst."""
@@ -110,12 +112,13 @@ def test_entry_modes_and_host_walk_agree_in_quality(gpu_faiss, metric, monkeypat
             for j, v in zip(I[r].tolist(), D[r].view(np.uint32).tolist()):
                 if j in ref[r]:
                     assert ref[r][j] == v
+        assert_output_contract(D, I, x, x[:nq], metric, n, oracle)
         assert (np.diff(D, axis=1) <= 0).all() if metric == 0 else (np.diff(D, axis=1) >= 0).all()
     assert rec["coarse"] >= 0.95 and rec["coarse"] >= rec["descent"] - 0.02, rec
 
 
 @pytest.mark.parametrize("d", [128, 100])
-def test_bf16_coarse_scan_matches_fp32_coarse_scan_in_quality(gpu_faiss, d, monkeypatch):
+def test_bf16_coarse_scan_matches_fp32_coarse_scan_in_quality(gpu_faiss, oracle, d, monkeypatch):
     """The coarse entry scan multiplies bf16 copies of the rows above level 0 (entry points only need the neighbourhood;
     the beam's rows are re-scored in fp32).  Same graph quality and recall as the fp32 coarse scan
     (KNN355_HNSW_COARSE_FP32=1), distances still flat-exact; d = 100 exercises the padding to 64 values."""
@@ -138,10 +141,11 @@ def test_bf16_coarse_scan_matches_fp32_coarse_scan_in_quality(gpu_faiss, d, monk
             for j, v in zip(I[r].tolist(), D[r].view(np.uint32).tolist()):
                 if j in ref:
                     assert ref[j] == v
+        assert_output_contract(D, I, x, x[:nq], 0, n, oracle)
     assert rec["bf16"] >= 0.95 and abs(rec["bf16"] - rec["fp32"]) <= 0.01, rec
 
 
-def test_rows_wider_than_the_device_beam_use_the_host_walk(gpu_faiss):
+def test_rows_wider_than_the_device_beam_use_the_host_walk(gpu_faiss, oracle):
     """The device beam serves rows of up to 1024 floats; wider embeddings (ESM-1b: 1280) fall back to the host walk with
     GPU distance batches -- same contract (flat-exact distances, -1 padding), recall against the flat search."""
     n, d, nq, k = 4000, 1280, 200, 20
@@ -160,6 +164,7 @@ def test_rows_wider_than_the_device_beam_use_the_host_walk(gpu_faiss):
         for j, v in zip(I[r].tolist(), D[r].view(np.uint32).tolist()):
             if j in ref:
                 assert ref[j] == v
+    assert_output_contract(D, I, x, x[:nq], 0, n, oracle)
 
 
 def test_add_dev_builds_the_same_graph(gpu_faiss):
@@ -491,7 +496,7 @@ def test_quality_matches_sequential_oracle(gpu_faiss, ko, metric):
         assert r_gpu >= r_ref - 0.02, (efs, r_gpu, r_ref)
 
 
-def test_bf16_beam_matches_fp32_beam_in_quality(gpu_faiss, monkeypatch):
+def test_bf16_beam_matches_fp32_beam_in_quality(gpu_faiss, oracle, monkeypatch):
     """The level-0 beam walks on bf16 copies of the rows (default) or on the fp32 rows (KNN355_HNSW_BEAM_FP32=1): same
     recall within half a point, and in both every returned distance is the flat search's value for that pair."""
     n, d, nq, k = 30000, 256, 800, 50
@@ -513,6 +518,7 @@ def test_bf16_beam_matches_fp32_beam_in_quality(gpu_faiss, monkeypatch):
             for j, v in zip(I[r].tolist(), D[r].view(np.uint32).tolist()):
                 if j in ref:
                     assert ref[j] == v
+        assert_output_contract(D, I, x, x[:nq], 0, n, oracle)
     assert rec["bf16"] >= 0.95 and abs(rec["bf16"] - rec["fp32"]) <= 0.005, rec
 
 
