@@ -313,24 +313,32 @@ int knn_lsh_search_refine(knn_lsh_handle base, knn_handle flat, const float *q_h
 int knn_last_refine_ms(knn_handle h, float *rescore_ms, float *select_ms);
 
 /* ---- consumers of (hits, scores): SURVEY section 8(f) N4 --------------------------
- * Host buffers in and out.  hits are int64 [nq][k] as returned by search. */
+ * Host buffers in and out.  hits are int64 [nq][k] as returned by search.  k > INT32_MAX is KNN_ERR_INVALID
+ * for all four.  Every KNN_ERR_INVALID is returned before anything is allocated or launched on the device,
+ * with the output buffers untouched.  Rows go through the device in slabs of 256 MiB of hits
+ * (KNN355_EVAL_SLAB_ROWS, a positive integer, sets the rows per slab instead: tests). */
 /* pfam/proteins.py:85-122 remove_self_hit: drops the self id from each row (or the last
  * hit when the row does not contain it: missing_out[r] = 1); outputs are [nq][k-1] */
 int knn_eval_remove_self_hit(const int64_t *hits, const float *scores, int64_t nq, int64_t k,
                              const int64_t *self_ids, int64_t *hits_out, float *scores_out,
                              int32_t *missing_out);
 /* seqvec_search/main.py:64-82 evaluate: lead_out[r] = hits of the query's label before the
- * first foreign hit, tp_out[r] = hits of the query's label anywhere; is_correct_out
+ * first foreign hit, tp_out[r] = hits of the query's label anywhere; a hit < 0 or >= nb matches
+ * nothing (labels_db may be NULL when nb is 0); is_correct_out
  * (uint8 [nq][k], may be NULL) is the per-hit match matrix of seqvec_search/tp_cumulative.py */
 int knn_eval_labels(const int64_t *hits, int64_t nq, int64_t k, const int32_t *labels_q,
                     const int32_t *labels_db, int64_t nb, uint8_t *is_correct_out, int32_t *lead_out,
                     int32_t *tp_out);
 /* pfam/proteins_shared.py:139-157 compute_auc1: query r is homologous to the SORTED target
- * rows set_members[set_offsets[r] .. set_offsets[r+1]) */
+ * rows set_members[set_offsets[r] .. set_offsets[r+1]); lead_out / tp_out as for knn_eval_labels.
+ * set_offsets [nq + 1]; set_members may be NULL when set_offsets[nq] is 0.  KNN_ERR_INVALID when
+ * set_offsets[0] < 0, when set_offsets[r+1] < set_offsets[r] for some r, or when the members of one
+ * set are not non-decreasing (all checked on the host before the device sees them) */
 int knn_eval_sets(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set_offsets,
                   const int64_t *set_members, int32_t *lead_out, int32_t *tp_out);
 /* cath/cath.py:76-84 compute_is_correct: out uint8 [nq][nlevels][k],
- * out[q][l][j] = mapping[query_rows[q]][l] == mapping[hits[q][j]][l]; mapping int32 [n][nlevels] */
+ * out[q][l][j] = mapping[query_rows[q]][l] == mapping[hits[q][j]][l]; mapping int32 [n][nlevels];
+ * a hit < 0 or >= n is 0 at every level; a query row outside [0, n) is KNN_ERR_INVALID */
 int knn_eval_levels(const int64_t *hits, int64_t nq, int64_t k, const int64_t *query_rows,
                     const int32_t *mapping, int64_t n, int32_t nlevels, uint8_t *out);
 

@@ -6,6 +6,8 @@
 // seqvec_search/tp_cumulative.py:15-34).  At 200k queries x 1000 hits these loops dominate the
 // wall time after the search.  Here each is one pass of integer work over hits[nq][k]: one wave
 // per row, coalesced reads of the row, gathers into small label tables.
+#include <errno.h>
+#include <stdlib.h>
 
 // out row = in row with the element at `index` removed; index = position of the self id
 // (0 when the search put it first), or k-1 when the row does not contain it (counted missing)
@@ -125,12 +127,27 @@ struct EvalBufs {
     type var = (type)bufs.get(bytes);                                                   \
     if (!var) return set_err(KNN_ERR_HIP, "eval: out of device memory")
 
-static int64_t eval_slab_rows(int64_t k) { return std::max<int64_t>(1, (int64_t)(256ull << 20) / (k * 8)); }
+// rows per slab: 256 MiB of hits.  KNN355_EVAL_SLAB_ROWS (read on every call; a positive decimal integer, anything else
+// is ignored) replaces the count, so that a test crosses slab boundaries with a handful of rows
+static int64_t eval_slab_rows(int64_t k)
+{
+    const char *e = getenv("KNN355_EVAL_SLAB_ROWS");
+    if (e && *e >= '0' && *e <= '9') {
+        char *end = nullptr;
+        errno = 0;
+        const long long v = strtoll(e, &end, 10);
+        if (errno == 0 && *end == '\0' && v > 0) return (int64_t)v;
+    }
+    return std::max<int64_t>(1, (int64_t)(256ull << 20) / (k * 8));
+}
+// the kernels take k as int
+static bool eval_k_too_large(int64_t k) { return k > (int64_t)INT32_MAX; }
 
 extern "C" int knn_eval_remove_self_hit(const int64_t *hits, const float *scores, int64_t nq, int64_t k, const int64_t *self_ids,
                                         int64_t *hits_out, float *scores_out, int32_t *missing_out)
 {
     if (nq < 0 || k < 2) return set_err(KNN_ERR_INVALID, "remove_self_hit: need k >= 2");
+    if (eval_k_too_large(k)) return set_err(KNN_ERR_INVALID, "remove_self_hit: k > INT32_MAX");
     if (nq == 0) return 0;
     if (!hits || !scores || !self_ids || !hits_out || !scores_out || !missing_out) return set_err(KNN_ERR_INVALID, "remove_self_hit: null pointer");
     int rc = ensure_device(g_device);
@@ -161,6 +178,7 @@ extern "C" int knn_eval_labels(const int64_t *hits, int64_t nq, int64_t k, const
                                int64_t nb, uint8_t *is_correct_out, int32_t *lead_out, int32_t *tp_out)
 {
     if (nq < 0 || k < 1 || nb < 0) return set_err(KNN_ERR_INVALID, "eval_labels: bad shape");
+    if (eval_k_too_large(k)) return set_err(KNN_ERR_INVALID, "eval_labels: k > INT32_MAX");
     if (nq == 0) return 0;
     if (!hits || !labels_q || (!labels_db && nb > 0) || !lead_out || !tp_out) return set_err(KNN_ERR_INVALID, "eval_labels: null pointer");
     int rc = ensure_device(g_device);
@@ -192,10 +210,18 @@ extern "C" int knn_eval_sets(const int64_t *hits, int64_t nq, int64_t k, const i
                              int32_t *lead_out, int32_t *tp_out)
 {
     if (nq < 0 || k < 1) return set_err(KNN_ERR_INVALID, "eval_sets: bad shape");
+    if (eval_k_too_large(k)) return set_err(KNN_ERR_INVALID, "eval_sets: k > INT32_MAX");
     if (nq == 0) return 0;
     if (!hits || !set_offsets || !lead_out || !tp_out) return set_err(KNN_ERR_INVALID, "eval_sets: null pointer");
+    // the kernel binary-searches set_members[set_offsets[r] .. set_offsets[r+1]) without further checks
+    if (set_offsets[0] < 0) return set_err(KNN_ERR_INVALID, "eval_sets: negative set offset");
+    for (int64_t r = 0; r < nq; r++)
+        if (set_offsets[r + 1] < set_offsets[r]) return set_err(KNN_ERR_INVALID, "eval_sets: set offsets decrease");
     const int64_t nmem = set_offsets[nq];
     if (nmem > 0 && !set_members) return set_err(KNN_ERR_INVALID, "eval_sets: null pointer");
+    for (int64_t r = 0; r < nq; r++)
+        for (int64_t i = set_offsets[r] + 1; i < set_offsets[r + 1]; i++)
+            if (set_members[i] < set_members[i - 1]) return set_err(KNN_ERR_INVALID, "eval_sets: set members not sorted");
     int rc = ensure_device(g_device);
     if (rc) return rc;
     EvalBufs bufs;
@@ -222,6 +248,7 @@ extern "C" int knn_eval_levels(const int64_t *hits, int64_t nq, int64_t k, const
                                int64_t n, int32_t nlevels, uint8_t *out)
 {
     if (nq < 0 || k < 1 || n < 1 || nlevels < 1) return set_err(KNN_ERR_INVALID, "eval_levels: bad shape");
+    if (eval_k_too_large(k)) return set_err(KNN_ERR_INVALID, "eval_levels: k > INT32_MAX");
     if (nq == 0) return 0;
     if (!hits || !query_rows || !mapping || !out) return set_err(KNN_ERR_INVALID, "eval_levels: null pointer");
     for (int64_t i = 0; i < nq; i++)

@@ -23,13 +23,25 @@ def _hits(h):
     return h
 
 
+def _per_query(a, dtype, nq, name):
+    """The library reads nq entries through a raw pointer: a shorter array would be read past its end."""
+    a = np.ascontiguousarray(a, dtype)
+    if a.shape != (nq,):
+        raise ValueError(f"{name} must have shape ({nq},), one entry per row of hits, not {a.shape}")
+    return a
+
+
 def remove_self_hit(hits: ndarray, scores: ndarray, self_ids: ndarray = None) -> Tuple[ndarray, ndarray]:
     """Removes the self hit from every row even when an approximate search did not put it
     first; rows that do not contain their own id lose their last hit instead."""
     hits = _hits(hits)
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     nq, k = hits.shape
-    self_ids = np.arange(nq, dtype=np.int64) if self_ids is None else np.ascontiguousarray(self_ids, np.int64)
+    if scores.shape != hits.shape:
+        raise ValueError(f"scores {scores.shape} and hits {hits.shape} must have the same shape")
+    if k < 2:
+        raise ValueError("remove_self_hit needs k >= 2")
+    self_ids = np.arange(nq, dtype=np.int64) if self_ids is None else _per_query(self_ids, np.int64, nq, "self_ids")
     print(f"Fixing {int((hits[:, 0] != self_ids).sum())} misplaced self hits")
     ho = np.empty((nq, k - 1), np.int64)
     so = np.empty((nq, k - 1), np.float32)
@@ -44,8 +56,10 @@ def label_matches(hits: ndarray, labels_q: ndarray, labels_db: ndarray, want_mat
     """(is_correct bool [nq,k] or None, leading-run length int32 [nq], match count int32 [nq])"""
     hits = _hits(hits)
     nq, k = hits.shape
-    lq = np.ascontiguousarray(labels_q, np.int32)
+    lq = _per_query(labels_q, np.int32, nq, "labels_q")
     ldb = np.ascontiguousarray(labels_db, np.int32)
+    if ldb.ndim != 1:
+        raise ValueError("labels_db must be 1-D")
     ic = np.empty((nq, k), np.uint8) if want_matrix else None
     lead = np.empty(nq, np.int32)
     tp = np.empty(nq, np.int32)
@@ -111,7 +125,7 @@ def compute_is_correct(results: ndarray, mapping_array: ndarray, query_rows: nda
     codes = np.empty(mapping.shape, np.int32)
     for l in range(mapping.shape[1]):
         _, codes[:, l] = np.unique(mapping[:, l], return_inverse=True)
-    qrows = np.arange(nq, dtype=np.int64) if query_rows is None else np.ascontiguousarray(query_rows, np.int64)
+    qrows = np.arange(nq, dtype=np.int64) if query_rows is None else _per_query(query_rows, np.int64, nq, "query_rows")
     out = np.empty((nq, mapping.shape[1], k), np.uint8)
     _lib.check(_lib.lib().knn_eval_levels(results.ctypes.data, nq, k, qrows.ctypes.data, codes.ctypes.data,
                                           mapping.shape[0], mapping.shape[1], out.ctypes.data))
