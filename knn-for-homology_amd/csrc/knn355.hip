@@ -1019,6 +1019,34 @@ __device__ __forceinline__ void sched_spread()
     }
 }
 
+// Pass 1 of flat_scan_kernel's sparse epilogue: ONE asm statement for four scores, put together from pieces.  A head leaves
+// the values in t0..t3 (accumulators in AGPRs or VGPRs, squared L2 or inner product); a bound leaves the compare masks in
+// m0..m3 (THR: the query's threshold; ROW, the second direction: each row's own, -inf for a lane whose query is no candidate);
+// the tail is every build's: slot address and pointer bump, score number, store.  The operand lists follow the pieces (in_l2
+// and out_bound may be empty), so a build names only what its text uses.  All of them name locals of pass1.
+#define KNN_P1_HEAD_AGPR_L2 "v_accvgpr_read_b32 %[t0], %[a0]\n\t" "v_accvgpr_read_b32 %[t1], %[a1]\n\t" "v_accvgpr_read_b32 %[t2], %[a2]\n\t" "v_accvgpr_read_b32 %[t3], %[a3]\n\t" \
+    "v_fma_f32 %[t0], %[t0], -2.0, %[s0]\n\t" "v_fma_f32 %[t1], %[t1], -2.0, %[s1]\n\t" "v_fma_f32 %[t2], %[t2], -2.0, %[s2]\n\t" "v_fma_f32 %[t3], %[t3], -2.0, %[s3]\n\t"
+#define KNN_P1_HEAD_AGPR_IP "v_accvgpr_read_b32 %[t0], %[a0]\n\t" "v_accvgpr_read_b32 %[t1], %[a1]\n\t" "v_accvgpr_read_b32 %[t2], %[a2]\n\t" "v_accvgpr_read_b32 %[t3], %[a3]\n\t" \
+    "v_xor_b32_e32 %[t0], 0x80000000, %[t0]\n\t" "v_xor_b32_e32 %[t1], 0x80000000, %[t1]\n\t" "v_xor_b32_e32 %[t2], 0x80000000, %[t2]\n\t" "v_xor_b32_e32 %[t3], 0x80000000, %[t3]\n\t"
+#define KNN_P1_HEAD_VGPR_L2 "v_fma_f32 %[t0], %[a0], -2.0, %[s0]\n\t" "v_fma_f32 %[t1], %[a1], -2.0, %[s1]\n\t" "v_fma_f32 %[t2], %[a2], -2.0, %[s2]\n\t" "v_fma_f32 %[t3], %[a3], -2.0, %[s3]\n\t" // (the 128 x 128 tile's accumulators are VGPRs: read in place)
+#define KNN_P1_HEAD_VGPR_IP "v_xor_b32_e32 %[t0], 0x80000000, %[a0]\n\t" "v_xor_b32_e32 %[t1], 0x80000000, %[a1]\n\t" "v_xor_b32_e32 %[t2], 0x80000000, %[a2]\n\t" "v_xor_b32_e32 %[t3], 0x80000000, %[a3]\n\t"
+#define KNN_P1_BOUND_THR "v_cmp_le_f32_e64 %[m0], %[t0], %[thr]\n\t" "v_cmp_le_f32_e64 %[m1], %[t1], %[thr]\n\t" "v_cmp_le_f32_e64 %[m2], %[t2], %[thr]\n\t" "v_cmp_le_f32_e64 %[m3], %[t3], %[thr]\n\t"
+#define KNN_P1_BOUND_ROW "v_cndmask_b32_e64 %[e0], %[ninf], %[h0], %[cok]\n\t" "v_cndmask_b32_e64 %[e1], %[ninf], %[h1], %[cok]\n\t" "v_cndmask_b32_e64 %[e2], %[ninf], %[h2], %[cok]\n\t" "v_cndmask_b32_e64 %[e3], %[ninf], %[h3], %[cok]\n\t" \
+    "v_cmp_le_f32_e64 %[m0], %[t0], %[e0]\n\t" "v_cmp_le_f32_e64 %[m1], %[t1], %[e1]\n\t" "v_cmp_le_f32_e64 %[m2], %[t2], %[e2]\n\t" "v_cmp_le_f32_e64 %[m3], %[t3], %[e3]\n\t"
+#define KNN_P1_TAIL "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t" "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t" "v_add_u32_e32 %[w], %[w], %[u]\n\t" \
+    "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t" "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t" "v_add_u32_e32 %[w], %[w], %[u]\n\t" \
+    "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t" "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t" "v_add_u32_e32 %[w], %[w], %[u]\n\t" \
+    "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t" "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t" "v_add_u32_e32 %[w], %[w], %[u]\n\t" \
+    "v_mov_b32_e32 %[i0], %[idx0]\n\t" "v_mov_b32_e32 %[i1], %[idx1]\n\t" "v_mov_b32_e32 %[i2], %[idx2]\n\t" "v_mov_b32_e32 %[i3], %[idx3]\n\t" \
+    "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t" "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t" "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t" "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
+#define KNN_P1_OUT_ROW , [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3])
+#define KNN_P1_IN_L2 , [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3)
+#define KNN_P1_IN_THR , [thr] "v"(thr[b])
+#define KNN_P1_IN_ROW , [h0] "v"(t2l[sc - c + 0]), [h1] "v"(t2l[sc - c + 1]), [h2] "v"(t2l[sc - c + 2]), [h3] "v"(t2l[sc - c + 3]), [ninf] "v"(ninf), [cok] "s"(cokm[b])
+#define KNN_PASS1(head, bound, out_bound, acc_reg, in_l2, in_bound) asm volatile(head bound KNN_P1_TAIL \
+    : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w) out_bound \
+    : [a0] acc_reg(a0), [a1] acc_reg(a1), [a2] acc_reg(a2), [a3] acc_reg(a3) in_l2 in_bound, [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8)) : "memory")
+
 // WM x WN waves; each wave owns TM x TN MFMA tiles of 32(db rows) x 32(queries)
 // NTDB: the launch has ONE query tile, so every database row is read by exactly one workgroup:
 // its staging loads are non-temporal and do not displace the queries (re-read by every workgroup
@@ -1793,10 +1821,8 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 return -accv(b, s);
             }
         };
-        // threshold filter + append of one tile's scores (getv(a, b, r, xnq): from the accumulators, or read back from
-        // the deferred first tile)
-        // Threshold filter + append of one tile's scores.  passes(a, b, r, thr, xnq): does the score beat thr; value(a, b, r,
-        // xnq): the score -- from the accumulators, or read back from the parked first tile.
+        // Threshold filter + append of one tile's scores.  passes(b, sc, thr, xnq): does score sc of query block b beat thr;
+        // value(b, sc, xnq): the score -- from the accumulators, or read back from the parked first tile.
         //   This code runs beside the OTHER resident workgroup's K loop, whose MFMAs own the SIMD's issue port: per-workgroup
         // stamps of a CATH-sized search showed the filter of round 2 (~45 vector instructions per score: row numbers, view
         // and sample-mask arithmetic in 64 bits, the key, then a divergent append with its own LDS round trip) taking 15-60 us
@@ -1959,8 +1985,6 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
         // slots hands the whole tile's second direction to the dense code below.
         bool dir2_dense = SYM && off_diag; // the second direction is (still) the dense code's
         auto sparse_epilogue = [&](int64_t trow0, bool second, auto *dense2) { // (generic: only the 256 x 256 builds instantiate it)
-            // slots per lane and tile, first / second direction (+ a dump slot each), all inside staging buffer 1: buffer 0 is
-            // taking the next tile's first K step meanwhile
             // Slots per lane and tile (+ a dump slot).  256 x 256 tile: inside staging buffer 1 (buffer 0 is taking the next tile's
             // first K step meanwhile); 128 x 128 tile: both of its 32-KB staging buffers are idle during the epilogue, the
             // symmetric build adds 8 KB (lds_main).  The symmetric launch's two directions use the SAME slots, one after the
@@ -1982,6 +2006,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
             const uint32_t dump = w_0 + C * 2048, step = 2048;
             const float ninf = -INFINITY;
             uint32_t w = w_0;                                        // ... of its next slot (counts on past the last)
+            auto slot_at = [&](int j) -> char * { return smem + OFF1 + (j * 256 + tid) * 8; }; // this lane's slot j (j <= C), as a pointer
             uint32_t nblk[NB] = {};                                  // first direction: 2048 x this lane's survivors of each query block
             KNN_TRACE_AT(tile_idx == 5, 125);
             if constexpr (BIGT) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); // (the K loop's last MFMAs -> v_accvgpr_read inside the statements below)
@@ -2019,300 +2044,16 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                             const float a0 = accv(b, sc), a1 = accv(b, sc + 1), a2 = accv(b, sc + 2), a3 = accv(b, sc + 3);
                             const float s0 = xnq[b] + ynl[sc - c], s1 = xnq[b] + ynl[sc - c + 1], s2 = xnq[b] + ynl[sc - c + 2], s3 = xnq[b] + ynl[sc - c + 3];
                             (void)s0; (void)s1; (void)s2; (void)s3;
-                            if constexpr (DIR == 1) {
-                                if constexpr (BIGT && L2) {
-                                    asm volatile("v_accvgpr_read_b32 %[t0], %[a0]\n\t"
-                                             "v_accvgpr_read_b32 %[t1], %[a1]\n\t"
-                                             "v_accvgpr_read_b32 %[t2], %[a2]\n\t"
-                                             "v_accvgpr_read_b32 %[t3], %[a3]\n\t"
-                                             "v_fma_f32 %[t0], %[t0], -2.0, %[s0]\n\t"
-                                             "v_fma_f32 %[t1], %[t1], -2.0, %[s1]\n\t"
-                                             "v_fma_f32 %[t2], %[t2], -2.0, %[s2]\n\t"
-                                             "v_fma_f32 %[t3], %[t3], -2.0, %[s3]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[thr]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w)
-                                             : [a0] "a"(a0), [a1] "a"(a1), [a2] "a"(a2), [a3] "a"(a3), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [thr] "v"(thr[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                } else if constexpr (BIGT) {
-                                    asm volatile("v_accvgpr_read_b32 %[t0], %[a0]\n\t"
-                                             "v_accvgpr_read_b32 %[t1], %[a1]\n\t"
-                                             "v_accvgpr_read_b32 %[t2], %[a2]\n\t"
-                                             "v_accvgpr_read_b32 %[t3], %[a3]\n\t"
-                                             "v_xor_b32_e32 %[t0], 0x80000000, %[t0]\n\t"
-                                             "v_xor_b32_e32 %[t1], 0x80000000, %[t1]\n\t"
-                                             "v_xor_b32_e32 %[t2], 0x80000000, %[t2]\n\t"
-                                             "v_xor_b32_e32 %[t3], 0x80000000, %[t3]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[thr]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w)
-                                             : [a0] "a"(a0), [a1] "a"(a1), [a2] "a"(a2), [a3] "a"(a3), [thr] "v"(thr[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                } else if constexpr (L2) { // (the 128 x 128 tile's accumulators are VGPRs: read in place)
-                                    asm volatile("v_fma_f32 %[t0], %[a0], -2.0, %[s0]\n\t"
-                                             "v_fma_f32 %[t1], %[a1], -2.0, %[s1]\n\t"
-                                             "v_fma_f32 %[t2], %[a2], -2.0, %[s2]\n\t"
-                                             "v_fma_f32 %[t3], %[a3], -2.0, %[s3]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[thr]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w)
-                                             : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [thr] "v"(thr[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                } else {
-                                    asm volatile("v_xor_b32_e32 %[t0], 0x80000000, %[a0]\n\t"
-                                             "v_xor_b32_e32 %[t1], 0x80000000, %[a1]\n\t"
-                                             "v_xor_b32_e32 %[t2], 0x80000000, %[a2]\n\t"
-                                             "v_xor_b32_e32 %[t3], 0x80000000, %[a3]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[thr]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[thr]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w)
-                                             : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [thr] "v"(thr[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                }
-                            } else { // (the second direction: the same values decide for rows rowl(sc ..) as queries; a lane whose own query is no
-                                     // candidate -- past the end, or a row of the sample -- compares against -inf)
-                                if constexpr (BIGT && L2) {
-                                    asm volatile("v_accvgpr_read_b32 %[t0], %[a0]\n\t"
-                                             "v_accvgpr_read_b32 %[t1], %[a1]\n\t"
-                                             "v_accvgpr_read_b32 %[t2], %[a2]\n\t"
-                                             "v_accvgpr_read_b32 %[t3], %[a3]\n\t"
-                                             "v_fma_f32 %[t0], %[t0], -2.0, %[s0]\n\t"
-                                             "v_fma_f32 %[t1], %[t1], -2.0, %[s1]\n\t"
-                                             "v_fma_f32 %[t2], %[t2], -2.0, %[s2]\n\t"
-                                             "v_fma_f32 %[t3], %[t3], -2.0, %[s3]\n\t"
-                                             "v_cndmask_b32_e64 %[e0], %[ninf], %[h0], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e1], %[ninf], %[h1], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e2], %[ninf], %[h2], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e3], %[ninf], %[h3], %[cok]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[e0]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[e1]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[e2]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[e3]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w), [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3])
-                                             : [a0] "a"(a0), [a1] "a"(a1), [a2] "a"(a2), [a3] "a"(a3), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [h0] "v"(t2l[sc - c + 0]), [h1] "v"(t2l[sc - c + 1]), [h2] "v"(t2l[sc - c + 2]), [h3] "v"(t2l[sc - c + 3]), [ninf] "v"(ninf), [cok] "s"(cokm[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                } else if constexpr (BIGT) {
-                                    asm volatile("v_accvgpr_read_b32 %[t0], %[a0]\n\t"
-                                             "v_accvgpr_read_b32 %[t1], %[a1]\n\t"
-                                             "v_accvgpr_read_b32 %[t2], %[a2]\n\t"
-                                             "v_accvgpr_read_b32 %[t3], %[a3]\n\t"
-                                             "v_xor_b32_e32 %[t0], 0x80000000, %[t0]\n\t"
-                                             "v_xor_b32_e32 %[t1], 0x80000000, %[t1]\n\t"
-                                             "v_xor_b32_e32 %[t2], 0x80000000, %[t2]\n\t"
-                                             "v_xor_b32_e32 %[t3], 0x80000000, %[t3]\n\t"
-                                             "v_cndmask_b32_e64 %[e0], %[ninf], %[h0], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e1], %[ninf], %[h1], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e2], %[ninf], %[h2], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e3], %[ninf], %[h3], %[cok]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[e0]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[e1]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[e2]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[e3]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w), [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3])
-                                             : [a0] "a"(a0), [a1] "a"(a1), [a2] "a"(a2), [a3] "a"(a3), [h0] "v"(t2l[sc - c + 0]), [h1] "v"(t2l[sc - c + 1]), [h2] "v"(t2l[sc - c + 2]), [h3] "v"(t2l[sc - c + 3]), [ninf] "v"(ninf), [cok] "s"(cokm[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                } else if constexpr (L2) { // (the 128 x 128 tile's accumulators are VGPRs: read in place)
-                                    asm volatile("v_fma_f32 %[t0], %[a0], -2.0, %[s0]\n\t"
-                                             "v_fma_f32 %[t1], %[a1], -2.0, %[s1]\n\t"
-                                             "v_fma_f32 %[t2], %[a2], -2.0, %[s2]\n\t"
-                                             "v_fma_f32 %[t3], %[a3], -2.0, %[s3]\n\t"
-                                             "v_cndmask_b32_e64 %[e0], %[ninf], %[h0], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e1], %[ninf], %[h1], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e2], %[ninf], %[h2], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e3], %[ninf], %[h3], %[cok]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[e0]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[e1]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[e2]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[e3]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w), [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3])
-                                             : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [s0] "v"(s0), [s1] "v"(s1), [s2] "v"(s2), [s3] "v"(s3), [h0] "v"(t2l[sc - c + 0]), [h1] "v"(t2l[sc - c + 1]), [h2] "v"(t2l[sc - c + 2]), [h3] "v"(t2l[sc - c + 3]), [ninf] "v"(ninf), [cok] "s"(cokm[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                } else {
-                                    asm volatile("v_xor_b32_e32 %[t0], 0x80000000, %[a0]\n\t"
-                                             "v_xor_b32_e32 %[t1], 0x80000000, %[a1]\n\t"
-                                             "v_xor_b32_e32 %[t2], 0x80000000, %[a2]\n\t"
-                                             "v_xor_b32_e32 %[t3], 0x80000000, %[a3]\n\t"
-                                             "v_cndmask_b32_e64 %[e0], %[ninf], %[h0], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e1], %[ninf], %[h1], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e2], %[ninf], %[h2], %[cok]\n\t"
-                                             "v_cndmask_b32_e64 %[e3], %[ninf], %[h3], %[cok]\n\t"
-                                             "v_cmp_le_f32_e64 %[m0], %[t0], %[e0]\n\t"
-                                             "v_cmp_le_f32_e64 %[m1], %[t1], %[e1]\n\t"
-                                             "v_cmp_le_f32_e64 %[m2], %[t2], %[e2]\n\t"
-                                             "v_cmp_le_f32_e64 %[m3], %[t3], %[e3]\n\t"
-                                             "v_min_u32_e32 %[ad0], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m0]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad1], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m1]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad2], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m2]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_min_u32_e32 %[ad3], %[w], %[dump]\n\t"
-                                             "v_cndmask_b32_e64 %[u], 0, %[step], %[m3]\n\t"
-                                             "v_add_u32_e32 %[w], %[w], %[u]\n\t"
-                                             "v_mov_b32_e32 %[i0], %[idx0]\n\t"
-                                             "v_mov_b32_e32 %[i1], %[idx1]\n\t"
-                                             "v_mov_b32_e32 %[i2], %[idx2]\n\t"
-                                             "v_mov_b32_e32 %[i3], %[idx3]\n\t"
-                                             "ds_write2_b32 %[ad0], %[t0], %[i0] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad1], %[t1], %[i1] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad2], %[t2], %[i2] offset1:1\n\t"
-                                             "ds_write2_b32 %[ad3], %[t3], %[i3] offset1:1"
-                                             : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [ad0] "=&v"(ad[0]), [ad1] "=&v"(ad[1]), [ad2] "=&v"(ad[2]), [ad3] "=&v"(ad[3]), [i0] "=&v"(ix[0]), [i1] "=&v"(ix[1]), [i2] "=&v"(ix[2]), [i3] "=&v"(ix[3]), [m0] "=&s"(mk[0]), [m1] "=&s"(mk[1]), [m2] "=&s"(mk[2]), [m3] "=&s"(mk[3]), [u] "=&v"(u), [w] "+v"(w), [e0] "=&v"(e[0]), [e1] "=&v"(e[1]), [e2] "=&v"(e[2]), [e3] "=&v"(e[3])
-                                             : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [h0] "v"(t2l[sc - c + 0]), [h1] "v"(t2l[sc - c + 1]), [h2] "v"(t2l[sc - c + 2]), [h3] "v"(t2l[sc - c + 3]), [ninf] "v"(ninf), [cok] "s"(cokm[b]), [dump] "v"(dump), [step] "v"(step), [idx0] "n"((sc + 0) | (b << 8)), [idx1] "n"((sc + 1) | (b << 8)), [idx2] "n"((sc + 2) | (b << 8)), [idx3] "n"((sc + 3) | (b << 8))
-                                             : "memory");
-                                }
-                            }
+                            // (the second direction: the same values decide for rows rowl(sc ..) as queries; a lane whose own query is no candidate --
+                            // past the end, or a row of the sample -- compares against -inf)
+                            if constexpr (DIR == 1 && BIGT && L2) KNN_PASS1(KNN_P1_HEAD_AGPR_L2, KNN_P1_BOUND_THR, , "a", KNN_P1_IN_L2, KNN_P1_IN_THR);
+                            else if constexpr (DIR == 1 && BIGT) KNN_PASS1(KNN_P1_HEAD_AGPR_IP, KNN_P1_BOUND_THR, , "a", , KNN_P1_IN_THR);
+                            else if constexpr (DIR == 1 && L2) KNN_PASS1(KNN_P1_HEAD_VGPR_L2, KNN_P1_BOUND_THR, , "v", KNN_P1_IN_L2, KNN_P1_IN_THR);
+                            else if constexpr (DIR == 1) KNN_PASS1(KNN_P1_HEAD_VGPR_IP, KNN_P1_BOUND_THR, , "v", , KNN_P1_IN_THR);
+                            else if constexpr (BIGT && L2) KNN_PASS1(KNN_P1_HEAD_AGPR_L2, KNN_P1_BOUND_ROW, KNN_P1_OUT_ROW, "a", KNN_P1_IN_L2, KNN_P1_IN_ROW);
+                            else if constexpr (BIGT) KNN_PASS1(KNN_P1_HEAD_AGPR_IP, KNN_P1_BOUND_ROW, KNN_P1_OUT_ROW, "a", , KNN_P1_IN_ROW);
+                            else if constexpr (L2) KNN_PASS1(KNN_P1_HEAD_VGPR_L2, KNN_P1_BOUND_ROW, KNN_P1_OUT_ROW, "v", KNN_P1_IN_L2, KNN_P1_IN_ROW);
+                            else KNN_PASS1(KNN_P1_HEAD_VGPR_IP, KNN_P1_BOUND_ROW, KNN_P1_OUT_ROW, "v", , KNN_P1_IN_ROW);
                         }
                         if constexpr (DIR == 1) nblk[b] += w - w_b;
                     }
@@ -2342,7 +2083,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 int base[NB], run[NB];
                 uint2 e[U1];
 #pragma unroll
-                for (int u = 0; u < U1; u++) e[u] = *(const uint2 *)(smem + OFF1 + (min(u, C) * 256 + tid) * 8);
+                for (int u = 0; u < U1; u++) e[u] = *(const uint2 *)slot_at(min(u, C));
 #pragma unroll
                 for (int b = 0; b < NB; b++) {
                     const int cnt = (int)(nblk[b] >> 11);
@@ -2374,7 +2115,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                     j0 += U1;
                     if (__ballot(j0 < n1) == 0ull) break;
 #pragma unroll
-                    for (int u = 0; u < U1; u++) e[u] = *(const uint2 *)(smem + OFF1 + (min(j0 + u, C) * 256 + tid) * 8);
+                    for (int u = 0; u < U1; u++) e[u] = *(const uint2 *)slot_at(min(j0 + u, C));
                 }
                 if (near_full) *L.s_need = 1;
             }
@@ -2405,7 +2146,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 uint2 g[U2];
                 int rk[U2];
 #pragma unroll
-                for (int u = 0; u < U2; u++) g[u] = *(const uint2 *)(smem + OFF1 + (min(u, C) * 256 + tid) * 8);
+                for (int u = 0; u < U2; u++) g[u] = *(const uint2 *)slot_at(min(u, C));
 #pragma unroll
                 for (int u = 0; u < U2; u++) rk[u] = atomicAdd(&s_cnt2[rowl((int)(g[u].y & 63u))], u < n2 ? 1 : 0);
                 for (int j0 = U2; j0 < n2; j0 += 4) { // (the entries past the registers: rank written back into the slot)
@@ -2413,7 +2154,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                     int r4[4];
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
-                        yp[u] = (uint32_t *)(smem + OFF1 + (min(j0 + u, C) * 256 + tid) * 8 + 4);
+                        yp[u] = (uint32_t *)(slot_at(min(j0 + u, C)) + 4);
                         y[u] = *yp[u];
                     }
 #pragma unroll
@@ -2453,7 +2194,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 for (int u = 0; u < U2; u++)
                     if (u < n2) put(__uint_as_float(g[u].x), (int)(g[u].y & 255u), (int)((g[u].y >> 8) & 3u), bs[u] + rk[u]);
                 for (int j = U2; j < n2; j++) {
-                    const uint2 e = *(const uint2 *)(smem + OFF1 + (j * 256 + tid) * 8);
+                    const uint2 e = *(const uint2 *)slot_at(j);
                     const int sc = (int)(e.y & 255u);
                     put(__uint_as_float(e.x), sc, (int)((e.y >> 8) & 3u), s_base2[rowl(sc)] + (int)(e.y >> 16));
                 }
@@ -2602,6 +2343,18 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
     lists_flush<QT>(L, s_base, q0, p.nq, p.qlist, p.qcnt, p.qcap, tid, SYM ? p.fail : nullptr);
     KNN_TRACE(63);
 }
+#undef KNN_P1_HEAD_AGPR_L2
+#undef KNN_P1_HEAD_AGPR_IP
+#undef KNN_P1_HEAD_VGPR_L2
+#undef KNN_P1_HEAD_VGPR_IP
+#undef KNN_P1_BOUND_THR
+#undef KNN_P1_BOUND_ROW
+#undef KNN_P1_TAIL
+#undef KNN_P1_OUT_ROW
+#undef KNN_P1_IN_L2
+#undef KNN_P1_IN_THR
+#undef KNN_P1_IN_ROW
+#undef KNN_PASS1
 
 // ---------------------------------------------------------------------------
 // final selection: one workgroup per query picks the best k of that query's candidate keys,
