@@ -213,7 +213,9 @@ int knn_sharded_search_dev(knn_handle h, knn_comm c, const float *q_dev, int64_t
  * Results use the flat index's layout; slots the walk could not fill hold id -1. */
 typedef struct knn_hnsw_s *knn_hnsw_handle;
 int knn_hnsw_create(int32_t d, int32_t M, int32_t metric, knn_hnsw_handle *out);
-/* index.hnsw.efSearch / index.hnsw.efConstruction (values <= 0 leave the setting alone) */
+/* index.hnsw.efSearch / index.hnsw.efConstruction (values <= 0 leave the setting alone).  efConstruction is the
+ * width of the beam that collects a new row's candidates (up to 1024 on the device, host walkers above); the
+ * closest 127 of them, by the walk's key, take part in the neighbour selection */
 int knn_hnsw_set_ef(knn_hnsw_handle h, int32_t efSearch, int32_t efConstruction);
 /* walk tuning (not in faiss): candidates expanded per walker per lock-step round (default 8;
  * 1 = strict best-first) and walkers / inserted rows per batch (default 16384); values <= 0 keep the setting */

@@ -1549,7 +1549,10 @@ extern "C" int knn_hnsw_set_ef(knn_hnsw_s *H, int32_t efSearch, int32_t efConstr
     if (!H) return set_err(KNN_ERR_INVALID, "hnsw_set_ef: null handle");
     std::lock_guard<std::mutex> lk(H->mu);
     if (efSearch > 0) H->efSearch = efSearch;
-    if (efConstruction > 0) H->efConstruction = std::min(efConstruction, SHRINK_MAX_MEMBERS - 1);
+    // efConstruction is the width of the construction beam, as in FAISS, and is kept as given.  The closest
+    // SHRINK_MAX_MEMBERS - 1 of the beam's candidates, by the walk's key, take part in the selection; above 1024 the device
+    // beam is off and host walkers link the rows (hnsw_insert_batch).
+    if (efConstruction > 0) H->efConstruction = efConstruction;
     return 0;
 }
 
