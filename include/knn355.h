@@ -118,14 +118,17 @@ int knn_flat_normalize_rows(knn_handle h);
 int knn_flat_view(knn_handle parent, knn_handle *out);
 /* per-shard result as packed sortable keys (uint64: order-preserving score
  * bits << 32 | id_base + local row), k per query, ascending = best first,
- * padded with UINT64_MAX.  This is what ranks exchange (RCCL all-gather). */
+ * padded with UINT64_MAX.  This is what ranks exchange (RCCL all-gather).
+ * The id is 32 bits wide: id_base + ntotal must not exceed 2^32 (the last row's id is then at
+ * most 0xFFFFFFFF); a larger sum is refused with KNN_ERR_INVALID before anything is launched. */
 int knn_flat_search_keys_dev(knn_handle h, const float *q_dev, int64_t nq, int64_t k,
                              uint32_t id_base, uint64_t *keys_dev, void *stream);
 /* merges nlists key lists per query ([nlists][nq][k], e.g. an all-gather
  * buffer) into final D/I on h's device, in h's metric: ONE selection launch that reads the
  * buffer in place whatever nlists * k is -- no scratch memory, nothing of h is written (h
  * supplies the device and the metric only), so merges issued through different handles or
- * streams cannot interfere */
+ * streams cannot interfere.  The keys of one query are distinct (every list draws its ids from
+ * its own range); the result is unspecified for duplicate keys. */
 int knn_merge_keys_dev(knn_handle h, const uint64_t *keys_dev, int32_t nlists, int64_t nq, int64_t k,
                        float *D_dev, int64_t *I_dev, void *stream);
 /* ---- index.range_search(x, radius) (FAISS's other flat-index query) ----------
@@ -180,6 +183,8 @@ void knn_free(knn_handle h);
  * communicators.  A rank whose local scan fails still enters the all-gather with "no rows" so
  * that its peers do not deadlock, and returns its error: a failure on ANY rank is a failure of
  * the search -- exchange the return codes before trusting a result.
+ * Global ids are 32 bits wide: a rank whose id_base + ntotal exceeds 2^32 fails in exactly that way
+ * (KNN_ERR_INVALID from its local scan, after the all-gather it entered with "no rows").
  * Bounded waits: knn_comm_create gives a peer KNN355_COMM_TIMEOUT_S seconds (environment; default 120) to
  * arrive, the synchronous form of knn_sharded_search_dev (stream == NULL) gives the search the same time to
  * complete; both return KNN_ERR_TIMEOUT with the rank named in knn_last_error() instead of hanging, and the

@@ -4238,6 +4238,11 @@ static int search_dev_impl(knn_index_s *h, const float *q_dev, int64_t nq, int k
                            uint64_t *keys_dev, uint32_t id_base, bool allow_stat, hipStream_t s)
 {
     if (nq == 0) return 0;
+    // packed keys carry id_base + row in 32 bits: a shard whose ids would wrap is refused before anything is launched (a
+    // wrapped id collides with or sorts in front of another shard's, and the merge takes keys to be distinct)
+    if (keys_dev && (uint64_t)id_base + (uint64_t)h->ntotal > (1ull << 32))
+        return set_err(KNN_ERR_INVALID, "search_keys: id_base " + std::to_string(id_base) + " + ntotal " + std::to_string(h->ntotal) +
+                                            " exceeds 2^32: ids are 32 bits wide in the packed keys");
     const int64_t total = nq * k;
     if (h->ntotal == 0) {
         hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, h->metric, keys_dev, D_dev, I_dev);

@@ -117,7 +117,11 @@ class HipShardBackend:
     # the three device steps; `index` picks the lane, the launches go to torch's CURRENT stream
     def search_keys(self, q: torch.Tensor, k: int, id_base: int, index=None, out=None) -> torch.Tensor:
         """k packed keys per query; ``out``: a contiguous [nq, k] int64 tensor to write them into (the front of the
-        all-gather's send buffer)"""
+        all-gather's send buffer).  Ids are 32 bits wide in the keys: ``id_base + ntotal`` must not exceed 2^32 (the
+        library refuses a larger sum; an ``id_base`` outside [0, 2^32) is refused here, ctypes would wrap it)"""
+        id_base = int(id_base)
+        if not 0 <= id_base < 1 << 32:
+            raise ValueError(f"search_keys: id_base {id_base} is outside [0, 2^32): ids are 32 bits wide in the packed keys")
         nq = q.shape[0]
         keys = out if out is not None else torch.empty((nq, k), dtype=torch.int64, device=q.device)
         assert keys.is_contiguous() and keys.shape == (nq, k) and keys.dtype == torch.int64

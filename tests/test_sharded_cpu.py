@@ -13,18 +13,10 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT / "tests") not in sys.path:
+    sys.path.insert(0, str(ROOT / "tests"))
 
-
-def _f2ord(v):
-    u = np.ascontiguousarray(v, np.float32).view(np.uint32).astype(np.uint64)
-    neg = (u & 0x80000000) != 0
-    return np.where(neg, (~u) & 0xFFFFFFFF, u | 0x80000000)
-
-
-def _ord2f(o):
-    o = o.astype(np.uint64)
-    u = np.where((o & 0x80000000) != 0, o & 0x7FFFFFFF, (~o) & 0xFFFFFFFF).astype(np.uint32)
-    return u.view(np.float32)
+from merge_reference import f2ord as _f2ord, ord2f as _ord2f  # noqa: E402
 
 
 class OracleShardBackend:
