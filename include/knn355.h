@@ -321,7 +321,7 @@ int knn_last_refine_ms(knn_handle h, float *rescore_ms, float *select_ms);
 
 /* ---- consumers of (hits, scores): SURVEY section 8(f) N4 --------------------------
  * Host buffers in and out.  hits are int64 [nq][k] as returned by search.  k > INT32_MAX is KNN_ERR_INVALID
- * for all four.  Every KNN_ERR_INVALID is returned before anything is allocated or launched on the device,
+ * for all five.  Every KNN_ERR_INVALID is returned before anything is allocated or launched on the device,
  * with the output buffers untouched.  Rows go through the device in slabs of 256 MiB of hits
  * (KNN355_EVAL_SLAB_ROWS, a positive integer, sets the rows per slab instead: tests). */
 /* pfam/proteins.py:85-122 remove_self_hit: drops the self id from each row (or the last
@@ -348,6 +348,36 @@ int knn_eval_sets(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set
  * a hit < 0 or >= n is 0 at every level; a query row outside [0, n) is KNN_ERR_INVALID */
 int knn_eval_levels(const int64_t *hits, int64_t nq, int64_t k, const int64_t *query_rows,
                     const int32_t *mapping, int64_t n, int32_t nlevels, uint8_t *out);
+/* pfam/slices/slices.py:256-291 assemble: protein-level hits from a search over slices (fixed-length windows of
+ * proteins; pfam/slices/slices_search.py).  hits / scores are [ns][k] as the slice search returned them; the k hits
+ * of a row need not be sorted.  Query group g (a protein) owns the rows [group_offsets[g], group_offsets[g+1])
+ * (group_offsets [ng + 1]); row_group[h] (int32 [nb]) is the group of database slice row h.  Per group:
+ *   entries   its (score, hit) pairs, entry p = (r - group_offsets[g]) * k + j for cell j of row r
+ *   order     ascending = 0: a before b when score_a > score_b; equal scores by smaller p; +0.0 and -0.0 are equal;
+ *             NaN scores behind every other score, by p among themselves.  ascending = 1 mirrors the comparison
+ *             (smaller scores first; ties and NaNs as before).  This is numpy.argsort(-scores) (slices.py:274) with
+ *             its unspecified order among equal scores fixed to the stable one, and nothing else added.
+ *   depth     only the first `depth` entries of that order are looked at (the reference: depth = k, slices.py:279)
+ *   walk      those entries in order: one whose hit is < 0 or >= nb keeps its place in the order (it counts toward
+ *             depth) but names no group, and neither does one whose row_group value is negative; one whose group is
+ *             self_group[g] (int32 [ng]; NULL: no exclusion) is skipped; one whose group was already emitted for g is
+ *             skipped; every other one is emitted: its group to groups_out, its score (the input's bits) to
+ *             scores_out, and, where given, its row of hits (0 .. ns - 1) to qrow_out and its hit id to hit_out.
+ *             The walk stops after k_out emissions.  (The reference indexes its slice table with the raw hit, so a
+ *             hit of -1 wraps to the table's last slice there: that is not reproduced.)
+ *   padding   unfilled slots: group -1, score -FLT_MAX (ascending: +FLT_MAX), -1 in qrow_out / hit_out, as the flat
+ *             search pads; a group without rows is all padding.
+ * Outputs are [ng][k_out].  KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched:
+ * ns, ng or nb < 0; k < 1 or k > INT32_MAX; depth < 1 or depth > KNN_MAX_K; k_out < 1 or k_out > depth; a null
+ * required pointer (row_group may be NULL when nb is 0, hits / scores when ns is 0); group_offsets[0] < 0, decreasing
+ * offsets, group_offsets[ng] > ns; a group with rows * k >= 2^31.  ng = 0 returns 0.  Slabs (see above) are cut at
+ * group boundaries and always take one whole group at least; row_group is uploaded once.
+ * Hot path: assemble_kernel (assemble.inc), one workgroup per group: selection of the best depth keys in LDS, group
+ * lookup and de-duplication in rank order, ballot-and-prefix compaction. */
+int knn_eval_assemble(const int64_t *hits, const float *scores, int64_t ns, int64_t k,
+                      const int64_t *group_offsets, int64_t ng, const int32_t *row_group, int64_t nb,
+                      const int32_t *self_group, int32_t depth, int32_t k_out, int32_t ascending,
+                      int64_t *groups_out, float *scores_out, int64_t *qrow_out, int64_t *hit_out);
 
 /* ---- MMseqs2 prefilter database: SURVEY section 8(f) N3 ----------------------------
  * seqvec_search/mmseqs/_write_prefilter_db.py:52-97 write_prefilter_db: data file

@@ -25,6 +25,7 @@
 //   merge_select_kernel  one wave per (query, group of lists): exact top-k of <= 4096 keys,
 //                        last round sorts and writes D / I.
 //   hnsw.inc / lsh.inc / eval.inc   IndexHNSWFlat, IndexLSH, consumers of (hits, scores).
+//   assemble.inc                    protein-level hits from slice searches (knn_eval_assemble).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
 #include <hip/hip_runtime.h>
 #include <thread>
@@ -5374,4 +5375,5 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "refine.inc"
 #include "lsh.inc"
 #include "eval.inc"
+#include "assemble.inc"
 #include "range.inc"

@@ -6,8 +6,12 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   compute_auc1            pfam/proteins_shared.py:139-157 (sets of homologous proteins)
   compute_is_correct      cath/cath.py:76-84 (C/A/T/H level matrix)
   compute_tps_comulative  seqvec_search/tp_cumulative.py:15-34
+  assemble                pfam/slices/slices.py:256-291 (protein-level hits from slice hits; also run over the
+                          MMseqs2 slice hits, slices.py:312-314)
+  auc1_assembled          pfam/slices/slices.py:294-305
 """
 from collections import Counter
+from itertools import groupby
 from typing import Dict, List, Sequence, Set, Tuple
 
 import numpy as np
@@ -130,3 +134,92 @@ def compute_is_correct(results: ndarray, mapping_array: ndarray, query_rows: nda
     _lib.check(_lib.lib().knn_eval_levels(results.ctypes.data, nq, k, qrows.ctypes.data, codes.ctypes.data,
                                           mapping.shape[0], mapping.shape[1], out.ctypes.data))
     return out.astype(bool)
+
+
+def assemble_grouping(slice_proteins: Sequence[str], db_proteins: Sequence[str] = None):
+    """The integer tables knn_eval_assemble takes, from protein names per slice row.
+
+    -> (group_offsets int64 [ng + 1], protein_names [ng], row_group int32 [nb], self_group int32 [ng], id_to_name)
+
+    Query side: runs of consecutive equal names in slice_proteins are the groups (the reference's groupby,
+    pfam/slices/slices.py:261), so a name that comes back after another one opens a second query group.  Database side:
+    ids go by NAME, in order of first appearance in db_proteins (default: slice_proteins, the self-search), because the
+    reference's `picked` set holds names; id_to_name[i] is the name of id i.  self_group[g] is the database id of query
+    group g's name, -1 when the database does not hold it."""
+    slice_proteins = list(slice_proteins)
+    db_proteins = slice_proteins if db_proteins is None else list(db_proteins)
+    name_to_id = {}
+    for name in db_proteins:
+        name_to_id.setdefault(name, len(name_to_id))
+    row_group = np.fromiter((name_to_id[name] for name in db_proteins), np.int32, len(db_proteins))
+    protein_names, offsets = [], [0]
+    for name, run in groupby(slice_proteins):
+        protein_names.append(name)
+        offsets.append(offsets[-1] + sum(1 for _ in run))
+    self_group = np.fromiter((name_to_id.get(name, -1) for name in protein_names), np.int32, len(protein_names))
+    return np.asarray(offsets, np.int64), protein_names, row_group, self_group, list(name_to_id)
+
+
+def assemble(slices_hits: ndarray, slices_scores: ndarray, slice_proteins: Sequence[str], db_proteins: Sequence[str] = None,
+             depth: int = None, k_out: int = None, ascending: bool = False, exclude_self: bool = False,
+             want_sources: bool = False):
+    """Protein-level hits from the hits of a search over slices (pfam/slices/slices.py:256-291), one GPU pass.
+
+    slice_proteins[r] is the protein of query slice row r, db_proteins[h] the protein of database slice row h (default:
+    the same list).  Per query protein: the hits of all its slices, best score first (ascending=True: smallest first,
+    for e-values; equal scores in input order), cut at depth (default k, as the reference), walked once ignoring hits
+    whose protein was already picked -- and, with exclude_self, the query protein itself -- up to k_out (default k; depth when that is smaller).
+    -> (groups int64 [ng, k_out] (ids of assemble_grouping's id_to_name, -1 = unfilled), scores float32 [ng, k_out],
+    protein_names [ng]) and, with want_sources, qrow and hit int64 [ng, k_out]: the row of slices_hits and the hit id
+    each output came from."""
+    hits = _hits(slices_hits)
+    scores = np.ascontiguousarray(slices_scores, dtype=np.float32)
+    ns, k = hits.shape
+    if scores.shape != hits.shape:
+        raise ValueError(f"scores {scores.shape} and hits {hits.shape} must have the same shape")
+    if len(slice_proteins) != ns:
+        raise ValueError(f"slice_proteins must name one protein per row of hits ({ns}), not {len(slice_proteins)}")
+    offsets, protein_names, row_group, self_group, _ = assemble_grouping(slice_proteins, db_proteins)
+    depth = k if depth is None else int(depth)
+    k_out = min(k, depth) if k_out is None else int(k_out)
+    ng = len(protein_names)
+    groups = np.empty((ng, k_out), np.int64)
+    out_scores = np.empty((ng, k_out), np.float32)
+    qrow = np.empty((ng, k_out), np.int64) if want_sources else None
+    hit = np.empty((ng, k_out), np.int64) if want_sources else None
+    _lib.check(_lib.lib().knn_eval_assemble(hits.ctypes.data, scores.ctypes.data, ns, k, offsets.ctypes.data, ng,
+                                            row_group.ctypes.data if row_group.size else None, row_group.shape[0],
+                                            self_group.ctypes.data if exclude_self else None, depth, k_out, 1 if ascending else 0,
+                                            groups.ctypes.data, out_scores.ctypes.data,
+                                            qrow.ctypes.data if want_sources else None, hit.ctypes.data if want_sources else None))
+    if want_sources:
+        return groups, out_scores, protein_names, qrow, hit
+    return groups, out_scores, protein_names
+
+
+def auc1_assembled(groups: ndarray, protein_names: Sequence[str], homologous_proteins: Dict[str, Set[str]],
+                   id_to_name: Sequence[str]) -> ndarray:
+    """pfam/slices/slices.py:294-305: the leading run of correct proteins of every assembled row over the number of
+    homologous proteins (an empty set divides by 1, as compute_auc1 does; the reference would divide by zero).  The run
+    is knn_eval_sets' leading-run count over the group ids: its binary search finds no -1 among the (non-negative)
+    members, so the padding ends a run like any other miss."""
+    groups = _hits(groups)
+    ng, k_out = groups.shape
+    if len(protein_names) != ng:
+        raise ValueError(f"protein_names must name one protein per row of groups ({ng}), not {len(protein_names)}")
+    name_to_id = {name: i for i, name in enumerate(id_to_name)}
+    offsets = np.zeros(ng + 1, np.int64)
+    members = []
+    sizes = np.empty(ng, np.int64)
+    for g in range(ng):
+        allc = homologous_proteins[protein_names[g]]
+        sizes[g] = max(len(allc), 1)
+        members.extend(sorted(name_to_id[t] for t in allc if t in name_to_id))
+        offsets[g + 1] = len(members)
+    members = np.asarray(members, np.int64)
+    lead = np.empty(ng, np.int32)
+    tp = np.empty(ng, np.int32)
+    if ng and k_out:
+        _lib.check(_lib.lib().knn_eval_sets(groups.ctypes.data, ng, k_out, offsets.ctypes.data,
+                                            members.ctypes.data if members.size else None, lead.ctypes.data, tp.ctypes.data))
+    return lead / sizes
