@@ -321,7 +321,7 @@ int knn_last_refine_ms(knn_handle h, float *rescore_ms, float *select_ms);
 
 /* ---- consumers of (hits, scores): SURVEY section 8(f) N4 --------------------------
  * Host buffers in and out.  hits are int64 [nq][k] as returned by search.  k > INT32_MAX is KNN_ERR_INVALID
- * for all five.  Every KNN_ERR_INVALID is returned before anything is allocated or launched on the device,
+ * for all of them.  Every KNN_ERR_INVALID is returned before anything is allocated or launched on the device,
  * with the output buffers untouched.  Rows go through the device in slabs of 256 MiB of hits
  * (KNN355_EVAL_SLAB_ROWS, a positive integer, sets the rows per slab instead: tests). */
 /* pfam/proteins.py:85-122 remove_self_hit: drops the self id from each row (or the last
@@ -378,6 +378,43 @@ int knn_eval_assemble(const int64_t *hits, const float *scores, int64_t ns, int6
                       const int64_t *group_offsets, int64_t ng, const int32_t *row_group, int64_t nb,
                       const int32_t *self_group, int32_t depth, int32_t k_out, int32_t ascending,
                       int64_t *groups_out, float *scores_out, int64_t *qrow_out, int64_t *hit_out);
+/* pfam/proteins.py:201-207 compute_correctness_array: the per-hit membership matrix of knn_eval_sets' sets.
+ * Arguments, argument checks, slabs and edge cases are knn_eval_sets' (members sorted per set, checked on the host;
+ * nq = 0 returns 0); is_correct_out (uint8 [nq][k], required) gets 1 where hits[r][j] is a member of set r, else 0:
+ * a hit that is in no set, a negative one included, gives 0. */
+int knn_eval_sets_matrix(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set_offsets,
+                         const int64_t *set_members, uint8_t *is_correct_out);
+/* pfam/proteins.py:626-648, the precision-recall sweep: mean precision and mean recall per query at each of nthr score
+ * thresholds.  is_correct (uint8) and scores are [nq][k], totals [nq] (the number of homologues of each query),
+ * thresholds [nthr]; every output is [nthr].
+ *   cells       only columns 0 .. limit-1 of each row are read (1 <= limit <= k); a cell is correct when its
+ *               is_correct byte is non-zero
+ *   selection   cell (q, c) is selected at threshold j when (double)scores[q][c] > thresholds[j]: a strict comparison in
+ *               double, as numpy compares a float32 array with a float64 scalar.  A NaN score is never selected; +-inf
+ *               scores and thresholds follow the comparison.
+ *   thresholds  non-decreasing and free of NaN; equal neighbours are legal (quantiles of tied scores).  With that,
+ *               "selected at j" is j < #{i : thresholds[i] < (double)s}: one binary search per cell.
+ *   per query   n = number of selected cells, tp = number of selected correct cells;
+ *               P(q,j) = n ? (double)tp / (double)n : 1.0 ("no prediction, no error", proteins.py:641);
+ *               R(q,j) = (double)tp / (double)totals[q]; both divisions IEEE double, correctly rounded
+ *   integers    selected_out[j] = sum over q of n, tp_out[j] = sum over q of tp, empty_out[j] = number of queries with
+ *               n = 0 (any of the three may be NULL)
+ *   means       precision_out[j] = S_P(j) / (double)nq and recall_out[j] = S_R(j) / (double)nq, the sums taken in one
+ *               stated order, so that the result is one defined double whatever the launch shape and the slab size:
+ *               queries form blocks of 256 consecutive rows by global row index; a block's sum starts at +0.0 and adds
+ *               its queries' terms in row order; S starts at +0.0 and adds the block sums in block order.  (No
+ *               floating-point atomics, no tree whose shape depends on the grid.)
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: nq < 1 (a mean over
+ * nothing); k < 1, k > INT32_MAX, limit < 1, limit > k; nthr < 1 or nthr > 4096; a null required pointer (precision_out
+ * and recall_out are required); totals[q] < 1 for some q; a decreasing or NaN threshold.
+ * Slabs: as above, but the rows per slab (KNN355_EVAL_SLAB_ROWS included) are rounded up to a multiple of 256, so that
+ * blocks never straddle slabs; pr_fold_kernel adds a slab's block sums to the running S in block order.
+ * Hot path: pr_curve_kernel (pr_curve.inc), one workgroup per block of 256 queries: per query a histogram over the
+ * thresholds in LDS, a workgroup-wide suffix scan, one division per threshold into per-thread accumulators. */
+int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores, int64_t nq, int64_t k, int64_t limit,
+                      const int64_t *totals, const double *thresholds, int32_t nthr,
+                      double *precision_out, double *recall_out,
+                      int64_t *selected_out, int64_t *tp_out, int64_t *empty_out);
 
 /* ---- MMseqs2 prefilter database: SURVEY section 8(f) N3 ----------------------------
  * seqvec_search/mmseqs/_write_prefilter_db.py:52-97 write_prefilter_db: data file

@@ -64,9 +64,12 @@ __global__ void label_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, 
 }
 
 // set-membership evaluation (pfam/proteins_shared.py:139-157): query r is homologous to the
-// sorted target rows members[offsets[r] .. offsets[r+1])
+// sorted target rows members[offsets[r] .. offsets[r+1]).  MATRIX: the per-hit membership bytes
+// (pfam/proteins.py:201-207 compute_correctness_array) instead of the leading run and the count
+template <bool MATRIX>
 __global__ void set_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, int k, const int64_t *__restrict__ offsets,
-                                const int64_t *__restrict__ members, int32_t *__restrict__ lead, int32_t *__restrict__ tp)
+                                const int64_t *__restrict__ members, int32_t *__restrict__ lead, int32_t *__restrict__ tp,
+                                uint8_t *__restrict__ is_correct)
 {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -81,9 +84,14 @@ __global__ void set_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, in
             if (members[mid] < hid) lo = mid + 1; else hi = mid;
         }
         const bool ok = lo < hi0 && members[lo] == hid;
+        if (MATRIX) {
+            is_correct[r * k + j] = ok ? 1 : 0;
+            continue;
+        }
         cnt += ok ? 1 : 0;
         if (!ok) first_bad = min(first_bad, j);
     }
+    if (MATRIX) return;
     for (int off = 32; off >= 1; off >>= 1) {
         cnt += __shfl_xor(cnt, off, 64);
         first_bad = min(first_bad, __shfl_xor(first_bad, off, 64));
@@ -206,13 +214,14 @@ extern "C" int knn_eval_labels(const int64_t *hits, int64_t nq, int64_t k, const
     return 0;
 }
 
-extern "C" int knn_eval_sets(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set_offsets, const int64_t *set_members,
-                             int32_t *lead_out, int32_t *tp_out)
+// knn_eval_sets (lead_out, tp_out) and knn_eval_sets_matrix (is_correct_out): one set of checks, one slab walk
+static int eval_sets_run(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set_offsets, const int64_t *set_members,
+                         int32_t *lead_out, int32_t *tp_out, uint8_t *is_correct_out, bool matrix)
 {
     if (nq < 0 || k < 1) return set_err(KNN_ERR_INVALID, "eval_sets: bad shape");
     if (eval_k_too_large(k)) return set_err(KNN_ERR_INVALID, "eval_sets: k > INT32_MAX");
     if (nq == 0) return 0;
-    if (!hits || !set_offsets || !lead_out || !tp_out) return set_err(KNN_ERR_INVALID, "eval_sets: null pointer");
+    if (!hits || !set_offsets || (matrix ? !is_correct_out : (!lead_out || !tp_out))) return set_err(KNN_ERR_INVALID, "eval_sets: null pointer");
     // the kernel binary-searches set_members[set_offsets[r] .. set_offsets[r+1]) without further checks
     if (set_offsets[0] < 0) return set_err(KNN_ERR_INVALID, "eval_sets: negative set offset");
     for (int64_t r = 0; r < nq; r++)
@@ -229,19 +238,40 @@ extern "C" int knn_eval_sets(const int64_t *hits, int64_t nq, int64_t k, const i
     EVAL_ALLOC(d_h, int64_t *, (size_t)slab * k * 8);
     EVAL_ALLOC(d_off, int64_t *, (size_t)(nq + 1) * 8);
     EVAL_ALLOC(d_mem, int64_t *, (size_t)nmem * 8);
-    EVAL_ALLOC(d_lead, int32_t *, (size_t)slab * 4);
-    EVAL_ALLOC(d_tp, int32_t *, (size_t)slab * 4);
+    EVAL_ALLOC(d_lead, int32_t *, matrix ? 0 : (size_t)slab * 4);
+    EVAL_ALLOC(d_tp, int32_t *, matrix ? 0 : (size_t)slab * 4);
+    EVAL_ALLOC(d_ic, uint8_t *, matrix ? (size_t)slab * k : 0);
     HIP_TRY(hipMemcpy(d_off, set_offsets, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice));
     if (nmem) HIP_TRY(hipMemcpy(d_mem, set_members, (size_t)nmem * 8, hipMemcpyHostToDevice));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
         HIP_TRY(hipMemcpy(d_h, hits + r0 * k, (size_t)m * k * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(set_eval_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_off + r0, d_mem, d_lead, d_tp);
+        if (matrix) {
+            hipLaunchKernelGGL(set_eval_kernel<true>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_off + r0, d_mem,
+                               d_lead, d_tp, d_ic);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(is_correct_out + r0 * k, d_ic, (size_t)m * k, hipMemcpyDeviceToHost));
+            continue;
+        }
+        hipLaunchKernelGGL(set_eval_kernel<false>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_off + r0, d_mem,
+                           d_lead, d_tp, d_ic);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(lead_out + r0, d_lead, (size_t)m * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(tp_out + r0, d_tp, (size_t)m * 4, hipMemcpyDeviceToHost));
     }
     return 0;
+}
+
+extern "C" int knn_eval_sets(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set_offsets, const int64_t *set_members,
+                             int32_t *lead_out, int32_t *tp_out)
+{
+    return eval_sets_run(hits, nq, k, set_offsets, set_members, lead_out, tp_out, nullptr, false);
+}
+
+extern "C" int knn_eval_sets_matrix(const int64_t *hits, int64_t nq, int64_t k, const int64_t *set_offsets,
+                                    const int64_t *set_members, uint8_t *is_correct_out)
+{
+    return eval_sets_run(hits, nq, k, set_offsets, set_members, nullptr, nullptr, is_correct_out, true);
 }
 
 extern "C" int knn_eval_levels(const int64_t *hits, int64_t nq, int64_t k, const int64_t *query_rows, const int32_t *mapping,

@@ -26,6 +26,7 @@
 //                        last round sorts and writes D / I.
 //   hnsw.inc / lsh.inc / eval.inc   IndexHNSWFlat, IndexLSH, consumers of (hits, scores).
 //   assemble.inc                    protein-level hits from slice searches (knn_eval_assemble).
+//   pr_curve.inc                    the precision-recall threshold sweep over (is_correct, scores) (knn_eval_pr_curve).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
 #include <hip/hip_runtime.h>
 #include <thread>
@@ -5376,4 +5377,5 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "lsh.inc"
 #include "eval.inc"
 #include "assemble.inc"
+#include "pr_curve.inc"
 #include "range.inc"

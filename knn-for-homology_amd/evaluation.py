@@ -9,10 +9,12 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   assemble                pfam/slices/slices.py:256-291 (protein-level hits from slice hits; also run over the
                           MMseqs2 slice hits, slices.py:312-314)
   auc1_assembled          pfam/slices/slices.py:294-305
+  compute_correctness_array  pfam/proteins.py:201-207 (per-hit "is this a homologue" matrix)
+  precision_recall_curve     pfam/proteins.py:626-648 (mean precision / recall per query over score thresholds)
 """
 from collections import Counter
 from itertools import groupby
-from typing import Dict, List, Sequence, Set, Tuple
+from typing import Dict, Iterable, List, Sequence, Set, Tuple
 
 import numpy as np
 from numpy import ndarray
@@ -223,3 +225,81 @@ def auc1_assembled(groups: ndarray, protein_names: Sequence[str], homologous_pro
         _lib.check(_lib.lib().knn_eval_sets(groups.ctypes.data, ng, k_out, offsets.ctypes.data,
                                             members.ctypes.data if members.size else None, lead.ctypes.data, tp.ctypes.data))
     return lead / sizes
+
+
+def compute_correctness_array(hits: ndarray, homologous_rows: Sequence[Iterable[int]]) -> ndarray:
+    """bool [nq, k]: is hit j of query q one of homologous_rows[q] (pfam/proteins.py:201-207; homologous_rows is the
+    reference's homologous_proteins_int: per query an iterable of database rows).  A hit that is in no set, -1 included,
+    is False."""
+    hits = _hits(hits)
+    nq, k = hits.shape
+    if len(homologous_rows) != nq:
+        raise ValueError(f"homologous_rows must hold one set per row of hits ({nq}), not {len(homologous_rows)}")
+    offsets = np.zeros(nq + 1, np.int64)
+    members = []
+    for i in range(nq):
+        members.extend(sorted(set(int(t) for t in homologous_rows[i])))
+        offsets[i + 1] = len(members)
+    members = np.asarray(members, np.int64)
+    out = np.empty((nq, k), np.uint8)
+    if nq and k:
+        _lib.check(_lib.lib().knn_eval_sets_matrix(hits.ctypes.data, nq, k, offsets.ctypes.data,
+                                                   members.ctypes.data if members.size else None, out.ctypes.data))
+    return out.astype(bool)
+
+
+def precision_recall_curve(correct: ndarray, scores: ndarray, correct_totals: ndarray, limit: int = 300, smoothness: int = 300,
+                           thresholds: ndarray = None, want_counts: bool = False):
+    """The reference's precision-recall sweep (pfam/proteins.py:626-648) as one GPU pass -> (recall, precision,
+    thresholds), the tuple the reference stores in plot_data[label]; each is float64 [number of thresholds].
+
+    correct bool / uint8 [nq, k] (compute_correctness_array), scores float32 [nq, k], correct_totals [nq] (the number of
+    homologues per query, at least 1); only the first `limit` columns count.  At threshold t a hit is predicted when
+    its score > t; precision is the mean over queries of (correct predicted / predicted), 1 for a query with no
+    prediction, recall the mean of (correct predicted / total).  The means are sums in a fixed order (blocks of 256
+    queries, include/knn355.h), so they can differ from numpy.mean's pairwise sum in the last bits.
+    thresholds=None: numpy.quantile(scores[:, :limit], numpy.linspace(0, 1, smoothness + 1)), as the reference; the
+    quantiles are host work (numpy; computing them on the device is out of scope here).  Thresholds given in any order are
+    sorted for the call and the results put back in the caller's order.  want_counts=True appends (selected, tp, empty)
+    int64 arrays: predictions and correct predictions summed over the queries, and queries with no prediction."""
+    correct = np.asarray(correct)
+    if correct.ndim != 2:
+        raise ValueError("correct must be 2-D")
+    correct = np.ascontiguousarray(correct != 0 if correct.dtype != np.bool_ else correct).view(np.uint8)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    nq, k = correct.shape
+    if scores.shape != correct.shape:
+        raise ValueError(f"scores {scores.shape} and correct {correct.shape} must have the same shape")
+    if nq < 1:
+        raise ValueError("precision_recall_curve needs one query at least")
+    limit = int(limit)
+    if limit < 1 or limit > k:
+        raise ValueError(f"limit must be in [1, k = {k}], not {limit}")
+    totals = _per_query(correct_totals, np.int64, nq, "correct_totals")
+    if (totals < 1).any():
+        raise ValueError("correct_totals must be positive: recall divides by them")
+    if thresholds is None:
+        thresholds = np.quantile(scores[:, :limit], np.linspace(0, 1, int(smoothness) + 1))
+    thresholds = np.array(thresholds, dtype=np.float64)
+    if thresholds.ndim != 1 or not 1 <= thresholds.size <= 4096:
+        raise ValueError("thresholds must be 1-D with 1 .. 4096 entries")
+    if np.isnan(thresholds).any():
+        raise ValueError("thresholds must not hold NaN")
+    order = np.argsort(thresholds, kind="stable")
+    thr = np.ascontiguousarray(thresholds[order])
+    nthr = thr.size
+    precision = np.empty(nthr, np.float64)
+    recall = np.empty(nthr, np.float64)
+    counts = [np.empty(nthr, np.int64) for _ in range(3)] if want_counts else [None] * 3
+    _lib.check(_lib.lib().knn_eval_pr_curve(correct.ctypes.data, scores.ctypes.data, nq, k, limit, totals.ctypes.data,
+                                            thr.ctypes.data, nthr, precision.ctypes.data, recall.ctypes.data,
+                                            *(c.ctypes.data if want_counts else None for c in counts)))
+
+    def back(a):
+        out = np.empty_like(a)
+        out[order] = a
+        return out
+
+    if want_counts:
+        return back(recall), back(precision), thresholds, tuple(back(c) for c in counts)
+    return back(recall), back(precision), thresholds
