@@ -415,6 +415,40 @@ int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores, int64_t nq
                       const int64_t *totals, const double *thresholds, int32_t nthr,
                       double *precision_out, double *recall_out,
                       int64_t *selected_out, int64_t *tp_out, int64_t *empty_out);
+/* pfam/proteins.py:216-240 ("combined") and 340-372 ("both aligned"): one output row per query from two hit lists.
+ * hits_a / scores_a / keep_a are [nq][ka], hits_b / scores_b [nq][kb], hits_out / scores_out / source_out [nq][k_out],
+ * filled_out [nq]; all host arrays, row-major.  Scores are float64, as the reference's e-values are
+ * (seqvec_search/mmseqs/_read_results_db.py:172; a float32 holds 0 for every e-value under 1.4e-45, and float32 scores
+ * upcast exactly); ids are compared as whole int64 values.
+ *   entries    an entry of A exists when its hit is >= 0 and keep_a is NULL or non-zero there; an entry of B exists when
+ *              its hit is >= 0.  Entries that do not exist are never emitted and never enter a set.  (The reference pads
+ *              its rows with id 0, which is therefore an ordinary id here too.)
+ *   positions  the position of A's column j is j, the position of B's column j is ka + j
+ *   KNN_FUSE_PREFIX_FILL   the row's output is the existing A entries in column order, then the existing B entries, in
+ *              column order, whose id no existing A entry of that row carries; cut at k_out.  Repeats inside A, or inside
+ *              B, are kept, as the reference keeps them.  `ascending` only chooses the padding.
+ *   KNN_FUSE_SORTED_UNION  the existing entries of A and B are ordered by score: ascending != 0 puts the smallest first,
+ *              otherwise the largest; -0.0 and +0.0 tie; every NaN sorts behind everything else; equal scores (and the
+ *              NaNs among themselves) are ordered by position.  Sub-normal scores order by their value: the comparison is
+ *              made on the doubles' bits and flushes nothing.  The row is walked once in that order: an entry whose id an
+ *              earlier entry of the walk carries is dropped; the walk stops at k_out outputs.  This is numpy.argsort
+ *              (proteins.py:345) with its unspecified order among equal scores fixed to the stable one.
+ *   outputs    filled_out[q] is the number of outputs of row q; scores_out holds the input's bits; source_out (may be
+ *              NULL) holds each output's position.  The rest of the row is padded: id -1, score +DBL_MAX (ascending) or
+ *              -DBL_MAX (not ascending), source -1.
+ * KNN_ERR_INVALID, with a message naming the argument, before anything is allocated or launched and with the outputs
+ * untouched: nq < 0; ka or kb outside [1, KNN_MAX_K]; k_out outside [1, ka + kb]; an unknown mode; a null required
+ * pointer (keep_a and source_out may be NULL).  nq = 0 returns 0 before any pointer is looked at.  Rows go through the
+ * device in slabs of the row count above for k = ka + kb (KNN355_EVAL_SLAB_ROWS included).
+ * Hot path: fuse_kernel (fuse.inc), one workgroup per row: a bitonic sort of (order word of the double, position) pairs
+ * in LDS and a repeat scan in rank order (sorted union), or a membership scan of B against A's ids in LDS (prefix, then
+ * fill); ballot-and-prefix compaction either way. */
+#define KNN_FUSE_PREFIX_FILL 0
+#define KNN_FUSE_SORTED_UNION 1
+int knn_eval_fuse(const int64_t *hits_a, const double *scores_a, const uint8_t *keep_a, int64_t ka,
+                  const int64_t *hits_b, const double *scores_b, int64_t kb, int64_t nq,
+                  int32_t mode, int32_t ascending, int32_t k_out,
+                  int64_t *hits_out, double *scores_out, int32_t *source_out, int32_t *filled_out);
 
 /* ---- MMseqs2 prefilter database: SURVEY section 8(f) N3 ----------------------------
  * seqvec_search/mmseqs/_write_prefilter_db.py:52-97 write_prefilter_db: data file

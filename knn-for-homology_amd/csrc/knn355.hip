@@ -27,6 +27,7 @@
 //   hnsw.inc / lsh.inc / eval.inc   IndexHNSWFlat, IndexLSH, consumers of (hits, scores).
 //   assemble.inc                    protein-level hits from slice searches (knn_eval_assemble).
 //   pr_curve.inc                    the precision-recall threshold sweep over (is_correct, scores) (knn_eval_pr_curve).
+//   fuse.inc                        the two hit-list fusions of the results scripts: prefix-then-fill, sorted union (knn_eval_fuse).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
 #include <hip/hip_runtime.h>
 #include <thread>
@@ -218,6 +219,26 @@ __device__ __forceinline__ void wg_bitonic_sort(uint64_t *sb, int P, int tid, in
                 bool up = (a & k2) == 0;
                 uint64_t x = sb[a], y = sb[b];
                 if ((x > y) == up) { sb[a] = y; sb[b] = x; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// The same network over (word, tag) PAIRS compared lexicographically, for keys that fill all 64 bits of the word and
+// leave no room to pack a position behind them (fuse.inc: the order word of a double).  P <= 65536 tags.
+__device__ __forceinline__ void wg_bitonic_sort_pairs(uint64_t *sk, uint16_t *st, int P, int tid, int nthreads)
+{
+    for (int k2 = 2; k2 <= P; k2 <<= 1) {
+        for (int j = k2 >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < (P >> 1); i += nthreads) {
+                int a = ((i & ~(j - 1)) << 1) | (i & (j - 1));
+                int b = a + j;
+                bool up = (a & k2) == 0;
+                uint64_t x = sk[a], y = sk[b];
+                uint16_t tx = st[a], ty = st[b];
+                bool gt = x > y || (x == y && tx > ty);
+                if (gt == up && (x != y || tx != ty)) { sk[a] = y; sk[b] = x; st[a] = ty; st[b] = tx; }
             }
             __syncthreads();
         }
@@ -5378,4 +5399,5 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "eval.inc"
 #include "assemble.inc"
 #include "pr_curve.inc"
+#include "fuse.inc"
 #include "range.inc"

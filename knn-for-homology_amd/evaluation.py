@@ -11,6 +11,8 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   auc1_assembled          pfam/slices/slices.py:294-305
   compute_correctness_array  pfam/proteins.py:201-207 (per-hit "is this a homologue" matrix)
   precision_recall_curve     pfam/proteins.py:626-648 (mean precision / recall per query over score thresholds)
+  combine_hits               pfam/proteins.py:216-240 ("combined": MMseqs2 hits with E < 0.1, filled up with k-NN hits)
+  merge_hits                 pfam/proteins.py:340-372 ("both aligned": two lists sorted together, repeated ids dropped)
 """
 from collections import Counter
 from itertools import groupby
@@ -303,3 +305,79 @@ def precision_recall_curve(correct: ndarray, scores: ndarray, correct_totals: nd
     if want_counts:
         return back(recall), back(precision), thresholds, tuple(back(c) for c in counts)
     return back(recall), back(precision), thresholds
+
+
+KNN_FUSE_PREFIX_FILL, KNN_FUSE_SORTED_UNION = 0, 1  # include/knn355.h
+
+
+def _fuse(hits_a, scores_a, keep_a, hits_b, scores_b, mode, ascending, k_out, want_sources):
+    """knn_eval_fuse over checked arrays -> (hits, scores, source or None, filled)"""
+    hits_a, hits_b = _hits(hits_a), _hits(hits_b)
+    scores_a = np.ascontiguousarray(scores_a, dtype=np.float64)
+    scores_b = np.ascontiguousarray(scores_b, dtype=np.float64)
+    if scores_a.shape != hits_a.shape or scores_b.shape != hits_b.shape:
+        raise ValueError(f"scores {scores_a.shape}, {scores_b.shape} and hits {hits_a.shape}, {hits_b.shape} must have the same shapes")
+    if hits_a.shape[0] != hits_b.shape[0]:
+        raise ValueError(f"both hit lists must have one row per query, not {hits_a.shape[0]} and {hits_b.shape[0]}")
+    (nq, ka), kb = hits_a.shape, hits_b.shape[1]
+    k_out = ka if k_out is None else int(k_out)
+    if keep_a is not None:
+        keep_a = np.ascontiguousarray(keep_a, dtype=np.uint8)
+        if keep_a.shape != hits_a.shape:
+            raise ValueError(f"keep {keep_a.shape} and hits {hits_a.shape} must have the same shape")
+    hits = np.empty((nq, max(k_out, 0)), np.int64)
+    scores = np.empty(hits.shape, np.float64)
+    source = np.empty(hits.shape, np.int32) if want_sources else None
+    filled = np.empty(nq, np.int32)
+    _lib.check(_lib.lib().knn_eval_fuse(hits_a.ctypes.data, scores_a.ctypes.data, None if keep_a is None else keep_a.ctypes.data, ka,
+                                        hits_b.ctypes.data, scores_b.ctypes.data, kb, nq, mode, 1 if ascending else 0, k_out,
+                                        hits.ctypes.data, scores.ctypes.data, source.ctypes.data if want_sources else None,
+                                        filled.ctypes.data))
+    return hits, scores, source, filled
+
+
+def merge_hits(hits_a: ndarray, scores_a: ndarray, hits_b: ndarray, scores_b: ndarray, k_out: int = None, ascending: bool = True,
+               pad_hit: int = -1, pad_score: float = None, want_sources: bool = False):
+    """Two hit lists per query sorted together, every hit id already seen dropped (pfam/proteins.py:340-372), one GPU
+    pass -> (hits int64 [nq, k_out], scores float64 [nq, k_out]) and, with want_sources, source int32 [nq, k_out].
+
+    hits_a / scores_a [nq, ka] and hits_b / scores_b [nq, kb]; scores are taken as float64 (e-values: float32 cannot
+    order those under 1.4e-45).  Per query the entries of both lists are ordered by score (ascending=True: smallest
+    first, as for e-values; equal scores in the order of the concatenated lists, NaN last) and walked once, dropping an
+    entry whose id came earlier, up to k_out outputs (default: A's width, as the reference).  An entry with a negative
+    id does not exist.  source is the column of numpy.concatenate([hits_a, hits_b], axis=1) an output came from, -1
+    for padding.  Unfilled slots hold pad_hit and pad_score (default -1 and +-DBL_MAX, as the flat search pads; the
+    reference's call is pad_hit=0, pad_score=10**6, which makes its padding an ordinary hit of id 0)."""
+    hits, scores, source, filled = _fuse(hits_a, scores_a, None, hits_b, scores_b, KNN_FUSE_SORTED_UNION, ascending, k_out, want_sources)
+    if pad_hit != -1 or pad_score is not None:
+        unfilled = np.arange(hits.shape[1])[None, :] >= filled[:, None]
+        hits[unfilled] = pad_hit
+        if pad_score is not None:
+            scores[unfilled] = pad_score
+    return (hits, scores, source) if want_sources else (hits, scores)
+
+
+def combine_hits(hits_a: ndarray, e_values_a: ndarray, hits_b: ndarray, scores_b: ndarray, threshold: float = 0.1, k_out: int = None,
+                 short: str = "raise", want_sources: bool = False):
+    """The hits of A with an e-value under the threshold, filled up with the hits of B that are not among them
+    (pfam/proteins.py:216-240: A is MMseqs2's list, B the k-NN list), one GPU pass -> (hits int64 [nq, k_out], scores
+    float64 [nq, k_out]) and, with want_sources, source int32 [nq, k_out] (columns of the concatenated lists).
+
+    An entry of A is kept when e_values_a < threshold, in column order, and its score is -numpy.log(e_values_a +
+    10**-200) in float64 (numpy on the host, as the reference computes it); B's entries follow in column order with
+    their own scores, except those whose id a kept entry of the row carries.  k_out defaults to A's width.  An entry
+    with a negative id does not exist.  A row that cannot be filled raises ValueError, as the reference does;
+    short="pad" returns it padded with id -1 and score -DBL_MAX instead.  One case differs: a row that becomes full on
+    B's very last entry is a full row here, while the reference's `for ... else` raises there (its loop ends without
+    meeting the `break` that a further entry would have triggered)."""
+    if short not in ("raise", "pad"):
+        raise ValueError("short must be 'raise' or 'pad'")
+    e_values_a = np.ascontiguousarray(e_values_a, dtype=np.float64)
+    keep = e_values_a < threshold
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scores_a = -np.log(e_values_a + 10**-200)
+    hits, scores, source, filled = _fuse(hits_a, scores_a, keep, hits_b, scores_b, KNN_FUSE_PREFIX_FILL, False, k_out, want_sources)
+    if short == "raise" and (filled < hits.shape[1]).any():
+        row = int(np.argmax(filled < hits.shape[1]))
+        raise ValueError(f"row {row} holds {int(filled[row])} hits, fewer than k_out = {hits.shape[1]}")
+    return (hits, scores, source) if want_sources else (hits, scores)
