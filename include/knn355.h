@@ -110,7 +110,17 @@ int knn_flat_search_self_dev(knn_handle h, int64_t k, float *D_dev, int64_t *I_d
 int knn_flat_normalize_rows(knn_handle h);
 /* A second handle on the same device-resident rows with its own stream and scratch
  * memory (read-only: add/reset/reserve/normalize_rows fail on it; it sees the rows present
- * when it was made and must be freed before its parent).  Two searches on a handle and
+ * when it was made and must be freed before its parent).  A view goes STALE when its
+ * parent's storage moves: an add or reserve beyond the parent's capacity, a reset, the
+ * parent being freed (an add that fits the capacity leaves it alive, with its old row
+ * count; knn_flat_normalize_rows leaves it alive and it sees the new values).  Every call
+ * that reads rows refuses a stale view with KNN_ERR_INVALID before anything is copied or
+ * launched, the output arrays untouched: knn_flat_search / _dev / _keys_dev / _self /
+ * _self_dev, knn_sharded_search_dev, knn_flat_range_search / _self, knn_flat_refine,
+ * knn_lsh_search_refine (its flat handle), knn_gather_distances (an empty candidate list
+ * included), knn_flat_reconstruct, knn_flat_read_rate.  A view of a view: a stale parent
+ * view is refused (KNN_ERR_INVALID); a live one yields a view of the same rows that goes
+ * stale together with it.  Two searches on a handle and
  * its view overlap on the GPU -- the small launches at either end of one search (seed
  * sample, merges, the multi-GPU all-gather) hide behind the other one's scan.  FAISS's
  * GPU flat index does the same with two streams; the reference's CPU path has no

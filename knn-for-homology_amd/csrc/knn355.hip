@@ -3264,6 +3264,11 @@ struct knn_index_s {
     float last_ms = 0.f;
 };
 
+// A view whose parent's storage has moved on (grown, reset, freed): its xb / yn went back to the pool.  Every entry point
+// that reads a handle's rows asks this first, before anything is copied or launched.
+static bool view_is_stale(const knn_index_s *h) { return h->is_view && h->storage_gen->load() != h->view_gen; }
+#define KNN_STALE_VIEW_MSG ": this view is stale (its parent index was grown, reset or freed after the view was made)"
+
 static int ensure_device(int device)
 {
     int n = 0;
@@ -3429,6 +3434,7 @@ extern "C" int knn_flat_view(knn_handle parent, knn_handle *out)
     if (!parent || !out) return set_err(KNN_ERR_INVALID, "flat_view: null argument");
     std::lock_guard<std::mutex> lk(parent->mu);
     if (parent->approx16) return set_err(KNN_ERR_UNSUPPORTED, "flat_view: not for an approximate (bf16) index");
+    if (view_is_stale(parent)) return set_err(KNN_ERR_INVALID, "flat_view" KNN_STALE_VIEW_MSG); // (its xb / yn dangle: a copy of them must not pass for fresh)
     HIP_TRY(hipSetDevice(parent->device));
     knn_index_s *h = new knn_index_s();
     h->flags = parent->flags;
@@ -3442,7 +3448,9 @@ extern "C" int knn_flat_view(knn_handle parent, knn_handle *out)
     h->num_cus = parent->num_cus;
     h->is_view = true;
     h->storage_gen = parent->storage_gen;
-    h->view_gen = parent->storage_gen->load();
+    // a view of a live view goes stale together with it: the generation its rows were read at, not today's (the owner may have
+    // moved on between the check above and here)
+    h->view_gen = parent->is_view ? parent->view_gen : parent->storage_gen->load();
     h->xb = parent->xb;
     h->yn = parent->yn;
     h->ntotal = parent->ntotal;
@@ -3745,6 +3753,7 @@ extern "C" int knn_flat_reconstruct(knn_handle h, int64_t i0, int64_t n, float *
 {
     if (!h) return set_err(KNN_ERR_INVALID, "reconstruct: null handle");
     std::lock_guard<std::mutex> lk(h->mu);
+    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "reconstruct" KNN_STALE_VIEW_MSG);
     if (i0 < 0 || n < 0 || i0 + n > h->ntotal) return set_err(KNN_ERR_INVALID, "reconstruct: range out of bounds");
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
@@ -4230,8 +4239,7 @@ static int check_search_args(knn_index_s *h, const void *q, int64_t nq, int64_t 
     if (k < 1) return set_err(KNN_ERR_INVALID, "search: k must be >= 1");
     if (k > KNN_MAX_K) return set_err(KNN_ERR_UNSUPPORTED, "search: k > 2048 is not supported by the fused top-k");
     if (nq > 0 && (!q || !D || !I)) return set_err(KNN_ERR_INVALID, "search: null pointer");
-    if (h->is_view && h->storage_gen->load() != h->view_gen)
-        return set_err(KNN_ERR_INVALID, "search: this view is stale (its parent index was grown, reset or freed after the view was made)");
+    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "search" KNN_STALE_VIEW_MSG);
     return 0;
 }
 
@@ -5004,6 +5012,7 @@ extern "C" int knn_flat_read_rate(knn_handle h, int32_t reps, float *best_ms, in
 {
     if (!h || !best_ms || !bytes_read) return set_err(KNN_ERR_INVALID, "read_rate: null pointer");
     std::lock_guard<std::mutex> lk(h->mu);
+    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "read_rate" KNN_STALE_VIEW_MSG);
     HIP_TRY(hipSetDevice(h->device));
     const size_t bytes = (size_t)h->ntotal * h->dp * 4;
     *bytes_read = (int64_t)bytes;
@@ -5141,6 +5150,7 @@ extern "C" int knn_gather_distances(knn_handle h, const float *q_host, int64_t n
 {
     if (!h) return set_err(KNN_ERR_INVALID, "gather_distances: null handle");
     if (nq < 0) return set_err(KNN_ERR_INVALID, "gather_distances: negative nq");
+    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "gather_distances" KNN_STALE_VIEW_MSG); // (an empty list too: nothing of a stale view is served)
     if (nq == 0) return 0;
     if (!q_host || !cand_offsets) return set_err(KNN_ERR_INVALID, "gather_distances: null pointer");
     const int64_t np = cand_offsets[nq];

@@ -491,8 +491,7 @@ static int check_range_args(knn_index_s *h, const void *q, int64_t nq, const uin
     if (!h) return set_err(KNN_ERR_INVALID, "range_search: null handle");
     if (nq < 0) return set_err(KNN_ERR_INVALID, "range_search: negative nq");
     if (!lims || (nq > 0 && !q)) return set_err(KNN_ERR_INVALID, "range_search: null pointer");
-    if (h->is_view && h->storage_gen->load() != h->view_gen)
-        return set_err(KNN_ERR_INVALID, "range_search: this view is stale (its parent index was grown, reset or freed after the view was made)");
+    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "range_search" KNN_STALE_VIEW_MSG);
     return 0;
 }
 

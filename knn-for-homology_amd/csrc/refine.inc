@@ -174,8 +174,7 @@ static int refine_check_shape(int64_t nq, int64_t kb, int64_t k, const char *who
 static int refine_check_flat(knn_index_s *flat, const char *who)
 {
     if (flat->approx16) return set_err(KNN_ERR_UNSUPPORTED, std::string(who) + ": not for an approximate (bf16) index");
-    if (flat->is_view && flat->storage_gen->load() != flat->view_gen)
-        return set_err(KNN_ERR_INVALID, std::string(who) + ": this view is stale (its parent index was grown, reset or freed after the view was made)");
+    if (view_is_stale(flat)) return set_err(KNN_ERR_INVALID, std::string(who) + KNN_STALE_VIEW_MSG);
     return 0;
 }
 

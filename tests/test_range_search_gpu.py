@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from flat_lifecycle_reference import expected_range as _expected  # (lims, D, I) from the oracle's full ranking
 
 pytestmark = pytest.mark.gpu
 
@@ -22,21 +23,6 @@ def _bits(a):
 
 def _better(D, r, metric):
     return D > np.float32(r) if metric == IP else D < np.float32(r)
-
-
-def _expected(oracle, xb, xq, r, metric, l2_mode=0):
-    """(lims, D, I) from the oracle's full ranking"""
-    D, I = oracle.flat_search(xb, xq, xb.shape[0], metric, l2_mode=l2_mode)
-    lims, Ds, Is = [0], [], []
-    for q in range(xq.shape[0]):
-        keep = (I[q] >= 0) & _better(D[q], r, metric)
-        ids, d = I[q][keep], D[q][keep]
-        o = np.argsort(ids, kind="stable")
-        Is.append(ids[o])
-        Ds.append(d[o])
-        lims.append(lims[-1] + int(keep.sum()))
-    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
-    return np.array(lims, np.uint64), cat(Ds, np.float32), cat(Is, np.int64)
 
 
 def _assert_same(got, want):
