@@ -562,6 +562,20 @@ int knn_flat_set_scan16(knn_handle h, int32_t mode);
  * prefiltered searches of this handle that fell back to the fp32 scan so far.  Waits for the device. */
 int knn_last_scan16_info(knn_handle h, int32_t *used, int32_t *candidates_max, int64_t *fallbacks);
 
+/* Diagnostic entry: makes the index APPROXIMATE ON PURPOSE, as the coarse entry indexes of an HNSW index are.  Before the first
+ * add AND before knn_flat_reserve (the row stride changes: an index that already has storage is refused with KNN_ERR_INVALID
+ * until knn_reset), not on a view, and not together with knn_flat_set_scan16 or on the storage index of an HNSW index
+ * (KNN_ERR_UNSUPPORTED).  Rows are padded to a multiple of 64 values and a bf16
+ * copy of every row (round to nearest even) is kept beside the fp32 one; knn_flat_search, knn_flat_search_dev,
+ * knn_flat_search_keys_dev and knn_flat_search_self / _self_dev then multiply bf16 copies of rows and queries on the bf16 MFMA
+ * (exact products, fp32 accumulation in an order that is not specified) and take the squared-L2 norms from the fp32 values, with
+ * the norm formula at every batch size.  knn_flat_reconstruct returns the fp32 rows, knn_flat_normalize_rows converts the copies
+ * again.  Every other entry point that reads the rows refuses such a handle with KNN_ERR_UNSUPPORTED before anything is copied
+ * or launched: knn_flat_view, knn_flat_refine, knn_lsh_search_refine, knn_flat_range_search / _self, knn_gather_distances,
+ * knn_sharded_search_dev, knn_flat_read_rate.  It exists so that the tests can compare the bf16 builds of the scan kernel with
+ * a reference of their own arithmetic; nothing else should want it. */
+int knn_flat_set_approx16(knn_handle h);
+
 /* A caller that hands one batch of queries over in pieces (its own blocks, one slice per GPU) says how large the
  * whole batch is: FAISS chooses the squared-L2 formula by the batch ITS caller passed to index.search
  * (/root/reference/seqvec_search/main.py:45; fewer than 20 queries: the sum of squared differences), so pieces of

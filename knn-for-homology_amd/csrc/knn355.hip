@@ -3652,14 +3652,26 @@ static int scan16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s
     return 0;
 }
 
-// before the first add: the index multiplies bf16 copies (rows padded to a multiple of 64 values)
+// before the first add and before knn_flat_reserve: the index multiplies bf16 copies (rows padded to a multiple of 64 values).
+// The row stride changes, so storage that was sized with the old one (reserve on an empty index) must not exist.
 static int flat_set_approx16(knn_index_s *h)
 {
     if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "approx16: the index already holds rows");
+    if (h->cap_rows != 0 || h->xb) return set_err(KNN_ERR_INVALID, "approx16: the index already has storage (knn_flat_reserve): set it first, or knn_reset");
     if (h->scan16) return set_err(KNN_ERR_UNSUPPORTED, "approx16: the index keeps fp16 copies for the 16-bit prefilter");
+    if (h->keep16) return set_err(KNN_ERR_UNSUPPORTED, "approx16: not for an index that keeps bf16 copies (HNSW)");
     h->approx16 = true;
     h->dp = round_up(h->d, 64);
     return 0;
+}
+
+// the same for a caller's index: the way in for the tests of the bf16 builds (include/knn355.h)
+extern "C" int knn_flat_set_approx16(knn_handle h)
+{
+    if (!h) return set_err(KNN_ERR_INVALID, "set_approx16: null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->is_view) return set_err(KNN_ERR_INVALID, "set_approx16: a view uses its parent's rows");
+    return flat_set_approx16(h);
 }
 
 // before the first add: bf16 copies of the rows are kept (the scans do not use them)
@@ -5013,6 +5025,7 @@ extern "C" int knn_flat_read_rate(knn_handle h, int32_t reps, float *best_ms, in
     if (!h || !best_ms || !bytes_read) return set_err(KNN_ERR_INVALID, "read_rate: null pointer");
     std::lock_guard<std::mutex> lk(h->mu);
     if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "read_rate" KNN_STALE_VIEW_MSG);
+    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "read_rate: not for an approximate (bf16) index"); // (its scans read the bf16 copies: the fp32 rows' rate bounds nothing)
     HIP_TRY(hipSetDevice(h->device));
     const size_t bytes = (size_t)h->ntotal * h->dp * 4;
     *bytes_read = (int64_t)bytes;
@@ -5151,6 +5164,7 @@ extern "C" int knn_gather_distances(knn_handle h, const float *q_host, int64_t n
     if (!h) return set_err(KNN_ERR_INVALID, "gather_distances: null handle");
     if (nq < 0) return set_err(KNN_ERR_INVALID, "gather_distances: negative nq");
     if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "gather_distances" KNN_STALE_VIEW_MSG); // (an empty list too: nothing of a stale view is served)
+    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "gather_distances: not for an approximate (bf16) index"); // (fp32 scores: not the ones its searches return)
     if (nq == 0) return 0;
     if (!q_host || !cand_offsets) return set_err(KNN_ERR_INVALID, "gather_distances: null pointer");
     const int64_t np = cand_offsets[nq];
@@ -5338,6 +5352,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
     if (!c) return set_err(KNN_ERR_INVALID, "sharded_search: null communicator");
     int rc = check_search_args(h, q_dev, nq, k, D_dev, I_dev);
     if (rc) return rc;
+    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "sharded_search: not for an approximate (bf16) index"); // (before the collective, like every argument error)
     if (nq == 0) return 0;
     if (h->device != c->device) return set_err(KNN_ERR_INVALID, "sharded_search: index and communicator live on different devices");
     std::lock_guard<std::mutex> lc(c->mu);

@@ -492,6 +492,7 @@ static int check_range_args(knn_index_s *h, const void *q, int64_t nq, const uin
     if (nq < 0) return set_err(KNN_ERR_INVALID, "range_search: negative nq");
     if (!lims || (nq > 0 && !q)) return set_err(KNN_ERR_INVALID, "range_search: null pointer");
     if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "range_search" KNN_STALE_VIEW_MSG);
+    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "range_search: not for an approximate (bf16) index"); // (the range scan has no bf16 build)
     return 0;
 }
 

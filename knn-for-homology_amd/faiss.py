@@ -204,6 +204,11 @@ class IndexFlat(Index):
         """Before the first add: keep fp16 copies of the rows for the exact 16-bit prefilter (knn_flat_set_scan16; 0 = off)"""
         _lib.check(_lib.lib().knn_flat_set_scan16(self._h, int(mode)))
 
+    def set_approx16(self):
+        """Before the first add: the index becomes approximate on purpose -- its searches multiply bf16 copies of rows and
+        queries, as the coarse entry indexes of IndexHNSWFlat do (knn_flat_set_approx16: a diagnostic entry for the tests)"""
+        _lib.check(_lib.lib().knn_flat_set_approx16(self._h))
+
     def last_scan16(self):
         """{"used": the last search took the exact 16-bit prefilter, "candidates_max": most rows one of its queries re-scored,
         "fallbacks": prefiltered searches of this handle that fell back to the fp32 scan so far}"""

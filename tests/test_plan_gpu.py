@@ -1,7 +1,7 @@
 """GPU: the library plans every case of tests/plan_cases.py as the table says -- the introspection of the last scan launch
 after a real search through the entry the case names -- and, for the cases small enough for the CPU oracle (nb <= 2^15),
-returns the oracle's ids and score bits.  The bf16 rows of the table are left to test_plan_cpu.py: no exported call makes such
-an index or reaches its introspection (IndexHNSWFlat keeps its coarse index to itself).  The table's literals come from the
+returns the oracle's ids and score bits.  The bf16 rows of the table run on an index made approximate with set_approx16, over
+integer rows, and return the ids and score bits of tests/approx16_reference.py.  The table's literals come from the
 library before the planner moved into csrc/plan.h (see plan_cases.py); test_plan_cpu.py checks the same table against the
 stand-alone planner.  The same for the symmetric self-search (SYM_CASES up to 16384 rows, through search_self) and the range
 scan (RANGE_CASES of 4096 rows, through range_search)."""
@@ -11,6 +11,7 @@ import functools
 import numpy as np
 import pytest
 
+import approx16_reference as ar
 import plan_cases as pc
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +26,15 @@ def _rows(nb):
     return xb
 
 
+@functools.lru_cache(maxsize=None)
+def _rows16(nb):
+    """the rows of an approximate (bf16) index: integers in [-16, 16], on which its arithmetic is exact in any order"""
+    xb = np.random.default_rng(nb).integers(-16, 17, (nb, D)).astype(np.float32)
+    xb[nb // 2: nb // 2 + 3] = xb[:3]
+    return xb
+
+
 _INDEX = {}
-FP32_CASES = [c for c in pc.CASES if not c.approx16]
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -35,22 +43,28 @@ def _release_indexes():
     _INDEX.clear()
 
 
-def _index(gpu_faiss, nb, metric):
-    if (nb, metric) not in _INDEX:
+def _index(gpu_faiss, nb, metric, approx16=False):
+    if (nb, metric, approx16) not in _INDEX:
         if len(_INDEX) >= 4:  # (a few databases stay on the device: the cases of one shape follow each other)
             _INDEX.pop(next(iter(_INDEX)))
         idx = gpu_faiss.IndexFlat(D, metric)
-        idx.add(_rows(nb))
-        _INDEX[(nb, metric)] = idx
-    return _INDEX[(nb, metric)]
+        if approx16:
+            idx.set_approx16()
+        idx.add(_rows16(nb) if approx16 else _rows(nb))
+        _INDEX[(nb, metric, approx16)] = idx
+    return _INDEX[(nb, metric, approx16)]
 
 
 def observe(gpu_faiss, c):
     """runs the case; returns (the tuple of plan_cases.EXPECT, queries, D, I)"""
     from knn_for_homology_amd import _lib
-    idx = _index(gpu_faiss, c.nb, c.metric)
-    xq = np.random.default_rng(c.nq * 7919 + c.k).standard_normal((c.nq, D), dtype=np.float32)
-    xq[:3] = _rows(c.nb)[:min(3, c.nq)]  # (queries that tie between a row and its duplicate)
+    idx = _index(gpu_faiss, c.nb, c.metric, c.approx16)
+    if c.approx16:
+        xq = np.random.default_rng(c.nq * 7919 + c.k).integers(-16, 17, (c.nq, D)).astype(np.float32)
+        xq[:3] = _rows16(c.nb)[:min(3, c.nq)]
+    else:
+        xq = np.random.default_rng(c.nq * 7919 + c.k).standard_normal((c.nq, D), dtype=np.float32)
+        xq[:3] = _rows(c.nb)[:min(3, c.nq)]  # (queries that tie between a row and its duplicate)
     idx.set_tuning(c.force_qt, c.force_chunks, c.flags)
     idx.set_batch(c.batch)
     try:
@@ -81,12 +95,17 @@ def observe(gpu_faiss, c):
     return got, xq, Dg, Ig
 
 
-@pytest.mark.parametrize("case", FP32_CASES, ids=[c.name for c in FP32_CASES])
+@pytest.mark.parametrize("case", pc.CASES, ids=[c.name for c in pc.CASES])
 def test_last_launch_is_the_planned_one(gpu_faiss, oracle, case):
     got, xq, Dg, Ig = observe(gpu_faiss, case)
     print(f"{case.name!r}: {got!r},")
     assert got == pc.EXPECT[case.name]
-    if case.nb <= 1 << 15:
+    if case.approx16:
+        if case.nb <= 1 << 15:
+            Do, Io = ar.expected(_rows16(case.nb), xq, case.k, case.metric)
+            assert np.array_equal(Ig, Io), f"{int((Ig != Io).sum())} neighbour ids differ"
+            assert np.array_equal(Dg.view(np.uint32), Do.view(np.uint32)), "score bits differ"
+    elif case.nb <= 1 << 15:
         # (FAISS's small-batch rule follows the caller's batch: the norm formula under KNN_TUNE_NORM_L2 and for a piece of a larger batch)
         norm = bool(case.flags & pc.NORM_L2) or case.batch >= 20
         Do, Io = oracle.flat_search(_rows(case.nb), xq, case.k, case.metric, l2_mode=1 if norm else 0)
