@@ -388,6 +388,51 @@ int knn_eval_assemble(const int64_t *hits, const float *scores, int64_t ns, int6
                       const int64_t *group_offsets, int64_t ng, const int32_t *row_group, int64_t nb,
                       const int32_t *self_group, int32_t depth, int32_t k_out, int32_t ascending,
                       int64_t *groups_out, float *scores_out, int64_t *qrow_out, int64_t *hit_out);
+/* pfam/slices/slices.py:49-80 and :101-142 evaluate: the hits of a search over slices judged at slice level.
+ *   ids       families are dense int32 codes in [0, nfam), proteins int32 ids in [0, np)
+ *   domains   domain_offsets int64 [np + 1]: protein p owns the domains [domain_offsets[p], domain_offsets[p+1]);
+ *             domain_family / domain_start / domain_stop int32 [nd], nd = domain_offsets[np] (all three may be NULL
+ *             when nd is 0, domain_offsets when np is 0).  Within one protein domain_family does not decrease.
+ *   slices    slice_protein / slice_start / slice_stop int32 [ns]; a slice with slice_protein == -1 has no domains
+ *   tests     for slice s and a domain d of its protein, exactly as slices.py:57 and :65:
+ *               inside        slice_start <= domain_start && domain_stop <= slice_stop
+ *               intersecting  otherwise, when slice_start < domain_stop && domain_start < slice_stop
+ *             matching(s) is the set of families with a domain inside, intersecting(s) the set of families with a
+ *             domain intersecting; one family can be in both, through two of its domains.
+ * knn_eval_slice_annotate (slices.py:49-80):
+ *   match_count[s] = |matching(s)|, distinct families counted once; annotation[s] = the one family of matching(s) when
+ *   match_count[s] == 1, else -1 (slices.py:76-80: has_annotation is annotation >= 0); family_sizes[f] (int64 [nfam],
+ *   all of it written) = the number of slices whose matching holds f (slices.py:70-74).
+ * knn_eval_slices (slices.py:101-142), hits int64 [nq][k], row q with a = query_family[q] and hit h:
+ *   is_correct[q][j] = 1 when a is in matching(h); is_ignore[q][j] = 1 when a is in intersecting(h), and also when
+ *   ignore_unannotated is non-zero and match_count[h] == 0 (match_count as knn_eval_slice_annotate wrote it; it may be
+ *   NULL when ignore_unannotated is 0).  A hit outside [0, ns), -1 included, is neither correct nor ignored.  (The
+ *   reference indexes its lists with the raw hit, so -1 reads the last slice there: that is not reproduced.)  A row
+ *   with a < 0 is all zeros, its lead and tp included.
+ *   lead[q] = the correct hits in front of the first hit that is neither correct nor ignored (the loop at
+ *   slices.py:131-138; a hit that is both counts as correct); tp[q] = the correct hits of the row;
+ *   column_correct[j] (int64 [k], may be NULL) = the rows whose hit j is correct, summed over all slabs (the script
+ *   plots its cumulative sum, slices.py:226-227).
+ * KNN_ERR_INVALID, with a message, before anything is allocated or launched and with the outputs untouched: a negative
+ * nq, ns, np or nfam; np > INT32_MAX; k < 1 or k > INT32_MAX; a null required pointer; domain_offsets[0] < 0 or
+ * decreasing offsets; a domain family outside [0, nfam) or smaller than its predecessor in the same protein; a
+ * slice_protein outside [-1, np); a query_family >= nfam.  nq = 0 returns 0 before any pointer is looked at.  ns = 0
+ * runs the same checks and then returns 0 without touching the device: family_sizes is zeros, and every output of
+ * knn_eval_slices is zeros (no hit names a slice).  The slice and domain tables are uploaded once per call, the hits go
+ * through the device in slabs (see above).
+ * Hot path: slice_annotate_kernel, one thread per slice over its protein's domains in family order, integer atomics
+ * into family_sizes; slice_eval_kernel, one wave per row: per hit one 16-byte slice record, a lower-bound search for a
+ * in the protein's domains and the interval tests over a's run, ballots for lead and tp (slices_eval.inc). */
+int knn_eval_slice_annotate(const int32_t *slice_protein, const int32_t *slice_start, const int32_t *slice_stop,
+                            int64_t ns, const int64_t *domain_offsets, const int32_t *domain_family,
+                            const int32_t *domain_start, const int32_t *domain_stop, int64_t np, int64_t nfam,
+                            int32_t *match_count, int32_t *annotation, int64_t *family_sizes);
+int knn_eval_slices(const int64_t *hits, int64_t nq, int64_t k, const int32_t *query_family,
+                    const int32_t *slice_protein, const int32_t *slice_start, const int32_t *slice_stop, int64_t ns,
+                    const int64_t *domain_offsets, const int32_t *domain_family, const int32_t *domain_start,
+                    const int32_t *domain_stop, int64_t np, int64_t nfam, const int32_t *match_count,
+                    int32_t ignore_unannotated, uint8_t *is_correct, uint8_t *is_ignore, int32_t *lead, int32_t *tp,
+                    int64_t *column_correct);
 /* pfam/proteins.py:201-207 compute_correctness_array: the per-hit membership matrix of knn_eval_sets' sets.
  * Arguments, argument checks, slabs and edge cases are knn_eval_sets' (members sorted per set, checked on the host;
  * nq = 0 returns 0); is_correct_out (uint8 [nq][k], required) gets 1 where hits[r][j] is a member of set r, else 0:

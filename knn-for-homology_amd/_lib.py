@@ -126,7 +126,11 @@ def _declare(L):
         "knn_eval_levels": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
         "knn_eval_assemble": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32,
                                         c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-        "knn_eval_sets_matrix": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+        "knn_eval_slice_annotate": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                              c_void_p, c_void_p, c_void_p]),
+        "knn_eval_slices": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "knn_eval_sets_matrix":(c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
         "knn_eval_pr_curve": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
         "knn_eval_fuse": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,

@@ -26,6 +26,7 @@
 //                        last round sorts and writes D / I.
 //   hnsw.inc / lsh.inc / eval.inc   IndexHNSWFlat, IndexLSH, consumers of (hits, scores).
 //   assemble.inc                    protein-level hits from slice searches (knn_eval_assemble).
+//   slices_eval.inc                 slice-level correctness and AUC1 of slice searches (knn_eval_slice_annotate, knn_eval_slices).
 //   pr_curve.inc                    the precision-recall threshold sweep over (is_correct, scores) (knn_eval_pr_curve).
 //   fuse.inc                        the two hit-list fusions of the results scripts: prefix-then-fill, sorted union (knn_eval_fuse).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
@@ -5423,6 +5424,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "lsh.inc"
 #include "eval.inc"
 #include "assemble.inc"
+#include "slices_eval.inc"
 #include "pr_curve.inc"
 #include "fuse.inc"
 #include "range.inc"

@@ -9,12 +9,14 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   assemble                pfam/slices/slices.py:256-291 (protein-level hits from slice hits; also run over the
                           MMseqs2 slice hits, slices.py:312-314)
   auc1_assembled          pfam/slices/slices.py:294-305
+  slice_tables            pfam/slices/slices.py:49-80 (families inside each slice, family sizes, has_annotation)
+  evaluate_slices         pfam/slices/slices.py:101-142 (evaluate: slice-level is_correct, is_ignore and AUC1)
   compute_correctness_array  pfam/proteins.py:201-207 (per-hit "is this a homologue" matrix)
   precision_recall_curve     pfam/proteins.py:626-648 (mean precision / recall per query over score thresholds)
   combine_hits               pfam/proteins.py:216-240 ("combined": MMseqs2 hits with E < 0.1, filled up with k-NN hits)
   merge_hits                 pfam/proteins.py:340-372 ("both aligned": two lists sorted together, repeated ids dropped)
 """
-from collections import Counter
+from collections import Counter, namedtuple
 from itertools import groupby
 from typing import Dict, Iterable, List, Sequence, Set, Tuple
 
@@ -227,6 +229,110 @@ def auc1_assembled(groups: ndarray, protein_names: Sequence[str], homologous_pro
         _lib.check(_lib.lib().knn_eval_sets(groups.ctypes.data, ng, k_out, offsets.ctypes.data,
                                             members.ctypes.data if members.size else None, lead.ctypes.data, tp.ctypes.data))
     return lead / sizes
+
+
+SliceTables = namedtuple("SliceTables", [
+    "slice_protein", "slice_start", "slice_stop",                            # int32 [ns]; protein -1: no domain record
+    "domain_offsets", "domain_family", "domain_start", "domain_stop",        # int64 [np + 1], int32 [nd] x 3
+    "proteins", "families",                                                  # the name of every protein id / family code
+    "match_count", "annotation", "has_annotation", "family_sizes"])          # int32 [ns] x 2, bool [ns], int64 [nfam]
+
+
+def _slice_host_tables(slices, protein_to_domain):
+    """The integer tables knn_eval_slice_annotate and knn_eval_slices take (include/knn355.h), built on the host:
+    proteins numbered in order of first appearance among the slices, a protein without an entry in protein_to_domain
+    being -1; family codes dense, in sorted order of the names that occur in those proteins' domains; the domains of a
+    protein sorted by family code (a stable sort: equal families keep the order of the dict's list)."""
+    ns = len(slices)
+    slice_protein = np.empty(ns, np.int32)
+    slice_start = np.empty(ns, np.int32)
+    slice_stop = np.empty(ns, np.int32)
+    protein_id, proteins = {}, []
+    for s, (protein, (start, stop)) in enumerate(slices):
+        pid = protein_id.get(protein)
+        if pid is None:
+            pid = -1
+            if protein in protein_to_domain:
+                pid = len(proteins)
+                proteins.append(protein)
+            protein_id[protein] = pid
+        slice_protein[s], slice_start[s], slice_stop[s] = pid, start, stop
+    families = sorted({pfam for protein in proteins for pfam, _ in protein_to_domain[protein]})
+    code = {f: i for i, f in enumerate(families)}
+    offsets = np.zeros(len(proteins) + 1, np.int64)
+    fam, start, stop = [], [], []
+    for p, protein in enumerate(proteins):
+        for pfam, (d0, d1) in sorted(protein_to_domain[protein], key=lambda d: code[d[0]]):
+            fam.append(code[pfam])
+            start.append(d0)
+            stop.append(d1)
+        offsets[p + 1] = len(fam)
+    return (slice_protein, slice_start, slice_stop, offsets, np.asarray(fam, np.int32), np.asarray(start, np.int32),
+            np.asarray(stop, np.int32), proteins, families)
+
+
+def slice_tables(slices: Sequence[Tuple[str, Tuple[int, int]]], protein_to_domain: Dict[str, List[Tuple[str, Tuple[int, int]]]]) -> SliceTables:
+    """pfam/slices/slices.py:49-80 as integer tables and one GPU pass.
+
+    slices is the reference's list of (protein, (start, stop)) (slices.py:33-36), protein_to_domain maps a protein to
+    its list of (pfam, (start, stop)).  A protein that protein_to_domain does not hold has no domains (the reference
+    raises KeyError).  -> SliceTables: the tables (see _slice_host_tables), `families` (the name of every family code)
+    and, from knn_eval_slice_annotate: match_count[s], the number of families with a domain inside slice s;
+    annotation[s], that family's code when there is exactly one, else -1; has_annotation, the reference's bool array
+    (slices.py:76); family_sizes[code], the number of slices with a domain of that family inside (slices.py:70-74)."""
+    sp, s0, s1, offsets, fam, d0, d1, proteins, families = _slice_host_tables(slices, protein_to_domain)
+    ns, nfam = len(sp), len(families)
+    match_count = np.zeros(ns, np.int32)
+    annotation = np.full(ns, -1, np.int32)
+    family_sizes = np.zeros(nfam, np.int64)
+    _lib.check(_lib.lib().knn_eval_slice_annotate(sp.ctypes.data, s0.ctypes.data, s1.ctypes.data, ns, offsets.ctypes.data,
+                                                  fam.ctypes.data if fam.size else None, d0.ctypes.data if fam.size else None,
+                                                  d1.ctypes.data if fam.size else None, len(proteins), nfam, match_count.ctypes.data,
+                                                  annotation.ctypes.data, family_sizes.ctypes.data if nfam else None))
+    return SliceTables(sp, s0, s1, offsets, fam, d0, d1, proteins, families, match_count, annotation, annotation >= 0, family_sizes)
+
+
+def evaluate_slices(hits: ndarray, tables: SliceTables, query_rows: ndarray = None, ignore_unannotated: bool = False,
+                    want_column_counts: bool = False):
+    """The reference's evaluate (pfam/slices/slices.py:101-142), one GPU pass -> (is_correct bool [nq, k], is_ignore
+    bool [nq, k], auc1s float64 [nq]) and, with want_column_counts, the int64 [k] number of rows whose hit j is correct.
+
+    hits [nq, k] are the hits of the query slices query_rows (default: the annotated slices, numpy.flatnonzero(
+    tables.has_annotation), as the reference passes slices_hits[has_annotation]).  A hit is correct when the query's
+    family has a domain inside the hit slice, ignored when it has one that merely intersects it or, with
+    ignore_unannotated, when the hit slice holds no family at all.  auc1s is the number of correct hits in front of the
+    first hit that is neither, over the size of the query's family; a query row without an annotation yields 0.  Two
+    cases differ from the loop: a hit of -1 (or any id outside the table) names no slice, where the reference's
+    slices_pfams_matching[-1] reads the last one; a protein without a domain record has no domains (slice_tables)."""
+    hits = _hits(hits)
+    nq, k = hits.shape
+    ns = len(tables.slice_protein)
+    if query_rows is None:
+        query_rows = np.flatnonzero(tables.has_annotation)
+    query_rows = np.ascontiguousarray(query_rows, np.int64)
+    if query_rows.shape != (nq,):
+        raise ValueError(f"query_rows must have shape ({nq},), one slice per row of hits, not {query_rows.shape}")
+    if nq and (query_rows.min() < 0 or query_rows.max() >= ns):
+        raise ValueError(f"query_rows must lie in [0, {ns})")
+    annotation = np.ascontiguousarray(tables.annotation[query_rows], np.int32)
+    is_correct = np.zeros((nq, k), np.uint8)
+    is_ignore = np.zeros((nq, k), np.uint8)
+    lead = np.zeros(nq, np.int32)
+    tp = np.zeros(nq, np.int32)
+    columns = np.zeros(k, np.int64) if want_column_counts else None
+    nd = tables.domain_family.size
+    if nq and k:
+        _lib.check(_lib.lib().knn_eval_slices(
+            hits.ctypes.data, nq, k, annotation.ctypes.data, tables.slice_protein.ctypes.data, tables.slice_start.ctypes.data,
+            tables.slice_stop.ctypes.data, ns, tables.domain_offsets.ctypes.data, tables.domain_family.ctypes.data if nd else None,
+            tables.domain_start.ctypes.data if nd else None, tables.domain_stop.ctypes.data if nd else None, len(tables.proteins),
+            len(tables.families), tables.match_count.ctypes.data, 1 if ignore_unannotated else 0, is_correct.ctypes.data,
+            is_ignore.ctypes.data, lead.ctypes.data, tp.ctypes.data, columns.ctypes.data if want_column_counts else None))
+    annotated = annotation >= 0
+    auc1s = np.zeros(nq, np.float64)
+    auc1s[annotated] = lead[annotated] / tables.family_sizes[annotation[annotated]]
+    out = (is_correct.astype(bool), is_ignore.astype(bool), auc1s)
+    return out + (columns,) if want_column_counts else out
 
 
 def compute_correctness_array(hits: ndarray, homologous_rows: Sequence[Iterable[int]]) -> ndarray:
