@@ -470,6 +470,37 @@ int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores, int64_t nq
                       const int64_t *totals, const double *thresholds, int32_t nthr,
                       double *precision_out, double *recall_out,
                       int64_t *selected_out, int64_t *tp_out, int64_t *empty_out);
+/* cath/cath.py:404-438 bootstrap_scores, the replicates behind the "+-" of the accuracy table (:441-458): per method and
+ * per resample of the evaluable queries, the raw and the superfamily-normalized top-1 accuracy.  All arrays are host
+ * arrays.  is_correct uint8 [nm][n]: row m is method m's verdict for each of the n evaluable queries, a non-zero byte
+ * means correct; family int32 [n]: the dense code in [0, nfam) of each query's superfamily (the reference's
+ * mapping_array[is_possible, 0]); sample_ids int32 [nb][n]: replicate b's resample, values in [0, n).  present_out is
+ * [nb], the other three outputs are [nm][nb].
+ *   counts      for replicate b and family f, count_b[f] = #{i : family[sample_ids[b][i]] == f} and corr_{m,b}[f] = the
+ *               number of those i whose is_correct[m][sample_ids[b][i]] is non-zero: exact integers
+ *   integers    present_out[b] = #{f : count_b[f] > 0}; correct_out[m][b] = the sum of corr_{m,b}[f] over f
+ *   raw         raw_out[m][b] = (double)correct_out[m][b] / (double)n, correctly rounded: bit for bit what
+ *               is_correct[sample_ids].mean() gives (cath.py:419)
+ *   terms       every f with count_b[f] > 0 contributes t_f = (double)corr[f] / (double)count[f], one IEEE division; an
+ *               absent family contributes nothing: there is never a 0 / 0
+ *   normalized  normalized_out[m][b] = S / (double)present_out[b], S the sum of the t_f in the order knn_eval_pr_curve
+ *               defines for its queries, here over family codes: codes form blocks of 256 consecutive codes; a block's
+ *               sum starts at +0.0 and adds its present families in code order; S starts at +0.0 and adds the block sums
+ *               in block order.  (No floating-point atomics, no tree whose shape depends on the launch.)
+ *   reference   the real number is the one cath.py:413-418 computes, sum_i c_i * (1 / n_f(i)) / #families; only the
+ *               order of the sum is fixed differently (the reference's is numpy's pairwise sum)
+ * KNN_ERR_INVALID, with a message naming the argument, before anything is allocated or launched and with the outputs
+ * untouched: nm, nb or n negative; n < 1 when nm and nb are positive (a mean over nothing); n > INT32_MAX; nfam < 1 or
+ * nfam > KNN_BOOTSTRAP_MAX_FAMILIES; a null pointer (all four outputs are required); a family value outside [0, nfam);
+ * a sample_ids value outside [0, n): all checked on the host.  nm = 0 or nb = 0 returns 0 before any pointer is looked
+ * at.  is_correct and family are uploaded once; the replicates go through the device in slabs of 256 MiB of
+ * sample_ids rows (KNN355_EVAL_SLAB_ROWS sets the replicates per slab, as above).
+ * Hot path: bootstrap_kernel (bootstrap.inc), one workgroup per (replicate, method): integer histograms count and corr
+ * over the family codes in LDS (8 * nfam bytes: the cap is 128 KiB), then one wave per block of 256 codes. */
+#define KNN_BOOTSTRAP_MAX_FAMILIES 16384
+int knn_eval_bootstrap(const uint8_t *is_correct, int64_t nm, int64_t n, const int32_t *family, int32_t nfam,
+                       const int32_t *sample_ids, int64_t nb, int64_t *correct_out, int32_t *present_out,
+                       double *normalized_out, double *raw_out);
 /* pfam/proteins.py:216-240 ("combined") and 340-372 ("both aligned"): one output row per query from two hit lists.
  * hits_a / scores_a / keep_a are [nq][ka], hits_b / scores_b [nq][kb], hits_out / scores_out / source_out [nq][k_out],
  * filled_out [nq]; all host arrays, row-major.  Scores are float64, as the reference's e-values are

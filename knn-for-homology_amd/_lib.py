@@ -133,6 +133,8 @@ def _declare(L):
         "knn_eval_sets_matrix":(c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
         "knn_eval_pr_curve": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+        "knn_eval_bootstrap": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
         "knn_eval_fuse": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
         "knn_write_prefilter_db": (c_int32, [c_char_p, c_char_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32]),

@@ -5426,5 +5426,6 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "assemble.inc"
 #include "slices_eval.inc"
 #include "pr_curve.inc"
+#include "bootstrap.inc"
 #include "fuse.inc"
 #include "range.inc"

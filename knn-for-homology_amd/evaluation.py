@@ -5,6 +5,8 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   evaluate_faiss          seqvec_search/main.py:53-82 (AUC1 / TP with one family label per id)
   compute_auc1            pfam/proteins_shared.py:139-157 (sets of homologous proteins)
   compute_is_correct      cath/cath.py:76-84 (C/A/T/H level matrix)
+  bootstrap_scores        cath/cath.py:404-438 (the 500 resamples behind the accuracy table's confidence intervals)
+  class_accuracies        cath/cath.py:441-458 (make_report_accuracies_table's numbers, before pandas formats them)
   compute_tps_comulative  seqvec_search/tp_cumulative.py:15-34
   assemble                pfam/slices/slices.py:256-291 (protein-level hits from slice hits; also run over the
                           MMseqs2 slice hits, slices.py:312-314)
@@ -140,6 +142,141 @@ def compute_is_correct(results: ndarray, mapping_array: ndarray, query_rows: nda
     _lib.check(_lib.lib().knn_eval_levels(results.ctypes.data, nq, k, qrows.ctypes.data, codes.ctypes.data,
                                           mapping.shape[0], mapping.shape[1], out.ctypes.data))
     return out.astype(bool)
+
+
+KNN_BOOTSTRAP_MAX_FAMILIES = 16384  # include/knn355.h
+
+
+def bootstrap_samples(n: int, replicates: int = 500, seed: int = 42) -> ndarray:
+    """int32 [replicates, n]: the reference's resamples (cath/cath.py:405, 409), one rng.choice(n, n) per replicate out of
+    numpy.random.default_rng(seed).  Drawn on the host, so that the table's numbers are the reference's."""
+    n, replicates = int(n), int(replicates)
+    if n < 1 or replicates < 0:
+        raise ValueError("bootstrap_samples needs n >= 1 and replicates >= 0")
+    rng = np.random.default_rng(seed)
+    out = np.empty((replicates, n), np.int32)
+    for b in range(replicates):
+        out[b] = rng.choice(n, n)
+    return out
+
+
+def bootstrap_replicates(is_correct: ndarray, families: ndarray, sample_ids: ndarray):
+    """The replicates of the reference's bootstrap (cath/cath.py:408-419) for one method or many, one GPU pass ->
+    (normalized float64, raw float64, correct int64, present int32 [nb]); the first three are [nb] for a 1-D is_correct
+    and [nm, nb] for a 2-D one.
+
+    is_correct bool [n] or [nm, n]: the top-1 verdict per evaluable query (per method); families [n]: any labels, the
+    superfamily of each of those queries (the reference's mapping_array[is_possible, 0]); sample_ids int [nb, n]: the
+    resamples, values in [0, n) (bootstrap_samples).  Per replicate: raw is the mean of the resampled verdicts,
+    normalized the mean over the superfamilies present in the resample of each one's share of correct members, correct
+    the number of correct samples, present the number of superfamilies.  The normalized sum runs in a fixed order
+    (include/knn355.h), so it can differ from numpy's pairwise sum in the last bits; raw is the reference's double."""
+    ic = np.asarray(is_correct)
+    if ic.ndim not in (1, 2):
+        raise ValueError("is_correct must be [n] or [nm, n]")
+    one = ic.ndim == 1
+    ic = np.ascontiguousarray(np.atleast_2d(ic) != 0).view(np.uint8)
+    nm, n = ic.shape
+    families = np.asarray(families)
+    if families.shape != (n,):
+        raise ValueError(f"families must have shape ({n},), one label per column of is_correct, not {families.shape}")
+    ids = np.asarray(sample_ids)
+    if ids.ndim != 2 or ids.shape[1] != n:
+        raise ValueError(f"sample_ids must have shape (replicates, {n}), not {ids.shape}")
+    if n < 1:
+        raise ValueError("bootstrap_replicates needs one query at least")
+    if ids.size and (ids.min() < 0 or ids.max() >= n):
+        raise ValueError(f"sample_ids must lie in [0, {n})")
+    ids = np.ascontiguousarray(ids, np.int32)
+    nb = ids.shape[0]
+    names, codes = np.unique(families, return_inverse=True)
+    if len(names) > KNN_BOOTSTRAP_MAX_FAMILIES:
+        raise ValueError(f"families holds {len(names)} distinct labels, more than {KNN_BOOTSTRAP_MAX_FAMILIES}")
+    codes = np.ascontiguousarray(codes.reshape(n), np.int32)
+    normalized = np.empty((nm, nb), np.float64)
+    raw = np.empty((nm, nb), np.float64)
+    correct = np.empty((nm, nb), np.int64)
+    present = np.empty(nb, np.int32)
+    _lib.check(_lib.lib().knn_eval_bootstrap(ic.ctypes.data, nm, n, codes.ctypes.data, len(names), ids.ctypes.data, nb,
+                                             correct.ctypes.data, present.ctypes.data, normalized.ctypes.data, raw.ctypes.data))
+    if one:
+        return normalized[0], raw[0], correct[0], present
+    return normalized, raw, correct, present
+
+
+def bootstrap_scores(is_correct: ndarray, normalized, families: ndarray, replicates: int = 500, seed: int = 42,
+                     sample_ids: ndarray = None):
+    """The reference's bootstrap_scores (cath/cath.py:404-438) -> (plus_minus_normalized, plus_minus_raw): the larger
+    distance from the point estimate to the 2.5 % and the 97.5 % replicate.
+
+    is_correct bool [n] with normalized a float gives two floats; is_correct [nm, n] with normalized [nm] gives two
+    float64 [nm] arrays from one GPU pass.  families [n] takes the place of the reference's global
+    mapping_array[is_possible, 0]; sample_ids (default: bootstrap_samples(n, replicates, seed), the reference's stream)
+    lets a caller draw the resamples once for several calls."""
+    ic = np.asarray(is_correct)
+    if ic.ndim not in (1, 2):
+        raise ValueError("is_correct must be [n] or [nm, n]")
+    one = ic.ndim == 1
+    ic = np.atleast_2d(ic) != 0
+    x = np.atleast_1d(np.asarray(normalized, np.float64))
+    if x.shape != (ic.shape[0],):
+        raise ValueError(f"normalized must hold one value per method ({ic.shape[0]}), not shape {x.shape}")
+    if sample_ids is None:
+        sample_ids = bootstrap_samples(ic.shape[1], replicates, seed)
+    boot_normalized, boot_raw, _, _ = bootstrap_replicates(ic, families, sample_ids)
+    nb = boot_raw.shape[1]
+    if nb < 1:
+        raise ValueError("bootstrap_scores needs one replicate at least")
+    boot_normalized = np.sort(boot_normalized, axis=1)
+    boot_raw = np.sort(boot_raw, axis=1)
+    lower, upper = int(nb * 0.025), int(nb * 0.975)
+    mean = ic.mean(axis=1)
+    plus_minus_normalized = np.maximum(x - boot_normalized[:, lower], boot_normalized[:, upper] - x)
+    plus_minus_raw = np.maximum(mean - boot_raw[:, lower], boot_raw[:, upper] - mean)
+    if one:
+        return float(plus_minus_normalized[0]), float(plus_minus_raw[0])
+    return plus_minus_normalized, plus_minus_raw
+
+
+def class_accuracies(is_correct_all_per_method: Dict[str, ndarray], mapping_array: ndarray, bootstrap: bool = False,
+                     replicates: int = 500, seed: int = 42, sample_ids: ndarray = None) -> Dict[str, tuple]:
+    """The numbers of the reference's make_report_accuracies_table (cath/cath.py:441-458) before pandas formats them:
+    name -> (normalized, raw), or (normalized, raw, normalized_stderr, raw_stderr) with bootstrap=True, ordered by
+    normalized, descending (equal values keep the order of the input).
+
+    is_correct_all_per_method maps a method to compute_is_correct's bool [n, levels, hits] (its [:, 0, 0] is read: the
+    first hit at level 0) or to that bool [n] column itself; mapping_array is [n, levels], level 0 in column 0.  From
+    level 0 (cath.py:94-109): is_possible marks the queries whose level-0 family has more than one member,
+    normalization is 1 / family size there and 0 elsewhere, families_count the number of such families.  normalized =
+    (is_correct * normalization).sum() / families_count, raw = is_correct[is_possible].mean(), in numpy as the reference.
+    With bootstrap=True all methods share one batch of resamples and one GPU pass (bootstrap_scores)."""
+    mapping = np.asarray(mapping_array)
+    if mapping.ndim != 2:
+        raise ValueError("mapping_array must be [n, levels]")
+    n = mapping.shape[0]
+    names, codes, sizes = np.unique(mapping[:, 0], return_inverse=True, return_counts=True)
+    member_sizes = sizes[codes.reshape(n)]
+    is_possible = member_sizes > 1
+    normalization = 1 / member_sizes
+    normalization[~is_possible] = 0
+    families_count = int((sizes > 1).sum())
+    columns = {}
+    for name, is_correct in is_correct_all_per_method.items():
+        is_correct = np.asarray(is_correct)
+        column = is_correct[:, 0, 0] if is_correct.ndim == 3 else is_correct
+        if column.shape != (n,):
+            raise ValueError(f"is_correct of {name!r} must have one row per row of mapping_array ({n}), not shape {is_correct.shape}")
+        columns[name] = column != 0
+    if families_count < 1 and columns:
+        raise ValueError("no level-0 family has more than one member: nothing can be evaluated")
+    out = {name: ((column * normalization).sum() / families_count, column[is_possible].mean()) for name, column in columns.items()}
+    if bootstrap and out:
+        possible = np.stack([column[is_possible] for column in columns.values()])
+        plus_minus = bootstrap_scores(possible, np.asarray([v[0] for v in out.values()]), mapping[is_possible, 0], replicates, seed,
+                                      sample_ids)
+        for i, name in enumerate(out):
+            out[name] = out[name] + (plus_minus[0][i], plus_minus[1][i])
+    return dict(sorted(out.items(), key=lambda item: -item[1][0]))
 
 
 def assemble_grouping(slice_proteins: Sequence[str], db_proteins: Sequence[str] = None):
