@@ -20,8 +20,9 @@
 //            reading the same word (a broadcast).  depth <= 2048 bounds it at 8 k compares per thread; the reference's
 //            depth of 100..1000 is far below that, and the alternative (a second sort by (group, rank), marking heads,
 //            and a scatter back to rank order) costs more than the scan up to that depth.
-//   stage 3  compaction.  Survivors are written in rank order: ballot per wave, the waves' counts through LDS, prefix
-//            (range.inc's epilogue across four waves); the walk stops at k_out and the rest of the row is padding.
+//   stage 3  compaction.  Survivors are written in rank order (eval.inc's wg_dedup_compact does the scan of stage 2 and
+//            this walk: ballot per wave, the waves' counts through LDS, prefix); the walk stops at k_out and the rest of
+//            the row is padding.
 
 struct AssembleParams {
     const int64_t *hits;        // the slab's rows [rows][k]
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleParams p)
     uint64_t *sb = (uint64_t *)smem;          // [N] keys
     int32_t *s_grp = (int32_t *)(sb + p.N);   // [depth] group of rank i, -1 = none
     __shared__ int s_wcnt[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t g = blockIdx.x;
     const int64_t r_lo = p.offs[g], r_hi = p.offs[g + 1];
     const int n = (int)((r_hi - r_lo) * p.k); // (the host refuses groups of 2^31 entries or more)
@@ -74,22 +75,6 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleParams p)
             T = sb[depth - 1];
         }
     };
-    // exclusive position of this lane among the workgroup's lanes with `flag`, and their number
-    auto wg_compact = [&](bool flag, int *total) -> int {
-        const uint64_t m = __ballot(flag);
-        if (lane == 0) s_wcnt[par][wave] = __builtin_popcountll(m);
-        __syncthreads();
-        int pos = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const int c = s_wcnt[par][w];
-            pos += w < wave ? c : 0;
-            tot += c;
-        }
-        par ^= 1; // the next call writes the other set: one barrier per call is enough
-        *total = tot;
-        return pos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    };
 
     // ---- stage 1 ----
     for (int b0 = 0; b0 < n; b0 += 256) {
@@ -101,7 +86,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleParams p)
         const uint64_t key = idx < n ? assemble_key(sc[idx], (uint32_t)idx, p.ascending) : KEY_PAD;
         const bool pass = key < T;
         int tot;
-        const int pos = fill + wg_compact(pass, &tot);
+        const int pos = fill + wg_compact(pass, s_wcnt, par, &tot);
         if (pass) sb[pos] = key;
         fill += tot;
     }
@@ -121,26 +106,14 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleParams p)
     __syncthreads();
 
     // ---- stage 3 ----
-    int emitted = 0;
-    for (int c0 = 0; c0 < m && emitted < k_out; c0 += 256) {
-        const int i = c0 + tid;
-        int32_t gv = -1;
-        if (i < m) gv = s_grp[i];
-        bool keep = gv >= 0;
-        for (int j = 0; keep && j < i; j++) keep = s_grp[j] != gv;
-        int tot;
-        const int pos = emitted + wg_compact(keep, &tot);
-        if (keep && pos < k_out) {
-            const uint32_t pp = (uint32_t)sb[i];
-            const size_t o = (size_t)g * k_out + pos;
-            p.groups_out[o] = gv;
-            p.scores_out[o] = sc[pp];
-            if (p.qrow_out) p.qrow_out[o] = r_lo + pp / (uint32_t)p.k;
-            if (p.hit_out) p.hit_out[o] = hh[pp];
-        }
-        emitted += tot;
-    }
-    emitted = min(emitted, k_out);
+    const int emitted = wg_dedup_compact(s_grp, m, k_out, (int32_t)-1, s_wcnt, par, [&](int pos, int i, int32_t gv) {
+        const uint32_t pp = (uint32_t)sb[i];
+        const size_t o = (size_t)g * k_out + pos;
+        p.groups_out[o] = gv;
+        p.scores_out[o] = sc[pp];
+        if (p.qrow_out) p.qrow_out[o] = r_lo + pp / (uint32_t)p.k;
+        if (p.hit_out) p.hit_out[o] = hh[pp];
+    });
     for (int i = emitted + tid; i < k_out; i += 256) {
         const size_t o = (size_t)g * k_out + i;
         p.groups_out[o] = -1;
@@ -163,10 +136,7 @@ extern "C" int knn_eval_assemble(const int64_t *hits, const float *scores, int64
     if (ng == 0) return 0;
     if (!group_offsets || !groups_out || !scores_out || (ns > 0 && (!hits || !scores)) || (nb > 0 && !row_group))
         return set_err(KNN_ERR_INVALID, "assemble: null pointer");
-    if (group_offsets[0] < 0) return set_err(KNN_ERR_INVALID, "assemble: negative group offset");
-    for (int64_t g = 0; g < ng; g++)
-        if (group_offsets[g + 1] < group_offsets[g]) return set_err(KNN_ERR_INVALID, "assemble: group offsets decrease");
-    if (group_offsets[ng] > ns) return set_err(KNN_ERR_INVALID, "assemble: group offsets past the last row");
+    EVAL_TRY(eval_check_offsets("assemble", "group", group_offsets, ng, ns));
     for (int64_t g = 0; g < ng; g++)
         if (group_offsets[g + 1] - group_offsets[g] > (((int64_t)1 << 31) - 1) / k)
             return set_err(KNN_ERR_INVALID, "assemble: a group of 2^31 entries or more");
@@ -185,53 +155,31 @@ extern "C" int knn_eval_assemble(const int64_t *hits, const float *scores, int64
         cuts.push_back(g1);
         g0 = g1;
     }
-    int P = 64;
-    while (P < depth) P <<= 1;
-    const int N = std::max(2 * P, 1024);
+    const int N = std::max(2 * std::max(64, next_pow2_host(depth)), 1024);
     const size_t lds = (size_t)N * 8 + (size_t)depth * 4;
     EvalBufs bufs;
-    EVAL_ALLOC(d_h, int64_t *, (size_t)max_rows * k * 8);
-    EVAL_ALLOC(d_s, float *, (size_t)max_rows * k * 4);
-    EVAL_ALLOC(d_off, int64_t *, (size_t)(ng + 1) * 8);
-    EVAL_ALLOC(d_rg, int32_t *, (size_t)nb * 4);
-    EVAL_ALLOC(d_self, int32_t *, (size_t)ng * 4);
-    EVAL_ALLOC(d_go, int64_t *, (size_t)max_groups * k_out * 8);
-    EVAL_ALLOC(d_so, float *, (size_t)max_groups * k_out * 4);
-    EVAL_ALLOC(d_qo, int64_t *, qrow_out ? (size_t)max_groups * k_out * 8 : 0);
-    EVAL_ALLOC(d_ho, int64_t *, hit_out ? (size_t)max_groups * k_out * 8 : 0);
-    HIP_TRY(hipMemcpy(d_off, group_offsets, (size_t)(ng + 1) * 8, hipMemcpyHostToDevice));
-    if (nb) HIP_TRY(hipMemcpy(d_rg, row_group, (size_t)nb * 4, hipMemcpyHostToDevice));
-    if (self_group) HIP_TRY(hipMemcpy(d_self, self_group, (size_t)ng * 4, hipMemcpyHostToDevice));
+    // the inputs advance by rows and the outputs (and self_group) by groups: one walker each
+    EvalCols tab(bufs, 1), rows(bufs, max_rows), grp(bufs, max_groups);
+    const int64_t *d_off = tab.in(group_offsets, (size_t)(ng + 1) * 8);
+    const int32_t *d_rg = tab.in(row_group, (size_t)nb * 4);
+    const int64_t *d_h = rows.in(hits, (size_t)k * 8);
+    const float *d_s = rows.in(scores, (size_t)k * 4);
+    const int32_t *d_self = grp.in(self_group, 4);
+    int64_t *d_go = grp.out(groups_out, (size_t)k_out * 8);
+    float *d_so = grp.out(scores_out, (size_t)k_out * 4);
+    int64_t *d_qo = grp.out(qrow_out, (size_t)k_out * 8);
+    int64_t *d_ho = grp.out(hit_out, (size_t)k_out * 8);
+    EVAL_TRY(grp.ready());
+    EVAL_TRY(tab.upload(0, 1));
     for (size_t c = 0; c + 1 < cuts.size(); c++) {
         const int64_t g0 = cuts[c], m = cuts[c + 1] - g0;
-        const int64_t row0 = group_offsets[g0], rows = group_offsets[g0 + m] - row0;
-        if (rows) {
-            HIP_TRY(hipMemcpy(d_h, hits + row0 * k, (size_t)rows * k * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_s, scores + row0 * k, (size_t)rows * k * 4, hipMemcpyHostToDevice));
-        }
-        AssembleParams p;
-        p.hits = d_h;
-        p.scores = d_s;
-        p.offs = d_off + g0;
-        p.row0 = row0;
-        p.row_group = d_rg;
-        p.nb = nb;
-        p.self_group = self_group ? d_self + g0 : nullptr;
-        p.k = (int)k;
-        p.depth = depth;
-        p.k_out = k_out;
-        p.ascending = ascending ? 1 : 0;
-        p.N = N;
-        p.groups_out = d_go;
-        p.scores_out = d_so;
-        p.qrow_out = qrow_out ? d_qo : nullptr;
-        p.hit_out = hit_out ? d_ho : nullptr;
+        const int64_t row0 = group_offsets[g0];
+        EVAL_TRY(rows.upload(row0, group_offsets[g0 + m] - row0));
+        EVAL_TRY(grp.upload(g0, m));
+        const AssembleParams p = {d_h, d_s, d_off + g0, row0, d_rg, nb, d_self, (int)k, depth, k_out, ascending ? 1 : 0, N, d_go, d_so, d_qo, d_ho};
         hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)m), dim3(256), lds, 0, p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(groups_out + g0 * k_out, d_go, (size_t)m * k_out * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scores_out + g0 * k_out, d_so, (size_t)m * k_out * 4, hipMemcpyDeviceToHost));
-        if (qrow_out) HIP_TRY(hipMemcpy(qrow_out + g0 * k_out, d_qo, (size_t)m * k_out * 8, hipMemcpyDeviceToHost));
-        if (hit_out) HIP_TRY(hipMemcpy(hit_out + g0 * k_out, d_ho, (size_t)m * k_out * 8, hipMemcpyDeviceToHost));
+        EVAL_TRY(grp.download(g0, m));
     }
     return 0;
 }

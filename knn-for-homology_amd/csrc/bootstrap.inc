@@ -123,40 +123,26 @@ extern "C" int knn_eval_bootstrap(const uint8_t *is_correct, int64_t nm, int64_t
     const int64_t slab = std::min<int64_t>(std::min(nb, eval_slab_rows((n + 1) / 2)), (int64_t)1 << 20);
     const size_t lds = (size_t)nfam * 8;
     EvalBufs bufs;
-    EVAL_ALLOC(d_ic, uint8_t *, (size_t)nm * n);
-    EVAL_ALLOC(d_fam, int32_t *, (size_t)n * 4);
-    EVAL_ALLOC(d_ids, int32_t *, (size_t)slab * n * 4);
-    EVAL_ALLOC(d_cor, long long *, (size_t)nm * nb * 8);
-    EVAL_ALLOC(d_pre, int32_t *, (size_t)nb * 4);
-    EVAL_ALLOC(d_nor, double *, (size_t)nm * nb * 8);
-    EVAL_ALLOC(d_raw, double *, (size_t)nm * nb * 8);
-    HIP_TRY(hipMemcpy(d_ic, is_correct, (size_t)nm * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_fam, family, (size_t)n * 4, hipMemcpyHostToDevice));
+    EvalCols tab(bufs, 1), w(bufs, slab);
+    const uint8_t *d_ic = tab.in(is_correct, (size_t)nm * n);
+    const int32_t *d_fam = tab.in(family, (size_t)n * 4);
+    long long *d_cor = (long long *)tab.out(correct_out, (size_t)nm * nb * 8);
+    int32_t *d_pre = tab.out(present_out, (size_t)nb * 4);
+    double *d_nor = tab.out(normalized_out, (size_t)nm * nb * 8);
+    double *d_raw = tab.out(raw_out, (size_t)nm * nb * 8);
+    const int32_t *d_ids = w.in(sample_ids, (size_t)n * 4);
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
     HIP_TRY(hipFuncSetAttribute((const void *)bootstrap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (int64_t b0 = 0; b0 < nb; b0 += slab) {
         const int64_t rows = std::min(slab, nb - b0);
-        HIP_TRY(hipMemcpy(d_ids, sample_ids + b0 * n, (size_t)rows * n * 4, hipMemcpyHostToDevice));
+        EVAL_TRY(w.upload(b0, rows));
         for (int64_t m0 = 0; m0 < nm; m0 += 65535) { // (grid.y holds 65535 at most)
-            BootstrapParams p;
-            p.is_correct = d_ic;
-            p.family = d_fam;
-            p.sample_ids = d_ids;
-            p.nb = nb;
-            p.b0 = b0;
-            p.m0 = m0;
-            p.n = (int)n;
-            p.nfam = nfam;
-            p.correct = d_cor;
-            p.present = d_pre;
-            p.normalized = d_nor;
-            p.raw = d_raw;
+            const BootstrapParams p = {d_ic, d_fam, d_ids, nb, b0, m0, (int)n, nfam, d_cor, d_pre, d_nor, d_raw};
             hipLaunchKernelGGL(bootstrap_kernel, dim3((unsigned)rows, (unsigned)std::min<int64_t>(nm - m0, 65535)), dim3(256), lds, 0, p);
             HIP_TRY(hipGetLastError());
         }
     }
-    HIP_TRY(hipMemcpy(correct_out, d_cor, (size_t)nm * nb * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(present_out, d_pre, (size_t)nb * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(normalized_out, d_nor, (size_t)nm * nb * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(raw_out, d_raw, (size_t)nm * nb * 8, hipMemcpyDeviceToHost));
+    EVAL_TRY(tab.download(0, 1));
     return 0;
 }

@@ -9,15 +9,97 @@
 #include <errno.h>
 #include <stdlib.h>
 
+// ---- device helpers shared by the consumers (and by range.inc's epilogue) ---------------------
+// number of set bits of the ballot m below this lane
+__device__ __forceinline__ uint32_t ballot_rank(uint64_t m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// workgroup of 256: exclusive position of this thread among the threads with `flag`, and their number in *total.
+// s_wcnt is an LDS array [2][4] and par the set to write (0 at first): a call writes one set and flips par, so one
+// barrier per call is enough
+__device__ __forceinline__ int wg_compact(bool flag, int (*s_wcnt)[4], int &par, int *total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t m = __ballot(flag);
+    if (lane == 0) s_wcnt[par][wave] = __builtin_popcountll(m);
+    __syncthreads();
+    int pos = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const int c = s_wcnt[par][w];
+        pos += w < wave ? c : 0;
+        tot += c;
+    }
+    par ^= 1;
+    *total = tot;
+    return pos + (int)ballot_rank(m);
+}
+
+// workgroup of 256 over the LDS values s_val[0 .. n) in rank order: rank i survives when its value is not `none` and no
+// earlier rank holds it (a quadratic scan, every lane reading the same word: a broadcast); survivor number `at` gets
+// emit(at, i, value) while at < k_out, and the walk stops once k_out are out.  Returns min(survivors seen, k_out)
+template <typename T, typename Emit>
+__device__ __forceinline__ int wg_dedup_compact(const T *s_val, int n, int k_out, T none, int (*s_wcnt)[4], int &par, Emit emit)
+{
+    const int tid = threadIdx.x;
+    int emitted = 0;
+    for (int c0 = 0; c0 < n && emitted < k_out; c0 += 256) {
+        const int i = c0 + tid;
+        const T v = i < n ? s_val[i] : none;
+        bool keep = v != none;
+        for (int j = 0; keep && j < i; j++) keep = s_val[j] != v;
+        int tot;
+        const int at = emitted + wg_compact(keep, s_wcnt, par, &tot);
+        if (keep && at < k_out) emit(at, i, v);
+        emitted += tot;
+    }
+    return min(emitted, k_out);
+}
+
+// first i in [lo, hi) for which less(i) is false (less: "element i is below the key", true on a prefix); hi when none
+template <typename I, typename Less>
+__device__ __forceinline__ I lower_bound_dev(I lo, I hi, Less less)
+{
+    while (lo < hi) {
+        const I mid = (lo + hi) >> 1;
+        if (less(mid)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// one wave per row, four rows per block of 256 threads: this thread's lane and its wave's row; false (for the whole
+// wave) past the last row
+__device__ __forceinline__ bool wave_row(int64_t nq, int &lane, int64_t &r)
+{
+    lane = threadIdx.x & 63;
+    r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    return r < nq;
+}
+
+// the row's lead (lowest first_bad of the lanes) and tp (sum of their cnt), stored by lane 0
+__device__ __forceinline__ void wave_store_lead_tp(int lane, int first_bad, int cnt, int32_t *lead, int32_t *tp)
+{
+    for (int off = 32; off >= 1; off >>= 1) {
+        cnt += __shfl_xor(cnt, off, 64);
+        first_bad = min(first_bad, __shfl_xor(first_bad, off, 64));
+    }
+    if (lane == 0) {
+        *lead = first_bad;
+        *tp = cnt;
+    }
+}
+
 // out row = in row with the element at `index` removed; index = position of the self id
 // (0 when the search put it first), or k-1 when the row does not contain it (counted missing)
 __global__ void remove_self_hit_kernel(const int64_t *__restrict__ hits, const float *__restrict__ scores, int64_t nq, int k,
                                        const int64_t *__restrict__ self_ids, int64_t *__restrict__ hits_out,
                                        float *__restrict__ scores_out, int32_t *__restrict__ missing)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= nq) return;
+    int lane;
+    int64_t r;
+    if (!wave_row(nq, lane, r)) return;
     const int64_t *h = hits + r * k;
     const float *s = scores + r * k;
     const int64_t self = self_ids[r];
@@ -41,9 +123,9 @@ __global__ void label_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, 
                                   const int32_t *__restrict__ labels_db, int64_t nb, uint8_t *__restrict__ is_correct,
                                   int32_t *__restrict__ lead, int32_t *__restrict__ tp)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= nq) return;
+    int lane;
+    int64_t r;
+    if (!wave_row(nq, lane, r)) return;
     const int32_t lq = labels_q[r];
     int cnt = 0, first_bad = k;
     for (int j = lane; j < k; j += 64) {
@@ -53,14 +135,7 @@ __global__ void label_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, 
         cnt += ok ? 1 : 0;
         if (!ok) first_bad = min(first_bad, j);
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        cnt += __shfl_xor(cnt, off, 64);
-        first_bad = min(first_bad, __shfl_xor(first_bad, off, 64));
-    }
-    if (lane == 0) {
-        lead[r] = first_bad;
-        tp[r] = cnt;
-    }
+    wave_store_lead_tp(lane, first_bad, cnt, lead + r, tp + r);
 }
 
 // set-membership evaluation (pfam/proteins_shared.py:139-157): query r is homologous to the
@@ -71,18 +146,14 @@ __global__ void set_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, in
                                 const int64_t *__restrict__ members, int32_t *__restrict__ lead, int32_t *__restrict__ tp,
                                 uint8_t *__restrict__ is_correct)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= nq) return;
+    int lane;
+    int64_t r;
+    if (!wave_row(nq, lane, r)) return;
     const int64_t lo0 = offsets[r], hi0 = offsets[r + 1];
     int cnt = 0, first_bad = k;
     for (int j = lane; j < k; j += 64) {
         const int64_t hid = hits[r * k + j];
-        int64_t lo = lo0, hi = hi0;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (members[mid] < hid) lo = mid + 1; else hi = mid;
-        }
+        const int64_t lo = lower_bound_dev(lo0, hi0, [&](int64_t i) { return members[i] < hid; });
         const bool ok = lo < hi0 && members[lo] == hid;
         if (MATRIX) {
             is_correct[r * k + j] = ok ? 1 : 0;
@@ -92,23 +163,16 @@ __global__ void set_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, in
         if (!ok) first_bad = min(first_bad, j);
     }
     if (MATRIX) return;
-    for (int off = 32; off >= 1; off >>= 1) {
-        cnt += __shfl_xor(cnt, off, 64);
-        first_bad = min(first_bad, __shfl_xor(first_bad, off, 64));
-    }
-    if (lane == 0) {
-        lead[r] = first_bad;
-        tp[r] = cnt;
-    }
+    wave_store_lead_tp(lane, first_bad, cnt, lead + r, tp + r);
 }
 
 // cath/cath.py:76-84: out[q][l][j] = mapping[query_rows[q]][l] == mapping[hits[q][j]][l]
 __global__ void levels_eval_kernel(const int64_t *__restrict__ hits, int64_t nq, int k, const int64_t *__restrict__ query_rows,
                                    const int32_t *__restrict__ mapping, int64_t n, int nlevels, uint8_t *__restrict__ out)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= nq) return;
+    int lane;
+    int64_t r;
+    if (!wave_row(nq, lane, r)) return;
     const int64_t qrow = query_rows[r];
     for (int j = lane; j < k; j += 64) {
         const int64_t hid = hits[r * k + j];
@@ -122,18 +186,80 @@ __global__ void levels_eval_kernel(const int64_t *__restrict__ hits, int64_t nq,
 // ---- host wrappers: host buffers in and out, rows processed in slabs -------------------------
 struct EvalBufs {
     std::vector<std::pair<void *, size_t>> dev;
+    bool oom = false; // a get() has failed
     ~EvalBufs() { for (auto &b : dev) if (b.first) (void)hipFree(b.first); }
     void *get(size_t bytes)
     {
         void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
+            oom = true;
+            return nullptr;
+        }
         dev.push_back({p, bytes});
         return p;
     }
 };
+// a device-only buffer
 #define EVAL_ALLOC(var, type, bytes)                                                    \
     type var = (type)bufs.get(bytes);                                                   \
     if (!var) return set_err(KNN_ERR_HIP, "eval: out of device memory")
+#define EVAL_TRY(expr)                                                                  \
+    do {                                                                                \
+        const int rc_ = (expr);                                                         \
+        if (rc_) return rc_;                                                            \
+    } while (0)
+
+// The slab walker: the columns that travel between the host and the device.  A column is declared once -- host pointer,
+// bytes per row, input or output -- which allocates `cap` rows of it through EvalBufs and registers its copy; upload and
+// download then move the rows [r0, r0 + m) of every input and of every output column (synchronous copies on the null
+// stream, in the order of the declarations).  A null host pointer, an optional column that the caller left out, gives
+// a null device pointer: no allocation and no copy.  A whole-call table or accumulator is a column of a walker of one
+// row (cap 1, the row being the table): upload(0, 1) once in front of the slabs, download(0, 1) once behind them.
+// ready() after the declarations reports a failed allocation.
+struct EvalCols {
+    struct Col {
+        const char *src; // host source of an input, or null
+        char *dst;       // host target of an output, or null
+        char *dev;
+        size_t row;
+    };
+    EvalBufs &bufs;
+    const int64_t cap;
+    std::vector<Col> cols;
+    EvalCols(EvalBufs &b, int64_t cap_rows) : bufs(b), cap(cap_rows) {}
+    void *add(const void *src, void *dst, size_t row)
+    {
+        if (!src && !dst) return nullptr;
+        char *d = (char *)bufs.get((size_t)cap * row);
+        cols.push_back({(const char *)src, (char *)dst, d, row});
+        return d;
+    }
+    template <typename T> T *in(const T *host, size_t row_bytes) { return (T *)add(host, nullptr, row_bytes); }
+    template <typename T> T *out(T *host, size_t row_bytes) { return (T *)add(nullptr, host, row_bytes); }
+    int ready() const { return bufs.oom ? set_err(KNN_ERR_HIP, "eval: out of device memory") : 0; }
+    int upload(int64_t r0, int64_t m) const
+    {
+        for (const Col &c : cols)
+            if (c.src && m * c.row) HIP_TRY(hipMemcpy(c.dev, c.src + (size_t)r0 * c.row, (size_t)m * c.row, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int download(int64_t r0, int64_t m) const
+    {
+        for (const Col &c : cols)
+            if (c.dst && m * c.row) HIP_TRY(hipMemcpy(c.dst + (size_t)r0 * c.row, c.dev, (size_t)m * c.row, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
+// offs[0 .. n] start at or above 0 and never decrease; limit >= 0: and end at or below limit (rows)
+static int eval_check_offsets(const std::string &who, const char *noun, const int64_t *offs, int64_t n, int64_t limit = -1)
+{
+    if (offs[0] < 0) return set_err(KNN_ERR_INVALID, who + ": negative " + noun + " offset");
+    for (int64_t i = 0; i < n; i++)
+        if (offs[i + 1] < offs[i]) return set_err(KNN_ERR_INVALID, who + ": " + noun + " offsets decrease");
+    if (limit >= 0 && offs[n] > limit) return set_err(KNN_ERR_INVALID, who + ": " + noun + " offsets past the last row");
+    return 0;
+}
 
 // rows per slab: 256 MiB of hits.  KNN355_EVAL_SLAB_ROWS (read on every call; a positive decimal integer, anything else
 // is ignored) replaces the count, so that a test crosses slab boundaries with a handful of rows
@@ -162,22 +288,20 @@ extern "C" int knn_eval_remove_self_hit(const int64_t *hits, const float *scores
     if (rc) return rc;
     EvalBufs bufs;
     const int64_t slab = std::min(nq, eval_slab_rows(k));
-    EVAL_ALLOC(d_h, int64_t *, (size_t)slab * k * 8);
-    EVAL_ALLOC(d_s, float *, (size_t)slab * k * 4);
-    EVAL_ALLOC(d_self, int64_t *, (size_t)slab * 8);
-    EVAL_ALLOC(d_ho, int64_t *, (size_t)slab * (k - 1) * 8);
-    EVAL_ALLOC(d_so, float *, (size_t)slab * (k - 1) * 4);
-    EVAL_ALLOC(d_m, int32_t *, (size_t)slab * 4);
+    EvalCols w(bufs, slab);
+    const int64_t *d_h = w.in(hits, (size_t)k * 8);
+    const float *d_s = w.in(scores, (size_t)k * 4);
+    const int64_t *d_self = w.in(self_ids, 8);
+    int64_t *d_ho = w.out(hits_out, (size_t)(k - 1) * 8);
+    float *d_so = w.out(scores_out, (size_t)(k - 1) * 4);
+    int32_t *d_m = w.out(missing_out, 4);
+    EVAL_TRY(w.ready());
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        HIP_TRY(hipMemcpy(d_h, hits + r0 * k, (size_t)m * k * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_s, scores + r0 * k, (size_t)m * k * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_self, self_ids + r0, (size_t)m * 8, hipMemcpyHostToDevice));
+        EVAL_TRY(w.upload(r0, m));
         hipLaunchKernelGGL(remove_self_hit_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, d_s, m, (int)k, d_self, d_ho, d_so, d_m);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(hits_out + r0 * (k - 1), d_ho, (size_t)m * (k - 1) * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scores_out + r0 * (k - 1), d_so, (size_t)m * (k - 1) * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(missing_out + r0, d_m, (size_t)m * 4, hipMemcpyDeviceToHost));
+        EVAL_TRY(w.download(r0, m));
     }
     return 0;
 }
@@ -193,23 +317,21 @@ extern "C" int knn_eval_labels(const int64_t *hits, int64_t nq, int64_t k, const
     if (rc) return rc;
     EvalBufs bufs;
     const int64_t slab = std::min(nq, eval_slab_rows(k));
-    EVAL_ALLOC(d_h, int64_t *, (size_t)slab * k * 8);
-    EVAL_ALLOC(d_lq, int32_t *, (size_t)slab * 4);
-    EVAL_ALLOC(d_ldb, int32_t *, (size_t)nb * 4);
-    EVAL_ALLOC(d_ic, uint8_t *, (size_t)slab * k);
-    EVAL_ALLOC(d_lead, int32_t *, (size_t)slab * 4);
-    EVAL_ALLOC(d_tp, int32_t *, (size_t)slab * 4);
-    if (nb) HIP_TRY(hipMemcpy(d_ldb, labels_db, (size_t)nb * 4, hipMemcpyHostToDevice));
+    EvalCols tab(bufs, 1), w(bufs, slab);
+    const int32_t *d_ldb = tab.in(labels_db, (size_t)nb * 4);
+    const int64_t *d_h = w.in(hits, (size_t)k * 8);
+    const int32_t *d_lq = w.in(labels_q, 4);
+    uint8_t *d_ic = w.out(is_correct_out, (size_t)k);
+    int32_t *d_lead = w.out(lead_out, 4);
+    int32_t *d_tp = w.out(tp_out, 4);
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        HIP_TRY(hipMemcpy(d_h, hits + r0 * k, (size_t)m * k * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_lq, labels_q + r0, (size_t)m * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(label_eval_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_lq, d_ldb, nb,
-                           is_correct_out ? d_ic : (uint8_t *)nullptr, d_lead, d_tp);
+        EVAL_TRY(w.upload(r0, m));
+        hipLaunchKernelGGL(label_eval_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_lq, d_ldb, nb, d_ic, d_lead, d_tp);
         HIP_TRY(hipGetLastError());
-        if (is_correct_out) HIP_TRY(hipMemcpy(is_correct_out + r0 * k, d_ic, (size_t)m * k, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(lead_out + r0, d_lead, (size_t)m * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tp_out + r0, d_tp, (size_t)m * 4, hipMemcpyDeviceToHost));
+        EVAL_TRY(w.download(r0, m));
     }
     return 0;
 }
@@ -223,9 +345,7 @@ static int eval_sets_run(const int64_t *hits, int64_t nq, int64_t k, const int64
     if (nq == 0) return 0;
     if (!hits || !set_offsets || (matrix ? !is_correct_out : (!lead_out || !tp_out))) return set_err(KNN_ERR_INVALID, "eval_sets: null pointer");
     // the kernel binary-searches set_members[set_offsets[r] .. set_offsets[r+1]) without further checks
-    if (set_offsets[0] < 0) return set_err(KNN_ERR_INVALID, "eval_sets: negative set offset");
-    for (int64_t r = 0; r < nq; r++)
-        if (set_offsets[r + 1] < set_offsets[r]) return set_err(KNN_ERR_INVALID, "eval_sets: set offsets decrease");
+    EVAL_TRY(eval_check_offsets("eval_sets", "set", set_offsets, nq));
     const int64_t nmem = set_offsets[nq];
     if (nmem > 0 && !set_members) return set_err(KNN_ERR_INVALID, "eval_sets: null pointer");
     for (int64_t r = 0; r < nq; r++)
@@ -235,29 +355,22 @@ static int eval_sets_run(const int64_t *hits, int64_t nq, int64_t k, const int64
     if (rc) return rc;
     EvalBufs bufs;
     const int64_t slab = std::min(nq, eval_slab_rows(k));
-    EVAL_ALLOC(d_h, int64_t *, (size_t)slab * k * 8);
-    EVAL_ALLOC(d_off, int64_t *, (size_t)(nq + 1) * 8);
-    EVAL_ALLOC(d_mem, int64_t *, (size_t)nmem * 8);
-    EVAL_ALLOC(d_lead, int32_t *, matrix ? 0 : (size_t)slab * 4);
-    EVAL_ALLOC(d_tp, int32_t *, matrix ? 0 : (size_t)slab * 4);
-    EVAL_ALLOC(d_ic, uint8_t *, matrix ? (size_t)slab * k : 0);
-    HIP_TRY(hipMemcpy(d_off, set_offsets, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice));
-    if (nmem) HIP_TRY(hipMemcpy(d_mem, set_members, (size_t)nmem * 8, hipMemcpyHostToDevice));
+    EvalCols tab(bufs, 1), w(bufs, slab);
+    const int64_t *d_off = tab.in(set_offsets, (size_t)(nq + 1) * 8);
+    const int64_t *d_mem = tab.in(set_members, (size_t)nmem * 8);
+    const int64_t *d_h = w.in(hits, (size_t)k * 8);
+    int32_t *d_lead = w.out(lead_out, 4); // (the matrix build has is_correct_out alone, the other build lead_out and tp_out)
+    int32_t *d_tp = w.out(tp_out, 4);
+    uint8_t *d_ic = w.out(is_correct_out, (size_t)k);
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
+    const auto kern = matrix ? set_eval_kernel<true> : set_eval_kernel<false>;
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        HIP_TRY(hipMemcpy(d_h, hits + r0 * k, (size_t)m * k * 8, hipMemcpyHostToDevice));
-        if (matrix) {
-            hipLaunchKernelGGL(set_eval_kernel<true>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_off + r0, d_mem,
-                               d_lead, d_tp, d_ic);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpy(is_correct_out + r0 * k, d_ic, (size_t)m * k, hipMemcpyDeviceToHost));
-            continue;
-        }
-        hipLaunchKernelGGL(set_eval_kernel<false>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_off + r0, d_mem,
-                           d_lead, d_tp, d_ic);
+        EVAL_TRY(w.upload(r0, m));
+        hipLaunchKernelGGL(kern, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_off + r0, d_mem, d_lead, d_tp, d_ic);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(lead_out + r0, d_lead, (size_t)m * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tp_out + r0, d_tp, (size_t)m * 4, hipMemcpyDeviceToHost));
+        EVAL_TRY(w.download(r0, m));
     }
     return 0;
 }
@@ -287,18 +400,19 @@ extern "C" int knn_eval_levels(const int64_t *hits, int64_t nq, int64_t k, const
     if (rc) return rc;
     EvalBufs bufs;
     const int64_t slab = std::min(nq, eval_slab_rows(k));
-    EVAL_ALLOC(d_h, int64_t *, (size_t)slab * k * 8);
-    EVAL_ALLOC(d_q, int64_t *, (size_t)slab * 8);
-    EVAL_ALLOC(d_map, int32_t *, (size_t)n * nlevels * 4);
-    EVAL_ALLOC(d_out, uint8_t *, (size_t)slab * nlevels * k);
-    HIP_TRY(hipMemcpy(d_map, mapping, (size_t)n * nlevels * 4, hipMemcpyHostToDevice));
+    EvalCols tab(bufs, 1), w(bufs, slab);
+    const int32_t *d_map = tab.in(mapping, (size_t)n * nlevels * 4);
+    const int64_t *d_h = w.in(hits, (size_t)k * 8);
+    const int64_t *d_q = w.in(query_rows, 8);
+    uint8_t *d_out = w.out(out, (size_t)nlevels * k);
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        HIP_TRY(hipMemcpy(d_h, hits + r0 * k, (size_t)m * k * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_q, query_rows + r0, (size_t)m * 8, hipMemcpyHostToDevice));
+        EVAL_TRY(w.upload(r0, m));
         hipLaunchKernelGGL(levels_eval_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_q, d_map, n, (int)nlevels, d_out);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(out + (size_t)r0 * nlevels * k, d_out, (size_t)m * nlevels * k, hipMemcpyDeviceToHost));
+        EVAL_TRY(w.download(r0, m));
     }
     return 0;
 }

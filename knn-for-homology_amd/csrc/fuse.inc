@@ -19,7 +19,8 @@
 //     stage 2  the id of every rank goes to LDS (-1 for a slot that holds no entry: existing ids are never negative).
 //     stage 3  rank i is a repeat when an earlier rank holds its id: a quadratic scan of the LDS ids, every lane reading
 //              the same word (a broadcast), at most 4096 compares per entry and 16 entries per thread.  Survivors are
-//              compacted in rank order by ballot and prefix across the four waves; the walk stops at k_out.
+//              compacted in rank order by ballot and prefix across the four waves; the walk stops at k_out (stage 3 is
+//              eval.inc's wg_dedup_compact, the compaction of the prefix mode its wg_compact).
 //   prefix, then fill (KNN_FUSE_PREFIX_FILL)
 //     no sort.  A's existing entries are compacted in column order into the output and their ids into LDS; then B's
 //     entries whose id a linear (broadcast) scan does not find there are compacted behind them.
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseParams p)
     int64_t *s_id = (int64_t *)(smem + 32);           // [Pid]
     uint64_t *s_key = (uint64_t *)(s_id + p.Pid);     // [P]   (sorted union only)
     uint16_t *s_pos = (uint16_t *)(s_key + p.P);      // [P]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const size_t q = blockIdx.x;
     const int ka = p.ka, kb = p.kb, k_out = p.k_out, n = ka + kb;
     const int64_t *ha = p.ha + q * ka, *hb = p.hb + q * kb;
@@ -66,22 +67,6 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseParams p)
     int32_t *src = p.src ? p.src + q * k_out : nullptr;
     int par = 0;
 
-    // exclusive position of this lane among the workgroup's lanes with `flag`, and their number
-    auto wg_compact = [&](bool flag, int *total) -> int {
-        const uint64_t m = __ballot(flag);
-        if (lane == 0) s_wcnt[par][wave] = __builtin_popcountll(m);
-        __syncthreads();
-        int pos = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const int c = s_wcnt[par][w];
-            pos += w < wave ? c : 0;
-            tot += c;
-        }
-        par ^= 1; // the next call writes the other set: one barrier per call is enough
-        *total = tot;
-        return pos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    };
     auto emit = [&](int at, int64_t id, uint64_t bits, int pos) {
         ho[at] = id;
         so[at] = bits;
@@ -114,26 +99,17 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseParams p)
         }
         __syncthreads();
         // ---- stage 3 ----
-        for (int c0 = 0; c0 < n && emitted < k_out; c0 += 256) {
-            const int i = c0 + tid;
-            const int64_t id = i < n ? s_id[i] : -1;
-            bool ok = id >= 0;
-            for (int j = 0; ok && j < i; j++) ok = s_id[j] != id;
-            int tot;
-            const int at = emitted + wg_compact(ok, &tot);
-            if (ok && at < k_out) {
-                const int pos = s_pos[i];
-                emit(at, id, pos < ka ? sa[pos] : sb[pos - ka], pos);
-            }
-            emitted += tot;
-        }
+        emitted = wg_dedup_compact(s_id, n, k_out, (int64_t)-1, s_wcnt, par, [&](int at, int i, int64_t id) {
+            const int pos = s_pos[i];
+            emit(at, id, pos < ka ? sa[pos] : sb[pos - ka], pos);
+        });
     } else {
         for (int c0 = 0; c0 < ka; c0 += 256) {
             const int i = c0 + tid;
             const int64_t h = i < ka ? ha[i] : -1;
             const bool ok = h >= 0 && (!keep || keep[i]);
             int tot;
-            const int at = emitted + wg_compact(ok, &tot);
+            const int at = emitted + wg_compact(ok, s_wcnt, par, &tot);
             if (ok) {
                 s_id[at] = h; // (at < ka <= Pid)
                 if (at < k_out) emit(at, h, sa[i], i);
@@ -148,12 +124,12 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseParams p)
             bool ok = h >= 0;
             for (int j = 0; ok && j < na; j++) ok = s_id[j] != h;
             int tot;
-            const int at = emitted + wg_compact(ok, &tot);
+            const int at = emitted + wg_compact(ok, s_wcnt, par, &tot);
             if (ok && at < k_out) emit(at, h, sb[i], ka + i);
             emitted += tot;
         }
+        emitted = min(emitted, k_out);
     }
-    emitted = min(emitted, k_out);
     const double padv = p.ascending ? DBL_MAX : -DBL_MAX;
     for (int i = emitted + tid; i < k_out; i += 256) emit(i, -1, (uint64_t)__double_as_longlong(padv), -1);
     if (tid == 0) p.filled[q] = emitted;
@@ -176,48 +152,29 @@ extern "C" int knn_eval_fuse(const int64_t *hits_a, const double *scores_a, cons
     if (rc) return rc;
     const int n = (int)(ka + kb);
     const int64_t slab = std::min(nq, eval_slab_rows(n));
-    FuseParams p;
-    p.ka = (int)ka;
-    p.kb = (int)kb;
-    p.k_out = k_out;
-    p.mode = mode;
-    p.ascending = ascending ? 1 : 0;
-    p.P = mode == KNN_FUSE_SORTED_UNION ? next_pow2_host(n) : 0;
-    p.Pid = mode == KNN_FUSE_SORTED_UNION ? p.P : next_pow2_host((int)ka);
-    const size_t lds = 32 + (size_t)p.Pid * 8 + (size_t)p.P * (8 + 2); // 72 KB + 32 at ka + kb = 4096
+    const int P = mode == KNN_FUSE_SORTED_UNION ? next_pow2_host(n) : 0;
+    const int Pid = mode == KNN_FUSE_SORTED_UNION ? P : next_pow2_host((int)ka);
+    const size_t lds = 32 + (size_t)Pid * 8 + (size_t)P * (8 + 2); // 72 KB + 32 at ka + kb = 4096
     HIP_TRY(hipFuncSetAttribute((const void *)fuse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     EvalBufs bufs;
-    EVAL_ALLOC(d_ha, int64_t *, (size_t)slab * ka * 8);
-    EVAL_ALLOC(d_sa, uint64_t *, (size_t)slab * ka * 8);
-    EVAL_ALLOC(d_keep, uint8_t *, keep_a ? (size_t)slab * ka : 0);
-    EVAL_ALLOC(d_hb, int64_t *, (size_t)slab * kb * 8);
-    EVAL_ALLOC(d_sb, uint64_t *, (size_t)slab * kb * 8);
-    EVAL_ALLOC(d_ho, int64_t *, (size_t)slab * k_out * 8);
-    EVAL_ALLOC(d_so, uint64_t *, (size_t)slab * k_out * 8);
-    EVAL_ALLOC(d_src, int32_t *, source_out ? (size_t)slab * k_out * 4 : 0);
-    EVAL_ALLOC(d_fill, int32_t *, (size_t)slab * 4);
-    p.ha = d_ha;
-    p.sa = d_sa;
-    p.keep = keep_a ? d_keep : nullptr;
-    p.hb = d_hb;
-    p.sb = d_sb;
-    p.ho = d_ho;
-    p.so = d_so;
-    p.src = source_out ? d_src : nullptr;
-    p.filled = d_fill;
+    EvalCols w(bufs, slab);
+    const FuseParams p = {w.in(hits_a, (size_t)ka * 8),
+                          w.in(hits_b, (size_t)kb * 8),
+                          (const uint64_t *)w.in(scores_a, (size_t)ka * 8),
+                          (const uint64_t *)w.in(scores_b, (size_t)kb * 8),
+                          w.in(keep_a, (size_t)ka),
+                          (int)ka, (int)kb, k_out, mode, ascending ? 1 : 0, P, Pid,
+                          w.out(hits_out, (size_t)k_out * 8),
+                          (uint64_t *)w.out(scores_out, (size_t)k_out * 8),
+                          w.out(source_out, (size_t)k_out * 4),
+                          w.out(filled_out, 4)};
+    EVAL_TRY(w.ready());
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        HIP_TRY(hipMemcpy(d_ha, hits_a + r0 * ka, (size_t)m * ka * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sa, scores_a + r0 * ka, (size_t)m * ka * 8, hipMemcpyHostToDevice));
-        if (keep_a) HIP_TRY(hipMemcpy(d_keep, keep_a + r0 * ka, (size_t)m * ka, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_hb, hits_b + r0 * kb, (size_t)m * kb * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sb, scores_b + r0 * kb, (size_t)m * kb * 8, hipMemcpyHostToDevice));
+        EVAL_TRY(w.upload(r0, m));
         hipLaunchKernelGGL(fuse_kernel, dim3((unsigned)m), dim3(256), lds, 0, p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(hits_out + r0 * k_out, d_ho, (size_t)m * k_out * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scores_out + r0 * k_out, d_so, (size_t)m * k_out * 8, hipMemcpyDeviceToHost));
-        if (source_out) HIP_TRY(hipMemcpy(source_out + r0 * k_out, d_src, (size_t)m * k_out * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(filled_out + r0, d_fill, (size_t)m * 4, hipMemcpyDeviceToHost));
+        EVAL_TRY(w.download(r0, m));
     }
     return 0;
 }

@@ -62,11 +62,7 @@ __global__ __launch_bounds__(256) void pr_curve_kernel(PrCurveParams p)
         const uint8_t *ic = p.is_correct + r * p.k;
         for (int c = tid; c < limit; c += 256) {
             const double v = (double)sc[c];
-            int lo = 0, hi = nthr;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s_thr[mid] < v) lo = mid + 1; else hi = mid;
-            }
+            const int lo = lower_bound_dev(0, nthr, [&](int i) { return s_thr[i] < v; });
             if (lo) atomicAdd(&s_h[lo - 1], (1ull << 32) | (ic[c] ? 1ull : 0ull));
         }
         const double total = (double)p.totals[r];
@@ -170,34 +166,25 @@ extern "C" int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores,
     const int64_t rows_cap = std::min(slab, nq), blocks_cap = slab / 256;
     const size_t lds = (size_t)nthr * 16;
     EvalBufs bufs;
-    EVAL_ALLOC(d_ic, uint8_t *, (size_t)rows_cap * k);
-    EVAL_ALLOC(d_sc, float *, (size_t)rows_cap * k * 4);
-    EVAL_ALLOC(d_tot, int64_t *, (size_t)rows_cap * 8);
-    EVAL_ALLOC(d_thr, double *, (size_t)nthr * 8);
+    std::vector<double> sums((size_t)nthr * 2);
+    std::vector<int64_t> cnt((size_t)nthr * 3);
+    EvalCols tab(bufs, 1), w(bufs, rows_cap);
+    const double *d_thr = tab.in(thresholds, (size_t)nthr * 8);
+    double *d_sums = tab.out(sums.data(), sums.size() * 8);
+    unsigned long long *d_cnt = (unsigned long long *)tab.out(cnt.data(), cnt.size() * 8);
+    const uint8_t *d_ic = w.in(is_correct, (size_t)k);
+    const float *d_sc = w.in(scores, (size_t)k * 4);
+    const int64_t *d_tot = w.in(totals, 8);
     EVAL_ALLOC(d_bp, double *, (size_t)blocks_cap * nthr * 8);
     EVAL_ALLOC(d_br, double *, (size_t)blocks_cap * nthr * 8);
-    EVAL_ALLOC(d_sums, double *, (size_t)nthr * 2 * 8);
-    EVAL_ALLOC(d_cnt, unsigned long long *, (size_t)nthr * 3 * 8);
-    HIP_TRY(hipMemcpy(d_thr, thresholds, (size_t)nthr * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_sums, 0, (size_t)nthr * 2 * 8)); // (all bits zero: +0.0)
-    HIP_TRY(hipMemset(d_cnt, 0, (size_t)nthr * 3 * 8));
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
+    HIP_TRY(hipMemset(d_sums, 0, sums.size() * 8)); // (all bits zero: +0.0)
+    HIP_TRY(hipMemset(d_cnt, 0, cnt.size() * 8));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0), blocks = (m + 255) / 256;
-        HIP_TRY(hipMemcpy(d_ic, is_correct + r0 * k, (size_t)m * k, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sc, scores + r0 * k, (size_t)m * k * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_tot, totals + r0, (size_t)m * 8, hipMemcpyHostToDevice));
-        PrCurveParams p;
-        p.is_correct = d_ic;
-        p.scores = d_sc;
-        p.totals = d_tot;
-        p.thr = d_thr;
-        p.rows = m;
-        p.k = (int)k;
-        p.limit = (int)limit;
-        p.nthr = nthr;
-        p.block_p = d_bp;
-        p.block_r = d_br;
-        p.counts = d_cnt;
+        EVAL_TRY(w.upload(r0, m));
+        const PrCurveParams p = {d_ic, d_sc, d_tot, d_thr, m, (int)k, (int)limit, nthr, d_bp, d_br, d_cnt};
         if (nthr <= 256) rc = pr_curve_launch<1>(p, blocks, lds);
         else if (nthr <= 512) rc = pr_curve_launch<2>(p, blocks, lds);
         else if (nthr <= 1024) rc = pr_curve_launch<4>(p, blocks, lds);
@@ -207,10 +194,7 @@ extern "C" int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores,
         hipLaunchKernelGGL(pr_fold_kernel, dim3(1), dim3(256), 0, 0, d_bp, d_br, blocks, (int)nthr, d_sums);
         HIP_TRY(hipGetLastError());
     }
-    std::vector<double> sums((size_t)nthr * 2);
-    std::vector<int64_t> cnt((size_t)nthr * 3);
-    HIP_TRY(hipMemcpy(sums.data(), d_sums, sums.size() * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cnt.data(), d_cnt, cnt.size() * 8, hipMemcpyDeviceToHost));
+    EVAL_TRY(tab.download(0, 1));
     for (int32_t j = 0; j < nthr; j++) {
         precision_out[j] = sums[(size_t)j] / (double)nq;
         recall_out[j] = sums[(size_t)nthr + j] / (double)nq;

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void range_scan_kernel(RangeParams p)
                 const bool pass = row0 + r < c_hi && v < p.vthr;
                 const uint64_t m = __ballot(pass);
                 if (m == 0ull) continue;
-                const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                const uint32_t pre = ballot_rank(m); // (eval.inc)
                 const int64_t pos = (int64_t)cnt + pre;
                 if (pass && pos < lim) {
                     p.outD[base + pos] = L2 ? v : -v;

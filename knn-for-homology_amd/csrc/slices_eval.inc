@@ -24,16 +24,6 @@
 // same line instead of three arrays; and the annotate kernel walks the slices with a grid-stride loop, so the grid stays
 // small whatever ns is.
 
-// exclusive lower bound of family a among dom[lo .. hi) (sorted by .x)
-__device__ __forceinline__ int64_t slice_family_lower_bound(const int4 *__restrict__ dom, int64_t lo, int64_t hi, int32_t a)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (dom[mid].x < a) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void slice_annotate_kernel(const int32_t *__restrict__ slice_protein, const int32_t *__restrict__ slice_start,
                                                              const int32_t *__restrict__ slice_stop, int64_t ns,
                                                              const int64_t *__restrict__ doff, const int4 *__restrict__ dom,
@@ -68,9 +58,9 @@ __global__ __launch_bounds__(256) void slice_eval_kernel(const int64_t *__restri
                                                          int32_t *__restrict__ lead, int32_t *__restrict__ tp,
                                                          unsigned long long *__restrict__ column_correct)
 {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= nq) return; // (the whole wave)
+    int lane;
+    int64_t r;
+    if (!wave_row(nq, lane, r)) return;
     const int32_t a = query_family[r];
     const int64_t *h = hits + r * k;
     uint8_t *ic = is_correct + r * k, *ig = is_ignore + r * k;
@@ -87,7 +77,8 @@ __global__ __launch_bounds__(256) void slice_eval_kernel(const int64_t *__restri
                 ignore = ignore_unannotated && s.w == 0;
                 if (s.x >= 0) {
                     const int64_t hi = doff[s.x + 1];
-                    for (int64_t d = slice_family_lower_bound(dom, doff[s.x], hi, a); d < hi; d++) {
+                    // (the protein's domains are sorted by family: the run of family a starts at its lower bound)
+                    for (int64_t d = lower_bound_dev(doff[s.x], hi, [&](int64_t i) { return dom[i].x < a; }); d < hi; d++) {
                         const int4 m = dom[d];
                         if (m.x != a) break;
                         if (s.y <= m.y && m.z <= s.z) correct = true;
@@ -129,9 +120,7 @@ static int slices_check_tables(const char *who, const int32_t *slice_protein, co
     if (np > (int64_t)INT32_MAX) return set_err(KNN_ERR_INVALID, w + ": np > INT32_MAX");
     int64_t nd = 0;
     if (np > 0) {
-        if (domain_offsets[0] < 0) return set_err(KNN_ERR_INVALID, w + ": negative domain offset");
-        for (int64_t p = 0; p < np; p++)
-            if (domain_offsets[p + 1] < domain_offsets[p]) return set_err(KNN_ERR_INVALID, w + ": domain offsets decrease");
+        EVAL_TRY(eval_check_offsets(w, "domain", domain_offsets, np));
         nd = domain_offsets[np];
     }
     if (nd > 0 && (!domain_family || !domain_start || !domain_stop)) return set_err(KNN_ERR_INVALID, w + ": null pointer");
@@ -146,22 +135,17 @@ static int slices_check_tables(const char *who, const int32_t *slice_protein, co
     return 0;
 }
 
-// {family, start, stop, 0} per domain, on the device; d_off gets the offsets (one zero when np is 0)
-static int slices_upload_domains(EvalBufs &bufs, const int64_t *domain_offsets, const int32_t *domain_family, const int32_t *domain_start,
-                                 const int32_t *domain_stop, int64_t np, int64_t **d_off_out, int4 **d_dom_out)
+// the domain tables as columns of the whole-call walker: the offsets, and {family, start, stop, 0} per domain packed into
+// `packed`, which the caller keeps until the upload (np == 0: no slice has a protein, nothing reads either)
+static void slices_domain_columns(EvalCols &tab, const int64_t *domain_offsets, const int32_t *domain_family, const int32_t *domain_start,
+                                  const int32_t *domain_stop, int64_t np, std::vector<int4> &packed, const int64_t **d_off,
+                                  const int4 **d_dom)
 {
     const int64_t nd = np > 0 ? domain_offsets[np] : 0, d0 = np > 0 ? domain_offsets[0] : 0;
-    EVAL_ALLOC(d_off, int64_t *, (size_t)(np + 1) * 8);
-    EVAL_ALLOC(d_dom, int4 *, (size_t)nd * 16);
-    if (np > 0) HIP_TRY(hipMemcpy(d_off, domain_offsets, (size_t)(np + 1) * 8, hipMemcpyHostToDevice));
-    if (nd > d0) {
-        std::vector<int4> packed((size_t)(nd - d0));
-        for (int64_t d = d0; d < nd; d++) packed[(size_t)(d - d0)] = make_int4(domain_family[d], domain_start[d], domain_stop[d], 0);
-        HIP_TRY(hipMemcpy(d_dom + d0, packed.data(), packed.size() * 16, hipMemcpyHostToDevice));
-    }
-    *d_off_out = d_off;
-    *d_dom_out = d_dom;
-    return 0;
+    packed.assign((size_t)nd, make_int4(0, 0, 0, 0));
+    for (int64_t d = d0; d < nd; d++) packed[(size_t)d] = make_int4(domain_family[d], domain_start[d], domain_stop[d], 0);
+    *d_off = tab.in(np > 0 ? domain_offsets : nullptr, (size_t)(np + 1) * 8);
+    *d_dom = tab.in(packed.data(), (size_t)nd * 16);
 }
 
 extern "C" int knn_eval_slice_annotate(const int32_t *slice_protein, const int32_t *slice_start, const int32_t *slice_stop, int64_t ns,
@@ -181,26 +165,26 @@ extern "C" int knn_eval_slice_annotate(const int32_t *slice_protein, const int32
     rc = ensure_device(g_device);
     if (rc) return rc;
     EvalBufs bufs;
-    int64_t *d_off;
-    int4 *d_dom;
-    rc = slices_upload_domains(bufs, domain_offsets, domain_family, domain_start, domain_stop, np, &d_off, &d_dom);
-    if (rc) return rc;
-    EVAL_ALLOC(d_sp, int32_t *, (size_t)ns * 4);
-    EVAL_ALLOC(d_s0, int32_t *, (size_t)ns * 4);
-    EVAL_ALLOC(d_s1, int32_t *, (size_t)ns * 4);
-    EVAL_ALLOC(d_mc, int32_t *, (size_t)ns * 4);
-    EVAL_ALLOC(d_an, int32_t *, (size_t)ns * 4);
-    EVAL_ALLOC(d_fs, unsigned long long *, (size_t)nfam * 8);
-    HIP_TRY(hipMemcpy(d_sp, slice_protein, (size_t)ns * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_s0, slice_start, (size_t)ns * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_s1, slice_stop, (size_t)ns * 4, hipMemcpyHostToDevice));
+    EvalCols tab(bufs, 1), w(bufs, ns); // (the slices go in one slab: a slice is 12 bytes in and 8 out)
+    std::vector<int4> packed;
+    const int64_t *d_off;
+    const int4 *d_dom;
+    slices_domain_columns(tab, domain_offsets, domain_family, domain_start, domain_stop, np, packed, &d_off, &d_dom);
+    unsigned long long *d_fs = (unsigned long long *)tab.out(family_sizes, (size_t)nfam * 8);
+    const int32_t *d_sp = w.in(slice_protein, 4);
+    const int32_t *d_s0 = w.in(slice_start, 4);
+    const int32_t *d_s1 = w.in(slice_stop, 4);
+    int32_t *d_mc = w.out(match_count, 4);
+    int32_t *d_an = w.out(annotation, 4);
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
+    EVAL_TRY(w.upload(0, ns));
     if (nfam) HIP_TRY(hipMemset(d_fs, 0, (size_t)nfam * 8));
     const unsigned grid = (unsigned)std::min<int64_t>((ns + 255) / 256, 8192);
     hipLaunchKernelGGL(slice_annotate_kernel, dim3(grid), dim3(256), 0, 0, d_sp, d_s0, d_s1, ns, d_off, d_dom, d_mc, d_an, d_fs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(match_count, d_mc, (size_t)ns * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(annotation, d_an, (size_t)ns * 4, hipMemcpyDeviceToHost));
-    if (nfam) HIP_TRY(hipMemcpy(family_sizes, d_fs, (size_t)nfam * 8, hipMemcpyDeviceToHost));
+    EVAL_TRY(w.download(0, ns));
+    EVAL_TRY(tab.download(0, 1));
     return 0;
 }
 
@@ -232,38 +216,33 @@ extern "C" int knn_eval_slices(const int64_t *hits, int64_t nq, int64_t k, const
     rc = ensure_device(g_device);
     if (rc) return rc;
     EvalBufs bufs;
-    int64_t *d_off;
-    int4 *d_dom;
-    rc = slices_upload_domains(bufs, domain_offsets, domain_family, domain_start, domain_stop, np, &d_off, &d_dom);
-    if (rc) return rc;
     const int64_t slab = std::min(nq, eval_slab_rows(k));
-    EVAL_ALLOC(d_rec, int4 *, (size_t)ns * 16);
-    EVAL_ALLOC(d_h, int64_t *, (size_t)slab * k * 8);
-    EVAL_ALLOC(d_qf, int32_t *, (size_t)slab * 4);
-    EVAL_ALLOC(d_ic, uint8_t *, (size_t)slab * k);
-    EVAL_ALLOC(d_ig, uint8_t *, (size_t)slab * k);
-    EVAL_ALLOC(d_lead, int32_t *, (size_t)slab * 4);
-    EVAL_ALLOC(d_tp, int32_t *, (size_t)slab * 4);
-    EVAL_ALLOC(d_cc, unsigned long long *, column_correct ? (size_t)k * 8 : 0);
-    {
-        std::vector<int4> packed((size_t)ns);
-        for (int64_t s = 0; s < ns; s++)
-            packed[(size_t)s] = make_int4(slice_protein[s], slice_start[s], slice_stop[s], match_count ? match_count[s] : 0);
-        HIP_TRY(hipMemcpy(d_rec, packed.data(), (size_t)ns * 16, hipMemcpyHostToDevice));
-    }
-    if (column_correct) HIP_TRY(hipMemset(d_cc, 0, (size_t)k * 8));
+    EvalCols tab(bufs, 1), w(bufs, slab);
+    std::vector<int4> packed, recs((size_t)ns);
+    for (int64_t s = 0; s < ns; s++)
+        recs[(size_t)s] = make_int4(slice_protein[s], slice_start[s], slice_stop[s], match_count ? match_count[s] : 0);
+    const int64_t *d_off;
+    const int4 *d_dom;
+    slices_domain_columns(tab, domain_offsets, domain_family, domain_start, domain_stop, np, packed, &d_off, &d_dom);
+    const int4 *d_rec = tab.in(recs.data(), (size_t)ns * 16);
+    unsigned long long *d_cc = (unsigned long long *)tab.out(column_correct, (size_t)k * 8);
+    const int64_t *d_h = w.in(hits, (size_t)k * 8);
+    const int32_t *d_qf = w.in(query_family, 4);
+    uint8_t *d_ic = w.out(is_correct, (size_t)k);
+    uint8_t *d_ig = w.out(is_ignore, (size_t)k);
+    int32_t *d_lead = w.out(lead, 4);
+    int32_t *d_tp = w.out(tp, 4);
+    EVAL_TRY(w.ready());
+    EVAL_TRY(tab.upload(0, 1));
+    if (d_cc) HIP_TRY(hipMemset(d_cc, 0, (size_t)k * 8));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        HIP_TRY(hipMemcpy(d_h, hits + r0 * k, (size_t)m * k * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_qf, query_family + r0, (size_t)m * 4, hipMemcpyHostToDevice));
+        EVAL_TRY(w.upload(r0, m));
         hipLaunchKernelGGL(slice_eval_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, 0, d_h, m, (int)k, d_qf, d_rec, ns, d_off, d_dom,
-                           ignore_unannotated ? 1 : 0, d_ic, d_ig, d_lead, d_tp, column_correct ? d_cc : (unsigned long long *)nullptr);
+                           ignore_unannotated ? 1 : 0, d_ic, d_ig, d_lead, d_tp, d_cc);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(is_correct + r0 * k, d_ic, (size_t)m * k, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(is_ignore + r0 * k, d_ig, (size_t)m * k, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(lead + r0, d_lead, (size_t)m * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(tp + r0, d_tp, (size_t)m * 4, hipMemcpyDeviceToHost));
+        EVAL_TRY(w.download(r0, m));
     }
-    if (column_correct) HIP_TRY(hipMemcpy(column_correct, d_cc, (size_t)k * 8, hipMemcpyDeviceToHost));
+    EVAL_TRY(tab.download(0, 1));
     return 0;
 }

@@ -227,6 +227,19 @@ def test_slabs_are_cut_at_group_boundaries(gpu_faiss, monkeypatch, rows):
     _same(nosrc, want)
 
 
+@pytest.mark.parametrize("k", [3, 65])
+def test_optional_columns_across_slabs(gpu_faiss, monkeypatch, k):
+    """5 groups of one row in slabs of 2: self_group and qrow_out / hit_out, each present and absent"""
+    rng = np.random.default_rng(90 + k)
+    hits, scores, offsets, row_group = _case(rng, [1, 1, 1, 1, 1], k, nb=300, ndb=200)
+    row_group[hits[:, 0].clip(0, 299)] = [5, 6, 7, 8, 9]  # every group meets its own: leaving self_group out shows
+    monkeypatch.setenv(KNOB, "2")
+    for self_group in ([5, 6, 7, 8, 9], None):
+        want = ref.assemble(hits, scores, offsets, row_group, self_group, 70, 60, 0)
+        for sources in (True, False):
+            _same(c_assemble(hits, scores, offsets, row_group, self_group, 70, 60, 0, sources=sources), want)
+
+
 # ---- a seeded sweep -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", range(4))
 def test_random_sweep(gpu_faiss, seed):

@@ -219,6 +219,16 @@ def test_slabs(gpu_faiss, slab_inputs, monkeypatch, rows):
         assert all(np.array_equal(x, y) for x, y in zip(a[1:], b[1:]))
 
 
+@pytest.mark.parametrize("k", [3, 65])
+def test_label_eval_without_the_matrix_across_slabs(gpu_faiss, monkeypatch, k):
+    """5 rows in slabs of 2, one lane trip and two: is_correct_out present and absent"""
+    hits, lq, ldb = _label_case(np.random.default_rng(500 + k), 5, k)
+    want = ref.label_eval(hits, lq, ldb)
+    monkeypatch.setenv(KNOB, "2")
+    _same_labels(c_labels(gpu_faiss, hits, lq, ldb), want)
+    _same_labels(c_labels(gpu_faiss, hits, lq, ldb, matrix=False), want)
+
+
 @pytest.mark.parametrize("value", ["0", "-4", "", "seven", "7 ", "4x", "99999999999999999999"])
 def test_slab_knob_ignores_what_is_no_positive_integer(gpu_faiss, slab_inputs, monkeypatch, value):
     inputs, want = slab_inputs

@@ -241,6 +241,19 @@ def test_slabs(gpu_faiss, monkeypatch, rows, mode):
     _same(c_fuse(ha, sa, keep, hb, sb, mode, 1, 80, sources=False), want)
 
 
+@pytest.mark.parametrize("k", [3, 65])
+@pytest.mark.parametrize("mode", [PREFIX, UNION])
+def test_optional_columns_across_slabs(gpu_faiss, monkeypatch, k, mode):
+    """5 rows in slabs of 2: keep_a and source_out, each present and absent"""
+    rng = np.random.default_rng(90 + k)
+    ha, sa, keep, hb, sb = _case(rng, 5, k, k, keep=True)
+    monkeypatch.setenv(KNOB, "2")
+    for keep_a in (keep, None):
+        want = ref.fuse(ha, sa, keep_a, hb, sb, mode, 1, k + 1)
+        for sources in (True, False):
+            _same(c_fuse(ha, sa, keep_a, hb, sb, mode, 1, k + 1, sources=sources), want)
+
+
 # ---- a seeded sweep -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", range(4))
 def test_random_sweep(gpu_faiss, seed):

@@ -229,6 +229,14 @@ def test_slabs_of_whole_blocks(gpu_faiss, slab_case, monkeypatch, rows):
     _same(c_pr(*case), want)
 
 
+def test_count_outputs_are_optional_across_slabs(gpu_faiss, slab_case, monkeypatch):
+    """700 rows in slabs of 256 (the smallest slab this entry cuts): selected_out / tp_out / empty_out present and absent"""
+    case, want = slab_case
+    monkeypatch.setenv(KNOB, "256")
+    _same(c_pr(*case), want)
+    _same(c_pr(*case, counts=False), want)
+
+
 # ---- the Python facade -------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def golden():

@@ -225,6 +225,18 @@ def test_slabs(gpu_faiss, monkeypatch):
     _same(c_slices(hits, query_family, tables, 6, match_count, True, columns=False), want)
 
 
+@pytest.mark.parametrize("k", [3, 65])
+def test_optional_columns_across_slabs(gpu_faiss, monkeypatch, k):
+    """5 rows in slabs of 2: match_count (the flag off) and column_correct, each present and absent"""
+    hits, query_family, tables = _case(np.random.default_rng(230 + k), 5, k)
+    match_count = ref.annotate(*tables, 6)[0]
+    want = ref.evaluate(hits, query_family, *tables, False)
+    monkeypatch.setenv(KNOB, "2")
+    for mc in (match_count, None):
+        for columns in (True, False):
+            _same(c_slices(hits, query_family, tables, 6, mc, False, columns=columns), want)
+
+
 # ---- annotate ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ns", [1, 255, 256, 257])
 def test_annotate_slice_counts(gpu_faiss, ns):
