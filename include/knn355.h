@@ -536,6 +536,45 @@ int knn_eval_fuse(const int64_t *hits_a, const double *scores_a, const uint8_t *
                   int32_t mode, int32_t ascending, int32_t k_out,
                   int64_t *hits_out, double *scores_out, int32_t *source_out, int32_t *filled_out);
 
+/* ---- principal components of embedding rows ---------------------------------------
+ * pfam/reverse_evaluate.py:34-44, 100-108: sklearn.decomposition.PCA(n_components=2) over the concatenated forward and
+ * scrambled embeddings.  The two stateless entries below are its array-sized halves, the mean and covariance of the
+ * rows and the projection of rows onto given components; the eigen-solve of the d x d covariance between them is host
+ * work (decomposition.py: numpy.linalg.eigh in float64).  All pointers are host pointers; x is float32 [n][d],
+ * row-major, and is never written.  d is a multiple of 4 with 4 <= d <= KNN_PCA_MAX_D.
+ * "Chain" below means one fp32 fmaf per step with a single rounding, as in oracle/knn_oracle.c.
+ *   groups      the rows are cut into consecutive groups of L = 4096 * ceil(n / (4096 * 256)) rows: at most 256 groups,
+ *               the last may be short.  L depends on n alone, never on the device, its CU count or a tuning flag.
+ *   mean        per column j, a group's sum is the float64 sum of its rows' x[r][j] in ascending row order (starting
+ *               from the first row's value); the group sums are added in ascending group order in float64 (starting
+ *               from the first group's) and divided by (double)n; mean[j] is that value rounded to float32
+ *   centring    xc[r][j] = x[r][j] - mean[j], one fp32 subtraction, applied as rows are loaded and never stored
+ *   covariance  for group g and i <= j, P_g[i][j] is the chain over the group's rows in ascending row order,
+ *               acc = fmaf(xc[r][i], xc[r][j], acc), starting from +0;
+ *               cov[i][j] = (the float64 sum of (double)P_g[i][j] in ascending g, starting from P_0) / (double)(n - 1);
+ *               cov[j][i] is a copy of cov[i][j]
+ *   projection  out[r][c] is the library's dot chain (blocks of 8 columns in the order 0,4,1,5,2,6,3,7, the last block
+ *               zero padded) of xc[r][.] with components[c][.]
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: a d outside the rule above;
+ * a null pointer; knn_pca_moments with n < 2; knn_pca_project with n < 0 or nc outside [1, min(d, KNN_PCA_MAX_COMPONENTS)]
+ * (n = 0 returns 0 before any pointer is looked at).  Non-finite input is not refused: it gives non-finite outputs.
+ * knn_pca_moments (mean float32 [d], cov float64 [d][d]) keeps the rows on the device for the call, uploaded once on
+ * the copy pipeline's host-to-device stream: n * d * 4 bytes, plus groups * d * d * 4 bytes of partial sums.  A failed
+ * allocation returns KNN_ERR_HIP with nothing left allocated.  knn_pca_project (out float32 [n][nc]) holds no whole
+ * copy: the rows go through the device in slabs of 256 MiB (KNN355_EVAL_SLAB_ROWS sets the rows per slab, as above).
+ * Hot paths (pca.inc): pca_colsum_kernel, one thread per (group, column); pca_cov_kernel, one workgroup per (pair of
+ * 128-column tiles, group) on v_mfma_f32_32x32x2_f32 with a K step = two consecutive rows; pca_cov_reduce_kernel;
+ * pca_project_kernel, one lane per row and one chain per (row, component).  No floating-point atomics. */
+#define KNN_PCA_MAX_D 2048
+#define KNN_PCA_MAX_COMPONENTS 32
+int knn_pca_moments(const float *x, int64_t n, int32_t d, float *mean /* [d] */, double *cov /* [d * d] */);
+int knn_pca_project(const float *x, int64_t n, int32_t d, const float *mean, const float *components /* [nc * d] */,
+                    int32_t nc, float *out /* [n * nc] */);
+/* measurement (tools/bench_pca.py): HIP-event milliseconds of the calling thread's last successful knn_pca_moments,
+ * moments_ms[4] = upload, column sums and mean, covariance kernel, reduce, and of its last knn_pca_project, the
+ * projection kernel summed over the slabs */
+int knn_pca_last_ms(float *moments_ms, float *project_ms);
+
 /* ---- MMseqs2 prefilter database: SURVEY section 8(f) N3 ----------------------------
  * seqvec_search/mmseqs/_write_prefilter_db.py:52-97 write_prefilter_db: data file
  * ("<prefilter>.0") and index file ("<prefilter>.index"); queries[i] is the faiss row of

@@ -135,6 +135,9 @@ def _declare(L):
                                         c_void_p, c_void_p, c_void_p]),
         "knn_eval_bootstrap": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+        "knn_pca_moments": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+        "knn_pca_project": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+        "knn_pca_last_ms": (c_int32, [f32p, f32p]),
         "knn_eval_fuse": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
         "knn_write_prefilter_db": (c_int32, [c_char_p, c_char_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32]),

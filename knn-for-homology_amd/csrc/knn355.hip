@@ -29,6 +29,7 @@
 //   slices_eval.inc                 slice-level correctness and AUC1 of slice searches (knn_eval_slice_annotate, knn_eval_slices).
 //   pr_curve.inc                    the precision-recall threshold sweep over (is_correct, scores) (knn_eval_pr_curve).
 //   fuse.inc                        the two hit-list fusions of the results scripts: prefix-then-fill, sorted union (knn_eval_fuse).
+//   pca.inc                         mean, covariance (fp32 MFMA) and projection behind decomposition.PCA (knn_pca_moments, knn_pca_project).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
 #include <hip/hip_runtime.h>
 #include <thread>
@@ -5427,5 +5428,6 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "slices_eval.inc"
 #include "pr_curve.inc"
 #include "bootstrap.inc"
+#include "pca.inc"
 #include "fuse.inc"
 #include "range.inc"
