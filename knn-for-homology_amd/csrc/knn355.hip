@@ -59,6 +59,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #define KEY_PAD 0xFFFFFFFFFFFFFFFFull
+#define KEY_WORD_INF 0xFF800000u // f2ord(+inf): the first score word that is no score (select_topk_kernel's load)
 #ifndef KNN355_DIFF_SCALAR_Q
 #define KNN355_DIFF_SCALAR_Q 1 // difference builds read their query fragments with scalar loads (0: broadcast LDS reads, round-4 first form)
 #endif
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(64) void normalize_rows_kernel(float *__restrict__ 
     const int lane = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * 64;
     const int64_t row = row0 + lane;
-    float inv = 0.0f; // 0 == leave the row alone
+    float inv = -1.0f; // < 0 == leave the row alone (0 is a factor like any other: a row whose norm overflows is multiplied by 1 / sqrt(inf) = 0, as fvec_renorm_L2 does)
     if (row < n) {
         float nr = lane_norm_row<ALIGNED>(x + row * stride, d);
         if (nr > 0.0f) inv = (float)(1.0 / (double)sqrtf(nr));
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(64) void normalize_rows_kernel(float *__restrict__ 
     const int nrows = (int)min((int64_t)64, n - row0);
     for (int r = 0; r < nrows; r++) {
         const float s = __shfl(inv, r, 64);
-        if (s == 0.0f) continue;
+        if (s < 0.0f) continue;
         float *p = x + (row0 + r) * stride;
         if constexpr (ALIGNED) {
             for (int e = 4 * lane; e < d; e += 256) {
@@ -2478,12 +2479,21 @@ __global__ __launch_bounds__(NT) void select_topk_kernel(SelectParams p)
         n = max(0, min(n - seg_base, p.seg_len));
         orow = q * p.nseg + blockIdx.y;
     }
+    // A key whose score word is f2ord(+inf) or above is no key (a "smaller is better" value of +inf or
+    // a NaN never becomes a hit).  The scan's filters admit v <= threshold with ONE compare per score, and a list's threshold
+    // starts at +inf: until a list has been cut, a +inf score gets in.  It is dropped HERE, where every result leaves the
+    // scan -- D / I, out_keys, the seed's candidates and bound, the segment pass and the merge of shard lists all read their
+    // keys through this function -- so a starved list is padded and counted exactly as the oracle's.  (The words above
+    // f2ord(+inf) are the positive NaNs and KEY_PAD's own; a NaN fails every compare of the scan and never gets this far.)
     auto load = [&](int idx) -> uint64_t {
+        uint64_t v;
         if (p.lm_lists > 0) {
             const int l = idx / p.lm_k, j = idx - l * p.lm_k;
-            return ((gptr_u64)p.in)[((size_t)l * p.nq + q) * p.lm_k + j];
+            v = ((gptr_u64)p.in)[((size_t)l * p.nq + q) * p.lm_k + j];
+        } else {
+            v = ((gptr_u64)p.in)[(size_t)q * p.in_stride + seg_base + idx];
         }
-        return ((gptr_u64)p.in)[(size_t)q * p.in_stride + seg_base + idx];
+        return (uint32_t)(v >> 32) >= KEY_WORD_INF ? KEY_PAD : v;
     };
     const bool in_regs = n <= NT * R;
     // memory path (more keys than the registers hold): several independent loads in flight per thread
