@@ -4,10 +4,10 @@
 //   plan_check sym     reads lines "n k metric flags can_stream [force_qt]": the symmetric self-search's plan and work table --
 //                      "plain", or kernel ts tiles st S j qcap k_sample n_expect groups gstart[0..groups] first_run items lds
 //                      max_wgs and the 64-bit FNV-1a hash of the items' integers
-//   plan_check range   reads lines "n nq metric batch": the range scan's plan of one block of nq queries -- kernel qt dt nqtiles
-//                      nchunks tiles_base tiles_rem grid diff lds segcap
+//   plan_check range   reads lines "n nq metric batch [num_cus]": the range scan's plan of one block of nq queries -- kernel qt dt
+//                      nqtiles nchunks tiles_base tiles_rem grid diff lds segcap
 //   plan_check sweep   walks a grid of shapes and flags and exits non-zero on a broken invariant
-// The device has 256 CUs in both.  Built with the host compiler and -fsanitize=address,undefined (make plan_check).
+// The device has 256 CUs throughout, but for a `range` line that names another count.  Built with the host compiler and -fsanitize=address,undefined (make plan_check).
 #include "plan.h"
 
 #include <stdarg.h>
@@ -121,13 +121,15 @@ static int run_range()
     char line[512];
     while (fgets(line, sizeof line, stdin)) {
         long long n, nq, batch;
-        int metric;
-        if (sscanf(line, "%lld %lld %d %lld", &n, &nq, &metric, &batch) < 4) {
+        int metric, cus = 256;
+        if (sscanf(line, "%lld %lld %d %lld %d", &n, &nq, &metric, &batch, &cus) < 4) {
             if (line[0] == '\n' || line[0] == '#') continue;
             fprintf(stderr, "plan_check: bad case line: %s", line);
             return 2;
         }
-        const RangePlan p = plan_range(make_ctx(n, nq, metric, 0, 0, 0, batch, false), nq);
+        PlanCtx c = make_ctx(n, nq, metric, 0, 0, 0, batch, false);
+        c.num_cus = cus;
+        const RangePlan p = plan_range(c, nq);
         printf("%s %d %d %d %d %d %d %d %d %zu %lld\n", p.name, p.qt, p.dt, p.nqtiles, p.nchunks, p.tiles_base, p.tiles_rem, p.grid, (int)p.diff, p.lds,
                (long long)range_segcap(p, nq));
     }
