@@ -2892,10 +2892,14 @@ __global__ __launch_bounds__(256) void scan16_rows_kernel(const float *__restric
 }
 
 // Per search: the fp16 queries + exponents, and each query's bound B_q >= |s - s~| over every row:
-//   B_q = |q| R + |q - q'| X' + g(dp, u) |q| X + g(dp16, 4u) |q'| X' + 2^-140,   g(n, v) = n v / (1 - n v), u = 2^-24
+//   B_q = |q| R + |q - q'| X' + g(dp, u) |q| X + g(dp16, 4u) |q'| X' + (dp + 1) 2^-149,   g(n, v) = n v / (1 - n v), u = 2^-24
 // (the contract's fmaf chain; the f16 MFMA's fp32 accumulation, allowed four times the error of a round-to-nearest add; the
-// ldexp of a score below the normal range).  fail[q] = 1 sends the search to its fp32 fallback: a query value or the bound is
-// not finite, an exponent sum could overflow a score, a row is not finite.  One wave per query.
+// roundings below the normal range, where g's relative model does not hold: each of the chain's dp steps rounds a subnormal
+// partial sum to a multiple of 2^-149, and so does the ldexp of the approximate score -- half of 2^-149 each, counted whole.
+// The term was a flat 2^-140 for the ldexp alone: at d = 1280 a row and a query whose products are all 2^-150 give s = 0 and
+// s~ = 640 * 2^-149 against a bound of 512.54 * 2^-149, tests/test_scan16_reference.py).  fail[q] = 1 sends the search
+// to its fp32 fallback: a query value or the bound is not finite, an exponent sum could overflow a score, a row is not
+// finite.  One wave per query.
 __global__ __launch_bounds__(64) void scan16_queries_kernel(const float *__restrict__ xq, int dp, int dp16, _Float16 *__restrict__ q16,
                                                             int *__restrict__ qexp, float *__restrict__ Bq, uint32_t *__restrict__ fail,
                                                             const uint32_t *__restrict__ stat, uint32_t *__restrict__ sstat, int first)
@@ -2908,7 +2912,7 @@ __global__ __launch_bounds__(64) void scan16_queries_kernel(const float *__restr
     if (lane == 0) {
         const double R = __uint_as_float(stat[S16_R]), Xp = __uint_as_float(stat[S16_XP]), X = __uint_as_float(stat[S16_X]);
         const double u = 0x1p-24, g1 = dp * u / (1.0 - dp * u), g2 = dp16 * 4.0 * u / (1.0 - dp16 * 4.0 * u);
-        const double B = nq * R + nd * Xp + g1 * nq * X + g2 * nqp * Xp + 0x1p-140;
+        const double B = nq * R + nd * Xp + g1 * nq * X + g2 * nqp * Xp + (dp + 1) * 0x1p-149;
         const float Bf = s16_up(B);
         qexp[q] = e;
         Bq[q] = Bf;

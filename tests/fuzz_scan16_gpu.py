@@ -3,7 +3,9 @@
 the prefilter forced on (KNN_TUNE_SCAN16_ANY_NB) and with it off (KNN_TUNE_NO_SCAN16) and compares D / I bit for bit, and
 against the CPU oracle.  Random shapes, k, batch sizes and data kinds: gaussian, L2-normalised, rows scaled by powers
 of two up to 2^+-40, magnitudes mixed inside rows, duplicated and zero rows, near-duplicates of a query that fp16 cannot
-tell apart (the device fallback), constant rows.  usage: fuzz_scan16_gpu.py [ncases] [seed]"""
+tell apart (the device fallback), constant rows, and the adversarial generators of tests/scan16_reference.py (copy errors
+aligned with the query, flushed entries, rows at the exponent clamp and subnormals, the exponent gate) at the case's d;
+those bring their own rows, queries and k.  usage: fuzz_scan16_gpu.py [ncases] [seed]"""
 import sys
 import time
 from pathlib import Path
@@ -15,8 +17,31 @@ sys.path.insert(0, str(ROOT))
 from knn_for_homology_amd import faiss  # noqa: E402
 from knn_for_homology_amd._lib import KNN_TUNE_NO_SCAN16, KNN_TUNE_SCAN16_ANY_NB  # noqa: E402
 from oracle import knn_oracle as ko  # noqa: E402
+sys.path.insert(0, str(ROOT / "tests"))
+import scan16_reference as sr  # noqa: E402
 
-KINDS = ("gauss", "normed", "scaled", "mixed", "dups", "near", "const")
+KINDS = ("gauss", "normed", "scaled", "mixed", "dups", "near", "const", "aligned", "flushed", "tiny", "gate")
+
+
+def adversarial(rng, kind, d):
+    """(xb, xq, k) of one of the reference's generators at d (even: the aligned rows come in pairs of entries) and a random
+    seed / background size / k.  Of the tiny kind only the subnormal query and the p = -130 scores always fall back."""
+    seed, k = int(rng.integers(1, 1 << 30)), int(rng.choice([1, 2, 10, 50]))
+    if kind == "aligned":
+        c = sr.aligned_rows(d, seed, nbg=int(rng.integers(300, 3000)), k=max(2, k)) if rng.random() < 0.5 else sr.aligned_query(d, seed, nbg=int(rng.integers(300, 3000)), k=max(2, k))
+    elif kind == "flushed":
+        c = sr.flushed(bool(rng.random() < 0.5), d, seed, k=k, nbg=int(rng.integers(300, 3000)))
+    elif kind == "tiny":
+        which = int(rng.integers(0, 4))
+        if which == 0:
+            c = sr.tiny(d, seed, k=k, subq=bool(rng.random() < 0.25))
+        elif which == 1:
+            c = sr.subnormal_query_case(d, seed, k=k, nb=int(rng.integers(300, 3000)))
+        else:
+            c = sr.subnormal_scores(d, seed, k=k, nb=int(rng.integers(300, 3000)), p=int(rng.choice([-130, -125, -122, -118])))
+    else:
+        c = sr.gate(bool(rng.random() < 0.5), d, seed, k=k, nbg=int(rng.integers(300, 3000)))
+    return c.xb, c.xq, c.k
 
 
 def data(rng, kind, nb, d, nq):
@@ -54,7 +79,11 @@ def run(ncases=1000, seed=1):
         nq = int(rng.integers(1, 33))
         k = int(min(nb, rng.choice([1, 2, 10, 50, 100, 256, 500, 1000, 1500])))
         kind = KINDS[case % len(KINDS)]
-        xb, xq = data(rng, kind, nb, d, nq)
+        if kind in ("aligned", "flushed", "tiny", "gate"):
+            xb, xq, k = adversarial(rng, kind, d)
+            nb, nq = len(xb), len(xq)
+        else:
+            xb, xq = data(rng, kind, nb, d, nq)
         idx = faiss.IndexFlat(d, faiss.METRIC_INNER_PRODUCT)
         idx.set_scan16(1)
         idx.add(xb)
