@@ -13,7 +13,7 @@
 // bit's projections -- s[n/2] of the sorted column for odd n, (s[n/2 - 1] + s[n/2]) / 2 in float for even n; bit j of
 // a code is then (x . a_j - t_j >= 0).
 //
-//   lsh_encode_kernel    MFMA projection of 128 rows x 128 bits per workgroup, bits (acc >= threshold) packed
+//   lsh_encode_kernel    MFMA projection of 128 rows x 128 bits per workgroup, bits (acc - threshold >= 0) packed
 //                        with one ballot per accumulator register
 //   lsh_project_kernel   the same projection (lsh_project_tile: one K loop for both), accumulators stored
 //                        transposed as P[bit][row] for the training
@@ -40,6 +40,7 @@ struct LshEncodeParams {
     const float *rot; // [W*64][dp]
     int64_t n;
     int dp, W;
+    int nbits;         // code bits that exist; the bits from there up to W*64 are padding (lsh_encode_kernel)
     uint32_t *codes32; // [n][2W]                       (lsh_encode_kernel)
     const float *thr;  // [W*64] thresholds, or null     (lsh_encode_kernel)
     float *proj;       // [W*64][ldp], whole 128-row tiles (lsh_project_kernel)
@@ -129,18 +130,23 @@ __global__ __launch_bounds__(256, 2) void lsh_encode_kernel(LshEncodeParams p)
     f32x16 acc[2][2];
     lsh_project_tile(p, row0, bit0, smem, acc);
     // code bits: lane = bit (column), register = row; one ballot packs 32 bits of two rows.  FAISS subtracts the threshold
-    // and tests the sign (x - t >= 0); x >= t is the same predicate in IEEE fp32 as long as denormals are kept (x - t is
-    // then zero only for x == t, and its sign is that of the comparison) -- the fp32 default on gfx950, and the build
-    // passes no flush flag -- so the accumulator is compared directly.  Without thresholds the operand is 0.0f as ever.
+    // and tests the sign (x - t >= 0), and so does this: x >= t is the same predicate for FINITE operands as long as
+    // denormals are kept (the fp32 default on gfx950, and the build passes no flush flag), but not when x and t are the same
+    // infinity -- inf - inf is a NaN, bit 0, while inf >= inf holds -- and a threshold of +-inf is what training gives a
+    // column whose middle is infinite.  Without thresholds the operand is 0.0f (x - 0 is x, NaN included: bit 0).
+    // A padding bit (>= nbits) is 1 whatever the row holds: its rotation row is zero, so an ordinary row's 0 >= 0 sets it, a
+    // row with a NaN or an infinity would get 0 * inf = NaN there, and two rows' Hamming distance would count bits that do
+    // not exist (knn_lsh_add_codes fills the padding with ones too).
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++) {
             const int word = (bit0 >> 5) + wn * 2 + b;
             const float t = p.thr ? p.thr[word * 32 + li] : 0.0f;
+            const uint64_t padm = __ballot(word * 32 + li >= p.nbits); // (once per word: a scalar OR per ballot below, nothing per lane)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const uint64_t m = __ballot(acc[a][b][r] >= t);
+                const uint64_t m = __ballot(acc[a][b][r] - t >= 0.0f) | padm;
                 const int64_t row = row0 + (wm * 2 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (li == 0 && row < p.n) p.codes32[(size_t)row * (2 * p.W) + word] = lh ? (uint32_t)(m >> 32) : (uint32_t)m;
             }
@@ -458,7 +464,7 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
         }
         if (xp_out) *xp_out = xp;
         LshEncodeParams p;
-        p.x = xp; p.rot = h->rot; p.n = m; p.dp = h->dp; p.W = h->W;
+        p.x = xp; p.rot = h->rot; p.n = m; p.dp = h->dp; p.W = h->W; p.nbits = h->nbits;
         p.codes32 = proj ? nullptr : (uint32_t *)(dst_codes + (size_t)i0 * h->W);
         p.thr = h->thr;
         p.proj = proj ? proj + i0 : nullptr;
@@ -486,7 +492,8 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
     return 0;
 }
 
-// installs thr_host[nbits] as the handle's thresholds (the tail up to W*64 is 0: a padding bit stays 0 >= 0), null: none
+// installs thr_host[nbits] as the handle's thresholds (the tail up to W*64 is 0 and never decides anything: the encoder
+// sets the padding bits to 1 by their index), null: none
 static int lsh_install_thresholds(knn_lsh_s *h, const float *thr_host)
 {
     if (!thr_host) {
@@ -624,7 +631,8 @@ extern "C" int knn_lsh_add(knn_lsh_s *h, const float *x_host, int64_t n)
 }
 
 // codes in FAISS byte order: [n][bytes_per_vec], bit i of a row = byte i>>3, bit i&7.  The device codes carry 1 bits from
-// nbits up (the encoder's zero rotation rows: 0 >= 0); FAISS's codes have zeros there, so they are cleared on the way out.
+// nbits up (the encoder sets them by their index, whatever the row holds); FAISS's codes have zeros there, so they are
+// cleared on the way out.
 extern "C" int knn_lsh_get_codes(knn_lsh_s *h, uint8_t *out_host, int32_t bytes_per_vec)
 {
     if (!h || !out_host) return set_err(KNN_ERR_INVALID, "lsh_get_codes: null pointer");
@@ -662,7 +670,7 @@ extern "C" int knn_lsh_add_codes(knn_lsh_s *h, const uint8_t *codes_host, int64_
         h->codes = nc;
         h->cap_rows = ncap;
     }
-    // padding bits are 1 in codes produced by the encoder (0 >= 0): keep that convention
+    // padding bits are 1 in codes produced by the encoder: keep that convention
     std::vector<uint8_t> tmp((size_t)n * h->W * 8, 0xFF);
     for (int64_t i = 0; i < n; i++) {
         memcpy(&tmp[(size_t)i * h->W * 8], codes_host + (size_t)i * bytes_per_vec, (size_t)bytes_per_vec);

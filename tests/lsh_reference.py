@@ -1,7 +1,14 @@
 """Exact host restatement of IndexLSH (sign-bit codes + Hamming top-k), for the LSH tests and tests/fuzz_lsh_gpu.py.
 
-ref_codes    bit j of a row = (x . R[j] >= 0) with the products in float64; FAISS byte order (byte j >> 3, bit j & 7);
-             the bits of the last byte at and above nbits are zero
+projections32
+             x . R[j] with the products in float64, rounded to float32 (the exact inputs below have one right answer;
+             a NaN, an infinity or one entry of +-2^127 among small integers have one too: lsh_nonfinite_cases)
+faiss_bits   the code bit as FAISS 1.7.2 computes it (IndexLSH::sa_encode -> fvecs2bitvecs, restated from the published
+             source): the float32 projection, the float32 subtraction of the threshold (0 without thresholds), the sign
+             test `>= 0`.  For finite operands this is `p >= t` (denormals kept); it is NOT when p and t are the same
+             infinity (inf - inf is a NaN: bit 0) and a NaN projection's bit is 0
+ref_codes    bit j of a row = faiss_bits(projections32, 0); FAISS byte order (byte j >> 3, bit j & 7); the bits of the
+             last byte at and above nbits are zero
 ref_search   Hamming distances over uint64 words, the k smallest per query ordered by (distance, id); rows shorter
              than k are padded with FLT_MAX / -1
 assert_same_search, assert_same_codes
@@ -46,15 +53,31 @@ def zero_projection_rows(rng, R, n):
     return np.ascontiguousarray(R[js] * s, np.float32), js
 
 
-def ref_codes(x, R, chunk=8192):
-    """x [n, d], R [nbits, d] -> uint8 [n, (nbits + 7) // 8]: bit j = (x . R[j] >= 0), FAISS byte order, zero padding"""
+def projections32(x, R):
+    """[n, nbits] float32: the float64 products x . R[j], rounded to float32 once"""
+    with np.errstate(all="ignore"):
+        return (np.asarray(x, np.float64) @ np.asarray(R, np.float64).T).astype(np.float32)
+
+
+def faiss_bits(p, t=0.0):
+    """bool [n, nbits]: (p - t >= 0) with the subtraction in float32 -- p float32 projections, t float32 [nbits] or a scalar"""
+    with np.errstate(all="ignore"):
+        return (np.asarray(p, np.float32) - np.asarray(t, np.float32)) >= 0
+
+
+def pack_bits(bits):
+    """bool [n, nbits] -> uint8 [n, (nbits + 7) // 8], FAISS byte order, zero padding"""
+    return np.packbits(np.asarray(bits, bool), axis=1, bitorder="little")
+
+
+def ref_codes(x, R, t=0.0, chunk=8192):
+    """x [n, d], R [nbits, d] -> uint8 [n, (nbits + 7) // 8]: bit j = faiss_bits(x . R[j], t[j]), FAISS byte order, zero padding"""
     x = np.asarray(x)
-    R = np.asarray(R, np.float64)
-    nbits = R.shape[0]
+    nbits = np.asarray(R).shape[0]
+    t = np.broadcast_to(np.asarray(t, np.float32), (nbits,))
     out = np.empty((x.shape[0], (nbits + 7) // 8), np.uint8)
     for i in range(0, x.shape[0], chunk):
-        bits = (x[i:i + chunk].astype(np.float64) @ R.T) >= 0
-        out[i:i + chunk] = np.packbits(bits, axis=1, bitorder="little")
+        out[i:i + chunk] = pack_bits(faiss_bits(projections32(x[i:i + chunk], R), t))
     return out
 
 

@@ -141,21 +141,25 @@ def _chain_class(T):
     return cls, ssum
 
 
-def classify(xq, xb, form):
+def classify(xq, xb, form, mult=None):
     """outcome of every (query, row) pair of float32 xq [nq][d], xb [nb][d]: uint8 [nq][nb] of
-    0 never, 1 hit (finite), 2 best (inner product +inf), 3 zero (squared L2 exactly 0)"""
+    0 never, 1 hit (finite), 2 best (inner product +inf), 3 zero (squared L2 exactly 0).
+    mult = (xq', xb'): the dot product's terms are those of these vectors instead (the bf16 scan multiplies rounded copies,
+    tests/approx16_reference.py); the norms of form "l2n" stay those of xq and xb"""
     q = np.asarray(xq, np.float32).astype(np.float64)
     b = np.asarray(xb, np.float32).astype(np.float64)
+    mq, mb = (q, b) if mult is None else (np.asarray(m, np.float32).astype(np.float64) for m in mult)
     out = np.zeros((q.shape[0], b.shape[0]), np.uint8)
     fmax = float(FLT_MAX)
     with np.errstate(all="ignore"):
         if form == "l2d":
+            assert mult is None
             t = q[:, None, :] - b[None, :, :]
             cls, val = _chain_class(t * t)
             out[cls == 0] = 1
             out[(cls == 0) & (val == 0)] = 3
             return out
-        cls, ip = _chain_class(q[:, None, :] * b[None, :, :])
+        cls, ip = _chain_class(mq[:, None, :] * mb[None, :, :])
         if form == "ip":
             out[cls == 0] = 1
             out[cls == 1] = 2
@@ -252,3 +256,23 @@ def poison(rng, nb, nq, d, where, query_kinds=QUERY_KINDS, near=2):
         xq[qi] = make_row(kind, d, xq[qi])
         queries[qi] = kind
     return xb, xq, Table(xb, xq, rows, queries, nears)
+
+
+def poison_ints(rng, nb, nq, d, where, query_kinds=QUERY_KINDS, near=2, lim=6):
+    """`poison` with every ordinary entry mapped to a non-zero integer of its sign, at most `lim` in magnitude (zeros, the
+    poisoned entries and the huge values stay): for the paths whose arithmetic has one right answer only on such data (LSH
+    codes against a +-1 rotation, the bf16 scan).  The map is entry by entry, so a near-duplicate stays a copy of its query
+    and every sign that `poison` arranged holds; a near-duplicate's query is then made to sum to at most -1 again."""
+    xb, xq, t = poison(rng, nb, nq, d, where, query_kinds, near)
+
+    def ints(x):
+        with np.errstate(invalid="ignore", over="ignore"):
+            small = np.isfinite(x) & (np.abs(x) < 1e6) & (x != 0)
+            return np.where(small, np.sign(x) * np.clip(np.ceil(np.abs(x) * 2), 1, lim), x).astype(np.float32)
+    xb, xq = ints(xb), ints(xq)
+    for q, r in t.near.items():
+        s = xq[q].sum(dtype=np.float64)
+        if s > -1:
+            xq[q, 7] -= np.float32(s + 1)
+            xb[r, 7] = xq[q, 7]
+    return xb, xq, Table(xb, xq, t.rows, t.queries, t.near)

@@ -125,3 +125,22 @@ def test_reference_is_the_oracle_on_representable_inputs(oracle, metric, d):
     Ds, Is = ar.expected(xb * np.float32(0.25), xq * np.float32(0.25), 10, metric, scale=0.25)
     Do, Io = oracle.flat_search(xb * np.float32(0.25), xq * np.float32(0.25), 10, metric, l2_mode=1)
     assert np.array_equal(Is, Io) and np.array_equal(_bits(Ds), _bits(Do))
+
+
+def test_bf16_rne_on_non_finite_and_overflowing_values():
+    """NaN -> NaN (every payload, both signs), +-inf -> +-inf, finite values above the largest bf16 -> +-inf (FLT_MAX), and
+    the `twin` of tests/nonfinite_cases.py (1.8e19) stays finite: 0x5F79CCD9 rounds to 0x5F7A0000 = 1.8014e19, whose square
+    3.245e38 is still below FLT_MAX -- the bf16 scan's twin-against-twin inner product is a finite hit, as in fp32"""
+    nan_bits = np.array([0x7FC00000, 0x7F800001, 0x7FFFFFFF, 0xFFFFFFFF, 0xFF800001, 0x7F808000, 0x7FBF8000], np.uint32)
+    assert np.isnan(ar.bf16_rne(nan_bits.view(np.float32))).all()
+    inf = np.float32(np.inf)
+    fmax = np.float32(np.finfo(np.float32).max)
+    x = np.array([inf, -inf, fmax, -fmax, 1.8e19, -1.8e19, 3e19], np.float32)
+    r = ar.bf16_rne(x)
+    assert list(r[:4]) == [inf, -inf, inf, -inf]
+    assert np.float32(1.8e19).view(np.uint32) == 0x5F79CCD9 and r[4].view(np.uint32) == 0x5F7A0000 and r[5] == -r[4]
+    assert np.isfinite(r[4:]).all() and float(r[4]) ** 2 < float(fmax) and (r.view(np.uint32) & 0xFFFF == 0).all()
+    # the edge: the largest bf16 stays, the midpoint to 2^128 (a tie: the even neighbour is 2^128) and everything above go to inf
+    edge = np.array([0x7F7F0000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7F8001], np.uint32).view(np.float32)
+    assert list(ar.bf16_rne(edge).view(np.uint32)) == [0x7F7F0000, 0x7F7F0000, 0x7F800000, 0x7F800000]
+    assert list(ar.bf16_trunc(np.array([fmax, inf], np.float32)).view(np.uint32)) == [0x7F7F0000, 0x7F800000]

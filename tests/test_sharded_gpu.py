@@ -75,6 +75,55 @@ def test_emulated_four_shard_merge(gpu_faiss, oracle):
         assert np.array_equal(D.cpu().numpy().view(np.uint32), Do.view(np.uint32))
 
 
+@pytest.mark.parametrize("metric", [0, 1])
+@pytest.mark.parametrize("k", [10, 2048])
+def test_emulated_four_shard_merge_with_non_finite_rows(gpu_faiss, oracle, metric, k):
+    """DESIGN.md section 2 across shard boundaries: poisoned rows of every kind of tests/nonfinite_cases.py on both sides of
+    each of the three boundaries, near-duplicates whose poisoned copy lives in another shard than the clean row, and (k = 2048
+    over 2051 rows) starved queries -- the merged list is padded once, behind the hits of every shard, not once per shard.
+    Expected: the oracle's answer over the whole database, ids and distance bits."""
+    import torch
+    import nonfinite_cases as nc
+    from knn_for_homology_amd.sharded import HipShardBackend, shard_bounds
+    nb, d, nq, world = 2051, 64, 41, 4
+    bounds = [shard_bounds(nb, world, r) for r in range(world)]
+    cuts = [lo for lo, _ in bounds[1:]]
+    # seven kinds below and seven kinds from each boundary on: every kind on both sides, whatever kind a position gets
+    where = sorted({p for c in cuts for p in range(c - 7, c + 7)} | {0, nb - 1})
+    xb, xq, table = nc.poison(np.random.default_rng(300 + metric + k), nb, nq, d, where, near=3)
+    shard_of = lambda r: next(i for i, (lo, hi) in enumerate(bounds) if lo <= r < hi)
+    for c in cuts:
+        for side in (range(c - 7, c), range(c, c + 7)):
+            assert {table.rows[r] for r in side} == set(nc.ROW_KINDS), "every kind on both sides of every boundary"
+    # the clean twin of each near-duplicate: a copy of the query itself, in another shard than its poisoned copy
+    for q, r in table.near.items():
+        clean = next(p for p in range(bounds[(shard_of(r) + 2) % world][0] + 20, nb) if p not in table.rows)
+        xb[clean] = xq[q]
+        assert shard_of(clean) != shard_of(r)
+        table.rows[clean] = "clean"
+    Do, Io = oracle.flat_search(xb, xq, k, metric)
+    # not vacuous, on the oracle's answer
+    pad = -nc.FLT_MAX if metric == 0 else nc.FLT_MAX
+    if k > 10:
+        assert ((Io >= 0).sum(1) < k).any() and (((Io >= 0).sum(1) > 0) & ((Io >= 0).sum(1) < k)).any(), "no starved query"
+        assert ((Io[:, 1:] >= 0) <= (Io[:, :-1] >= 0)).all() and (Do[Io < 0] == pad).all(), "pads come once, behind every hit"
+    if metric == 0:
+        assert np.isposinf(Do).any(), "no +inf inner-product hit"
+    for q, r in table.near.items():
+        assert r not in Io[q], "the poisoned copy is no hit"
+    q = torch.from_numpy(xq).to(torch.device("cuda", 0))
+    parts, backs = [], []
+    for lo, hi in bounds:
+        b = HipShardBackend(d, metric)
+        b.add(xb[lo:hi])
+        backs.append(b)
+        parts.append(b.search_keys(q, k, lo))
+    D, I = backs[0].merge(torch.stack(parts).contiguous(), world, nq, k)
+    torch.cuda.synchronize()
+    assert np.array_equal(I.cpu().numpy(), Io)
+    assert np.array_equal(D.cpu().numpy().view(np.uint32), Do.view(np.uint32))
+
+
 def test_submit_overlaps_two_lanes_and_matches_sync(gpu_faiss, oracle, monkeypatch):
     """Searches submitted back to back alternate between the index and its read-only view (own
     streams and scratch memory) and must return what a blocking search returns, in any

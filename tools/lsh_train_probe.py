@@ -2,7 +2,8 @@
 """IndexLSH train_thresholds timing: train(x) against add(x) of the same rows (same upload, same projection work), with
 the training's upload / projection / selection split (HIP events, knn_lsh_last_train_ms), and one pfam/search.py-shaped
 search (k = 1000 over every row) with and without thresholds.
-usage: lsh_train_probe.py [out.json] [--search]   (default: profiles/lsh_thresholds.json)"""
+usage: lsh_train_probe.py [out.json] [--search]   (default: profiles/lsh_thresholds.json)
+       lsh_train_probe.py out.json --encode     (add(x) alone, repeated: the encoder's time, for comparing two builds)"""
 import ctypes
 import json
 import sys
@@ -62,9 +63,31 @@ def search_leg(x, nbits, thresholds, runs=5, k=1000):
     return out
 
 
+def encode_leg(x, nbits, thresholds, runs=12):
+    """add(x) of the same rows over and over on one handle (reset() keeps the allocation): upload + lsh_encode_kernel, host
+    wall clock; the first round warms the workspaces up and is dropped"""
+    idx = faiss.IndexLSH(x.shape[1], nbits, True, thresholds)
+    idx.train(x)
+    times = []
+    for _ in range(runs + 1):
+        idx.reset()
+        t0 = time.perf_counter(); idx.add(x); times.append(round((time.perf_counter() - t0) * 1e3, 3))
+    out = {"rows": int(x.shape[0]), "d": int(x.shape[1]), "nbits": nbits, "train_thresholds": thresholds, "library": Path(_lib.LIB_PATH).name,
+           "add_wall_ms": times[1:]}
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     dest = Path(args[0]) if args else ROOT / "profiles" / "lsh_thresholds.json"
+    if "--encode" in sys.argv:  # the encoder alone: one series per (thresholds, code width), for comparing two builds (KNN355_LIB)
+        x = rows(200_000)
+        res = {"what": "IndexLSH add(x) of 200 000 x 1024 rows: upload + lsh_encode_kernel, host wall clock in ms",
+               "legs": [encode_leg(x, nbits, thr) for nbits in (1024, 2048) for thr in (False, True)]}
+        dest.parent.mkdir(parents=True, exist_ok=True)
+        dest.write_text(json.dumps(res, indent=1) + "\n")
+        return
     res = {"what": "IndexLSH train_thresholds: train(x) vs add(x) of the same rows; times in ms (HIP events for the split, host wall clock otherwise)",
            "legs": [], "search": []}
     x = rows(200_000)
