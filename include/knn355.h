@@ -670,12 +670,20 @@ int knn_set_tuning(knn_handle h, int32_t query_tile, int32_t nchunks, int32_t fl
  * the copies, keep every row a rigorous error bound cannot rule out, re-score those with the fp32 chain and return the same
  * bits as the fp32 scan; a query the bound cannot serve falls back to the fp32 scan on the device.  A row that is not finite
  * turns the path off until knn_reset.  mode 0 (default) = off.  Not for HNSW indexes (KNN_ERR_UNSUPPORTED).  With
- * KNN355_SCAN16=0 in the environment mode 1 is ignored. */
+ * KNN355_SCAN16=0 in the environment modes 1 and 2 are ignored.
+ *   mode 2 keeps 12-bit fixed-point copies INSTEAD of the fp16 ones (+37.5 % of the fp32 row bytes, a quarter fewer bytes per
+ * scan): per row an exponent e with max|x| 2^-e in [2^10, 2^11) and n = round-to-nearest-even(x 2^-e) clamped to
+ * [-2047, 2047], stored as a byte plane and a nibble plane in tiles of 256 rows.  The integers are exact in fp16, so the scan
+ * multiplies exact fp16 values and the same bound holds with a larger measured copy error; the window is wider
+ * (k' = min(2048, max(3k, k + 128)) instead of max(2k, k + 64)).  Everything else is mode 1's.  With KNN355_SCAN_FORMAT=16
+ * in the environment mode 2 is taken as mode 1 (same-tree A/B). */
 int knn_flat_set_scan16(knn_handle h, int32_t mode);
 /* used = some piece of the last search took the 16-bit prefilter, candidates_max = the most rows any of its queries
  * re-scored, fallbacks =
  * prefiltered searches of this handle that fell back to the fp32 scan so far.  Waits for the device. */
 int knn_last_scan16_info(knn_handle h, int32_t *used, int32_t *candidates_max, int64_t *fallbacks);
+/* format = the row copies the last search's prefilter scanned: 16 (fp16), 12 (12-bit), 0 if it did not take the prefilter */
+int knn_last_scan16_format(knn_handle h, int32_t *format);
 
 /* Diagnostic entry: makes the index APPROXIMATE ON PURPOSE, as the coarse entry indexes of an HNSW index are.  Before the first
  * add AND before knn_flat_reserve (the row stride changes: an index that already has storage is refused with KNN_ERR_INVALID

@@ -145,6 +145,7 @@ def _declare(L):
         "knn_last_seed_info": (c_int32, [H, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)]),
         "knn_flat_set_scan16": (c_int32, [H, c_int32]),
         "knn_last_scan16_info": (c_int32, [H, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
+        "knn_last_scan16_format": (c_int32, [H, POINTER(c_int32)]),
         "knn_flat_set_approx16": (c_int32, [H]),
         "knn_flat_reserve": (c_int32, [H, c_int64]),
         "knn_flat_range_search": (c_int32, [H, c_void_p, c_int64, c_float, c_void_p]),

@@ -1117,7 +1117,7 @@ __device__ __forceinline__ void sched_spread()
 // accumulator register turns the scaled dot products into approximate scores; from there on the build is the fp32 one, run
 // with k' > k.  Its output is the exact top-k' of the APPROXIMATE scores, which the re-scoring tail checks against the
 // error bound and scores exactly (rescore16_kernel).  Inner product, one 32-query tile per launch.
-template <int WM, int WN, int TM, int TN, bool L2, bool NTDB = false, bool SYM = false, bool BF16 = false, int DNQ = 0, int Q16 = 0, bool F16X = false>
+template <int WM, int WN, int TM, int TN, bool L2, bool NTDB = false, bool SYM = false, bool BF16 = false, int DNQ = 0, int Q16 = 0, bool F16X = false, bool X12 = false>
 __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel(ScanParams p)
 {
     if (p.gate) { // (a gated fallback launch: uniform over the workgroup, in front of every barrier)
@@ -1127,6 +1127,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
     }
     constexpr bool DIFF = DNQ > 0; // the difference build, for batches of up to DNQ queries (8, 12, 16 or 20)
     static_assert(!F16X || (NTDB && !L2 && !SYM && !BF16 && DNQ == 0 && Q16 == 0 && TN == 1), "the 16-bit prefilter: one query tile, inner product");
+    static_assert(!X12 || (F16X && WM == 4 && TM == 2), "the 12-bit row copies: the prefilter's 256-row tile");
     constexpr bool H16 = BF16 || F16X; // 16-bit operands: a staged 128-byte segment holds 64 values
     static_assert(WM * WN == 4, "4 waves per workgroup");
     static_assert(!DIFF || (L2 && !SYM && !BF16 && WN == 1 && TN == 1), "the difference build: one 32-query tile, squared L2");
@@ -1141,9 +1142,15 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
     // through the sparse epilogue
     constexpr bool SPARSE = !NTDB && !BF16 && DNQ == 0 && Q16 == 0 && WM == 2 && WN == 2 && TM == TN && (TM == 2 || TM == 4);
     constexpr int ROWS = DT + QT;           // staged rows per K step
-    constexpr int NGRP = ROWS / 8;          // staging instructions per K step (8 rows each) ...
+    // (X12: a K step of a tile is 16 KB of high bytes + 8 KB of low nibbles, already in LDS order, + 4 KB of fp16 queries)
+    constexpr int X12_DB = 24;              // X12: staging instructions of a K step that fetch rows (1 KB each)
+    constexpr int NGRP = X12 ? X12_DB + QT / 8 : ROWS / 8; // staging instructions per K step (8 rows each) ...
     constexpr int NI = (NGRP + 3) / 4;      // ... per wave; a wave short of one (304 rows: 38 over 4 waves) repeats its previous one
     static_assert(ROWS % 8 == 0, "staging split");
+    static_assert(!X12 || NGRP % 4 == 0, "X12: every wave issues whole rounds, the last of them the queries'");
+    constexpr int NDBI = X12 ? X12_DB / 4 : DT / 32; // a wave's first NDBI staging instructions fetch rows, the rest queries
+    constexpr int KOFF_DB = X12 ? X12_DB * 256 : 32; // floats from one K step of a lane's row source to the next
+    constexpr int B_OFF = X12 ? X12_DB * 1024 : DT * 128; // the staged queries behind the staged rows
     constexpr int STAGE_BYTES = ROWS * 128; // 32 floats per row
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *stage0 = smem;
@@ -1234,10 +1241,14 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
     for (int n = 0; n < NI; n++) {
         int ii = wave + 4 * n;
         if (ii >= NGRP) ii -= 4; // (the same rows once more, to the same place: harmless)
-        int row_local = 8 * ii + (lane >> 3);
+        int row_local = X12 ? (ii < X12_DB ? 0 : DT + 8 * (ii - X12_DB) + (lane >> 3)) : 8 * ii + (lane >> 3);
         int sp = lane & 7;
         lds_off[n] = ii * 1024;
-        if (row_local < DT) {
+        if (X12 && ii < X12_DB) { // 1 KB of the tile's K step as it lies in memory: lane l's 16 bytes go to LDS bytes 16 l ..
+            is_db[n] = true;
+            rloc[n] = 0;
+            srcp[n] = p.xb + ii * 256 + lane * 4; // tile and K step added per tile
+        } else if (row_local < DT) {
             is_db[n] = true;
             rloc[n] = row_local;
             int s = sp ^ ((row_local >> 1) & 7);
@@ -1346,7 +1357,9 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
         if (!staged0) { // (256 x 256 builds: the previous tile's epilogue has worked these out already -- and staged the first K step)
 #pragma unroll
             for (int n = 0; n < NI; n++) {
-                if (is_db[n]) {
+                if (X12 && is_db[n]) { // (tiles past the end of a view are whole in memory: rows that are not there are dropped behind the K loop)
+                    tsrc[n] = srcp[n] + (int64_t)cur_tile * KT * KOFF_DB;
+                } else if (is_db[n]) {
                     int64_t r = view_row(min(row0 + rloc[n], p.nb - 1), p.row_mul, p.vshift);
                     tsrc[n] = srcp[n] + r * p.dp;
                 } else {
@@ -1391,7 +1404,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
         auto compute = [&](const char *cur, auto &&dma, auto nd_tag) {
             constexpr int ND = decltype(nd_tag)::value;
             const char *A = cur;
-            const char *B = cur + DT * 128;
+            const char *B = cur + B_OFF;
             if constexpr (DIFF) {
 #pragma unroll
                 for (int n = 0; n < ND; n++) dma(n); // (the next K step's staging goes out first: the chains below take microseconds)
@@ -1534,6 +1547,52 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 substep16(std::integral_constant<int, 1>{});
                 substep16(std::integral_constant<int, 2>{});
                 substep16(std::integral_constant<int, 3>{});
+                return;
+            }
+            if constexpr (X12) {
+                // 12-bit row copies: n = 16 (hb - 128) + lo, |n| <= 2047, as a byte hb and a nibble lo per value.  A
+                // K step of a row tile lies in memory as it lies here: [row tile of 32][half][lane][16 B] high bytes, then
+                // [row tile of 32][lane][16 B] nibbles -- lane (li, lh) finds the 32 + 16 bytes of its row's values
+                // k = 16 t + 8 lh + j (t = 0..3: the four MFMAs of the K step, j = 0..7) with three ds_read_b128, consecutive
+                // lanes 16 bytes apart.  High bytes: byte 8 (t & 1) + j of half t / 2; nibbles: byte 4 t + (j & 3), low nibble
+                // j < 4.  The fp16 fragment is rebuilt exactly: 0x6400 | b is 1024 + b, so with A = 1024 + hb and L = 1024 + lo
+                // fma(A - 1216, 16, L) = 16 (hb - 192) + 1024 + lo = n -- the difference is exact (|hb - 192| <= 192), the fma
+                // rounds once and n is an fp16 number.  Per 8 values: 3 mask / shift, 8 byte permutes, 4 packed subtracts, 4 packed fma.
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+                u32x4 hi[TM][2], lo[TM];
+                f32x4 bq[4][TN];
+#pragma unroll
+                for (int a = 0; a < TM; a++) {
+                    hi[a][0] = *(const u32x4 *)(A + ((wm * TM + a) * 2 + 0) * 1024 + lane * 16);
+                    hi[a][1] = *(const u32x4 *)(A + ((wm * TM + a) * 2 + 1) * 1024 + lane * 16);
+                    lo[a] = *(const u32x4 *)(A + DT * 64 + (wm * TM + a) * 1024 + lane * 16);
+                }
+#pragma unroll
+                for (int t = 0; t < 4; t++)
+#pragma unroll
+                    for (int b = 0; b < TN; b++) bq[t][b] = *(const f32x4 *)(B + ((wn * TN + b) * 32 + li) * 128 + (((2 * t + lh) ^ swz) * 16));
+#pragma unroll
+                for (int n = 0; n < ND; n++) dma(n); // (the next K step's staging first: the longest lead the double buffer allows)
+                const f16x2 bias = {(_Float16)1216.0f, (_Float16)1216.0f}, sixteen = {(_Float16)16.0f, (_Float16)16.0f};
+                auto pair = [&](uint32_t hw, uint32_t lw, uint32_t sel) -> uint32_t {
+                    const f16x2 ah = __builtin_bit_cast(f16x2, __builtin_amdgcn_perm(0x64646464u, hw, sel)) - bias;
+                    const f16x2 al = __builtin_bit_cast(f16x2, __builtin_amdgcn_perm(0x64646464u, lw, sel));
+                    return __builtin_bit_cast(uint32_t, __builtin_elementwise_fma(ah, sixteen, al));
+                };
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+#pragma unroll
+                    for (int a = 0; a < TM; a++) {
+                        const uint32_t h0 = hi[a][t >> 1][2 * (t & 1)], h1 = hi[a][t >> 1][2 * (t & 1) + 1];
+                        const uint32_t l0 = lo[a][t] & 0x0F0F0F0Fu, l1 = (lo[a][t] >> 4) & 0x0F0F0F0Fu;
+                        // (selector bytes 0..3: the data word's bytes, 4: the constant's 0x64)
+                        const u32x4 fr = {pair(h0, l0, 0x04010400u), pair(h0, l0, 0x04030402u), pair(h1, l1, 0x04010400u), pair(h1, l1, 0x04030402u)};
+#pragma unroll
+                        for (int b = 0; b < TN; b++)
+                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fr), __builtin_bit_cast(f16x8, bq[t][b]), acc[a][b], 0, 0, 0);
+                    }
+                }
                 return;
             }
             // fragments of sub-step t+1 are requested before the MFMAs of sub-step t are issued,
@@ -1740,7 +1799,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
             // prologue: stage K step 0 into buffer 0
 #pragma unroll
             for (int n = 0; n < NI; n++) {
-                if (NTDB && n < DT / 32) stage_issue<true>(tsrc[n], stage0 + lds_off[n]); // rows, not queries
+                if (NTDB && n < NDBI) stage_issue<true>(tsrc[n], stage0 + lds_off[n]); // rows, not queries
                 else stage_issue<false>(tsrc[n], stage0 + lds_off[n]);
             }
             // Batch launches: the two workgroups of a CU take TURNS in their K loops.  Per-workgroup stamps showed a K loop
@@ -1774,9 +1833,9 @@ __global__ __launch_bounds__(256, (TM * TN >= 16 ? 1 : 2)) void flat_scan_kernel
                 // from the third K step on.  Inline asm: the waitcnt pass cannot drop it.)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads(); // buffer nxt is free
-                const int koff = (kt + 1) * 32;
+                const int koff = (kt + 1) * 32, koff_db = (kt + 1) * KOFF_DB;
                 compute(cur, [&](int n) {
-                    if (NTDB && n < DT / 32) stage_issue<true>(tsrc[n] + koff, nxt + lds_off[n]);
+                    if (NTDB && n < NDBI) stage_issue<true>(tsrc[n] + koff_db, nxt + lds_off[n]);
                     else stage_issue<false>(tsrc[n] + koff, nxt + lds_off[n]);
                 }, nd_all{});
             }
@@ -2891,6 +2950,71 @@ __global__ __launch_bounds__(256) void scan16_rows_kernel(const float *__restric
     }
 }
 
+// The 12-bit copies (knn_flat_set_scan16 mode 2): n = rint(x 2^-e) clamped to [-2047, 2047] with max|x| 2^-e in [2^10, 2^11)
+// (e >= -128), x' = 2^e n -- integers an fp16 holds exactly, so the scan multiplies exact fp16 values as before and only R is
+// larger.  Stored as u = n + 2048 = 16 hb + lo in the order the scan's LDS wants them (flat_scan_kernel, X12): per tile of 256
+// rows and K step of 64 values 16 KB of bytes hb, then 8 KB of nibbles lo; 1.5 bytes per value.  One wave per row, a lane
+// per 8 values (one K-step quarter of a lane half: 8 bytes + 4 bytes).  Statistics as scan16_rows_kernel's, from the actual x'.
+__global__ __launch_bounds__(256) void scan12_rows_kernel(const float *__restrict__ xb, int dp, int64_t r0, int64_t n, int dp16,
+                                                          uint8_t *__restrict__ xs, int8_t *__restrict__ xexp, uint32_t *__restrict__ stat)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t r = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= r0 + n) return;
+    const float *x = xb + (size_t)r * dp;
+    float mx = 0.0f;
+    bool nf = false;
+    for (int i = lane; i < dp; i += 64) {
+        const float v = x[i];
+        nf |= !isfinite(v);
+        mx = fmaxf(mx, fabsf(v));
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const bool bad = __ballot(nf) != 0ull;
+    int e = (mx > 0.0f && isfinite(mx)) ? ilogbf(mx) - 10 : 0;
+    e = max(e, -128);
+    const int KT = dp16 / 64, rt = (int)(r & 255), li = rt & 31, wa = rt >> 5; // (wa: the row tile of 32 inside the tile of 256)
+    uint8_t *tile = xs + (size_t)(r >> 8) * KT * 24576;
+    double sx = 0.0, sxp = 0.0, sd = 0.0;
+    for (int g = lane; g < dp16 / 8; g += 64) { // values 8 g .. 8 g + 7: K step g / 8, MFMA t = (g / 2) % 4, lane half g % 2
+        const int ks = g >> 3, t = (g >> 1) & 3, lh = g & 1;
+        uint32_t hw[2] = {0u, 0u}, lw = 0u;
+        for (int j = 0; j < 8; j++) {
+            const int i = 8 * g + j;
+            const float v = i < dp ? x[i] : 0.0f;
+            float nv = rintf(ldexpf(v, -e)); // (round to nearest even; not finite only in a row that turns the path off)
+            nv = fminf(fmaxf(nv, -2047.0f), 2047.0f);
+            const int ni = nv == nv ? (int)nv : 0;
+            const uint32_t u = (uint32_t)(ni + 2048);
+            hw[j >> 2] |= (u >> 4) << (8 * (j & 3));
+            lw |= (u & 15u) << (8 * (j & 3) + 4 * (j >> 2));
+            const double xp = ldexp((double)ni, e), dv = (double)v;
+            sx += dv * dv;
+            sxp += xp * xp;
+            sd += (dv - xp) * (dv - xp);
+        }
+        uint8_t *ksp = tile + (size_t)ks * 24576;
+        *(uint2 *)(ksp + (wa * 2 + (t >> 1)) * 1024 + (lh * 32 + li) * 16 + (t & 1) * 8) = make_uint2(hw[0], hw[1]);
+        *(uint32_t *)(ksp + 16384 + wa * 1024 + (lh * 32 + li) * 16 + t * 4) = lw;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        sx += __shfl_xor(sx, o, 64);
+        sxp += __shfl_xor(sxp, o, 64);
+        sd += __shfl_xor(sd, o, 64);
+    }
+    if (lane == 0) {
+        xexp[r] = (int8_t)e; // (in [-128, 117])
+        if (bad) {
+            atomicOr(&stat[S16_NONFINITE], 1u);
+        } else {
+            atomicMax(&stat[S16_R], __float_as_uint(s16_up(sqrt(sd))));
+            atomicMax(&stat[S16_XP], __float_as_uint(s16_up(sqrt(sxp))));
+            atomicMax(&stat[S16_X], __float_as_uint(s16_up(sqrt(sx))));
+            atomicMax((int *)&stat[S16_EMAX], e);
+        }
+    }
+}
+
 // Per search: the fp16 queries + exponents, and each query's bound B_q >= |s - s~| over every row:
 //   B_q = |q| R + |q - q'| X' + g(dp, u) |q| X + g(dp16, 4u) |q'| X' + (dp + 1) 2^-149,   g(n, v) = n v / (1 - n v), u = 2^-24
 // (the contract's fmaf chain; the f16 MFMA's fp32 accumulation, allowed four times the error of a round-to-nearest add; the
@@ -3221,6 +3345,7 @@ struct knn_index_s {
     // exact 16-bit prefilter (knn_flat_set_scan16): fp16 copies of the rows, [cap_rows][dp16] (dp16 = d rounded
     // up to 64), one int8 exponent per row, the index-wide statistics (S16_*).  Views use their parent's.
     int scan16 = 0;               // 0 off, 1 copies kept, 2 dropped (allocation failed) until the index is reset
+    int s16_fmt = 16;             // the copies' format: 16 = fp16 [cap_rows][dp16]; 12 = 12-bit fixed point in tiles (scan12_rows_kernel)
     // the copies cover every row and every row is finite -- shared with the views, so a row added to the parent that is not
     // finite turns the path off for them too
     std::shared_ptr<std::atomic<bool>> s16_ok = std::make_shared<std::atomic<bool>>(false);
@@ -3232,6 +3357,7 @@ struct knn_index_s {
     std::string s16_note;
     DevBuf ws_q16x, ws_s16q, ws_s16ak, ws_s16ok, ws_s16stat; // fp16 queries; exponents, bounds, flags; keys; [largest window, fallbacks]
     bool last_s16_used = false;   // some piece of the last search (search_keys_impl) took the prefilter
+    int last_s16_fmt = 0;         // ... on copies of this format (recorded where the pass is enqueued)
     int s16_pieces = 0;           // ... how many: the first one restarts the largest-window counter
     float *yn = nullptr; // [cap_rows + pad]
     size_t xb_bytes = 0, yn_bytes = 0; // allocation sizes (may exceed the row capacity: pooled)
@@ -3473,6 +3599,7 @@ extern "C" int knn_flat_view(knn_handle parent, knn_handle *out)
     h->cap_rows = parent->ntotal;
     h->scan16 = parent->scan16;
     h->dp16 = parent->dp16;
+    h->s16_fmt = parent->s16_fmt;
     h->s16_rows = parent->s16_rows;
     h->s16_exp = parent->s16_exp;
     h->s16_stat = parent->s16_stat;
@@ -3629,7 +3756,8 @@ static int approx16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t
 static int scan16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s)
 {
     if (h->scan16 != 1 || h->is_view) return 0;
-    const size_t need = (size_t)h->cap_rows * h->dp16 * 2;
+    // (12-bit copies: whole tiles of 256 rows, 1.5 bytes per value)
+    const size_t need = h->s16_fmt == 12 ? (size_t)((h->cap_rows + 255) / 256) * (h->dp16 / 64) * 24576 : (size_t)h->cap_rows * h->dp16 * 2;
     if (h->cap_rows > 0 && (h->s16_rows_buf.bytes < need || h->s16_exp_buf.bytes < (size_t)h->cap_rows || !h->s16_stat_buf.p)) {
         HIP_TRY(hipStreamSynchronize(s));
         if (h->s16_rows_buf.p || h->s16_exp_buf.p) {
@@ -3645,7 +3773,7 @@ static int scan16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s
             h->s16_stat = nullptr;
             h->s16_ok->store(false);
             h->scan16 = 2;
-            h->s16_note = "dropped: no device memory for the fp16 copies";
+            h->s16_note = "dropped: no device memory for the row copies";
             return 0;
         }
         n += r0;
@@ -3657,8 +3785,12 @@ static int scan16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s
     h->s16_stat = (const uint32_t *)h->s16_stat_buf.p;
     uint32_t init[S16_NSTAT] = {0u, 0u, 0u, 0x80000000u, 0u, 0u, 0u, 0u}; // (largest exponent: INT_MIN)
     if (r0 == 0) HIP_TRY(hipMemcpyAsync(h->s16_stat_buf.p, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(scan16_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->xb, h->dp, r0, n, h->dp16,
-                       (_Float16 *)h->s16_rows_buf.p, (int8_t *)h->s16_exp_buf.p, (uint32_t *)h->s16_stat_buf.p);
+    if (h->s16_fmt == 12)
+        hipLaunchKernelGGL(scan12_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->xb, h->dp, r0, n, h->dp16,
+                           (uint8_t *)h->s16_rows_buf.p, (int8_t *)h->s16_exp_buf.p, (uint32_t *)h->s16_stat_buf.p);
+    else
+        hipLaunchKernelGGL(scan16_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->xb, h->dp, r0, n, h->dp16,
+                           (_Float16 *)h->s16_rows_buf.p, (int8_t *)h->s16_exp_buf.p, (uint32_t *)h->s16_stat_buf.p);
     HIP_TRY(hipGetLastError());
     uint32_t nonfinite = 0;
     HIP_TRY(hipMemcpyAsync(&nonfinite, (const uint32_t *)h->s16_stat_buf.p + S16_NONFINITE, 4, hipMemcpyDeviceToHost, s));
@@ -3902,7 +4034,7 @@ static ScanKernel scan_build(bool l2, bool approx16, bool one_qtile)
 // The flat_scan_kernel build that serves a launch: query tile qt, squared L2 or inner product, bf16 rows, one query tile or
 // several, the width of the difference build (0: none), the pass of a prefiltered search (S16Pass::mode).  nullptr with the
 // error set when no build serves the combination (scan_kernel_illegal, plan.h).
-static ScanKernel pick_scan_kernel(int qt, bool l2, bool approx16, bool one_qtile, int diff_width, int pass_mode)
+static ScanKernel pick_scan_kernel(int qt, bool l2, bool approx16, bool one_qtile, int diff_width, int pass_mode, int s16_fmt = 16)
 {
     if (const char *why = scan_kernel_illegal(qt, l2, approx16, one_qtile, pass_mode)) {
         set_err(KNN_ERR_INVALID, why);
@@ -3916,6 +4048,7 @@ static ScanKernel pick_scan_kernel(int qt, bool l2, bool approx16, bool one_qtil
     case 48: return l2 ? flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 0, 3> : flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 3>;
     case 64: return scan_build<2, 2, 2, 1>(l2, approx16, one_qtile);
     }
+    if (pass_mode == 1 && s16_fmt == 12) return flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true, true>; // ... on the 12-bit row copies
     if (pass_mode == 1) return flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>; // the 16-bit pass of a prefiltered search (search_view_s16)
     // (difference builds for up to 8, 12, 16 and 19 queries: the vector work of a K step grows with the build's width -- up to 8
     // queries scan at the speed of their HBM traffic)
@@ -3989,13 +4122,14 @@ static PlanCtx plan_ctx(const knn_index_s *h)
     c.metric = h->metric; c.approx16 = h->approx16;
     c.flags = h->flags; c.force_qt = h->force_qt; c.force_chunks = h->force_chunks;
     c.num_cus = h->num_cus; c.batch_nq = h->batch_nq; c.pub_rounds_force = h->pub_rounds_force; c.ntotal = h->ntotal;
+    c.s16_fmt = h->s16_fmt;
     return c;
 }
 
-// One prefiltered search, six launches on the caller's stream, no host wait:
+// One prefiltered search, ten launches on the caller's stream, no host wait:
 //   scan16_queries_kernel   fp16 queries, exponents, bounds B_q, the per-query fallback flags
-//   16-bit pass             the streaming scan machinery on the fp16 copies with k' = s16_kprime(k): the exact top-k'
-//                           of the approximate scores (state reset, flat_scan_q32_d256_f16x, selection)
+//   16-bit pass             the streaming scan machinery on the fp16 (or 12-bit) copies with k' = s16_kprime(k, format): the exact
+//                           top-k' of the approximate scores (state reset, flat_scan_q32_d256_f16x / _x12, selection in two launches)
 //   rescore16_kernel        the window check and the exact scores of the rows inside the window: a grid of (query, 16 of its
 //                           k' keys), every row fetched by a whole workgroup with coalesced 16-byte loads
 //   selection               the exact top-k of those -> D / I or keys, exactly as the fp32 search writes them
@@ -4004,7 +4138,7 @@ static PlanCtx plan_ctx(const knn_index_s *h)
 static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int vshift,
                            const SearchOut &out, hipStream_t s, int *reset_flag)
 {
-    const int kp = s16_kprime(k);
+    const int kp = s16_kprime(k, h->s16_fmt);
     if (h->ws_q16x.ensure((size_t)nq * h->dp16 * 2, h->done, s) || h->ws_s16q.ensure((size_t)nq * 16, h->done, s) ||
         h->ws_s16ak.ensure((size_t)nq * kp * 8, h->done, s) || h->ws_s16ok.ensure((size_t)nq * kp * 8, h->done, s))
         return set_err(KNN_ERR_HIP, "search: out of device memory");
@@ -4046,6 +4180,7 @@ static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, 
     gated.gate_count = sstat + 1;
     rc = search_view(h, q_dev, xn, nq, k, id_base, 1, vshift, 0, out, false, s, nullptr, gated);
     h->last_s16_used = true;
+    h->last_s16_fmt = h->s16_fmt;
     h->s16_pieces++;
     return rc;
 }
@@ -4058,7 +4193,7 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
 {
     const int64_t nb = view_rows(h->ntotal, row_mul, vshift);
     const PlanCtx c = plan_ctx(h);
-    if (h->scan16 == 1 && h->s16_ok->load() && h->s16_rows && !out.seed_cnt && s16_eligible(c, pass.mode, nb, nq, k, row_mul, level, h->dp))
+    if (h->scan16 == 1 && h->s16_ok->load() && h->s16_rows && !out.seed_cnt && s16_eligible(c, pass.mode, nb, nq, k, row_mul, level, h->dp, h->s16_fmt))
         return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
     if (level >= knn_index_s::MAX_LEVELS) return set_err(KNN_ERR_INVALID, "search: seed recursion too deep");
     const SearchPlan plan = plan_search(c, nb, nq, k, level, row_mul, allow_stat, pass.mode);
@@ -4127,6 +4262,8 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
         p.dp = h->dp / 2;
     }
     if (pass.mode == 1) { // the 16-bit pass: fp16 rows and queries (q_dev), a row is dp16 / 2 four-byte units
+        // (the 12-bit build addresses whole tiles of consecutive rows: plan_search gives its pass no sample, and nothing else strides it)
+        if (h->s16_fmt == 12 && (row_mul != 1 || sstride)) return set_err(KNN_ERR_INVALID, "search: the 12-bit row copies cannot serve a strided view");
         p.xb = (const float *)h->s16_rows;
         p.dp = h->dp16 / 2;
         p.xexp = h->s16_exp;
@@ -4175,14 +4312,14 @@ static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int6
     }
 #endif
     if (top && (rc = open_timed_launch(h, s))) return rc;
-    const ScanKernel kern = pick_scan_kernel(pl.qt, h->metric == KNN_METRIC_L2, h->approx16, pl.nqtiles == 1, pl.diff ? diff_build_width(nq) : 0, pass.mode);
+    const ScanKernel kern = pick_scan_kernel(pl.qt, h->metric == KNN_METRIC_L2, h->approx16, pl.nqtiles == 1, pl.diff ? diff_build_width(nq) : 0, pass.mode, h->s16_fmt);
     if (!kern) return KNN_ERR_INVALID;
     rc = scan_lds_opt_in(kern, pl.lds);
     if (!rc) rc = launch_scan(kern, p, pl.grid, pl.lds, s);
     if (rc) return rc;
     if (top) {
         HIP_TRY(hipEventRecord(h->ev1, s));
-        h->last_kernel = pass.mode == 1 ? std::string(pl.name) + "_f16x" : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
+        h->last_kernel = pass.mode == 1 ? std::string(pl.name) + (h->s16_fmt == 12 ? "_x12" : "_f16x") : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
         h->last_seed_stride = pub_rounds ? -pub_rounds * pub_m : sstride; // (negative: tile-minimum seed, keys per workgroup and query)
         h->last_seed_stat = seed_stat ? plan.seed_j : 0;
         h->last_sample_rows = sstride ? view_rows(nb, sstride, p.vshift) : 0;
@@ -4980,14 +5117,17 @@ extern "C" int knn_flat_reserve(knn_handle h, int64_t nrows)
 extern "C" int knn_flat_set_scan16(knn_handle h, int32_t mode)
 {
     if (!h) return set_err(KNN_ERR_INVALID, "set_scan16: null handle");
-    if (mode != 0 && mode != 1) return set_err(KNN_ERR_INVALID, "set_scan16: mode must be 0 or 1");
+    if (mode != 0 && mode != 1 && mode != 2) return set_err(KNN_ERR_INVALID, "set_scan16: mode must be 0, 1 or 2");
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->is_view) return set_err(KNN_ERR_INVALID, "set_scan16: a view uses its parent's setting");
     if (mode && (h->approx16 || h->keep16)) return set_err(KNN_ERR_UNSUPPORTED, "set_scan16: not for an index that keeps bf16 copies (HNSW)");
     if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "set_scan16: the index already holds rows");
     const char *env = getenv("KNN355_SCAN16");
-    if (mode == 1 && env && strcmp(env, "0") == 0) mode = 0; // (same-tree A/B runs)
-    h->scan16 = mode;
+    if (mode && env && strcmp(env, "0") == 0) mode = 0; // (same-tree A/B runs)
+    const char *fenv = getenv("KNN355_SCAN_FORMAT");
+    if (mode == 2 && fenv && strcmp(fenv, "16") == 0) mode = 1; // (... of the two formats)
+    h->scan16 = mode ? 1 : 0;
+    h->s16_fmt = mode == 2 ? 12 : 16;
     h->dp16 = round_up(h->d, 64);
     h->s16_note = mode ? "on" : "off";
     return 0;
@@ -5006,6 +5146,14 @@ extern "C" int knn_last_scan16_info(knn_handle h, int32_t *used, int32_t *candid
     if (used) *used = h->last_s16_used ? 1 : 0;
     if (candidates_max) *candidates_max = h->last_s16_used ? (int32_t)st[0] : 0;
     if (fallbacks) *fallbacks = (int64_t)st[1];
+    return 0;
+}
+
+extern "C" int knn_last_scan16_format(knn_handle h, int32_t *format)
+{
+    if (!h || !format) return set_err(KNN_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *format = h->last_s16_used ? h->last_s16_fmt : 0;
     return 0;
 }
 

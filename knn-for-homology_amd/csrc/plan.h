@@ -22,6 +22,7 @@ struct PlanCtx {
     int64_t batch_nq = 0;         // the caller's whole batch while a search works through it in pieces (0: this call is the batch)
     int pub_rounds_force = 0;     // tile-minimum seed: rounds of publications (0: the planner's choice)
     int64_t ntotal = 0;
+    int s16_fmt = 16;             // the prefilter's row copies: 16 = fp16, 12 = 12-bit tiles (knn_flat_set_scan16 mode 2)
 };
 
 // rows of the view with stride row_mul over a database of n rows
@@ -252,18 +253,24 @@ static int stat_seed_rank(int64_t S, int64_t N, int k)
 
 // approximate keys the 16-bit pass hands to the re-scoring tail: room for the window above the k-th (fp16 on normalised
 // rows: a few percent of k beyond it at 10 M rows, k = 100)
-static int s16_kprime(int k) { return std::min(KNN_WAVE_SELECT_MAX_K, std::max(2 * k, k + 64)); }
+// (fmt: the row copies' format, 16 = fp16, 12 = 12-bit fixed point -- its copy error R is about five times fp16's, so its
+// window is wider: 62 rows expected beyond the k-th at 10 M normalised rows, k = 100, against 24)
+static int s16_kprime(int k, int fmt = 16)
+{
+    if (fmt == 12) return std::min(KNN_WAVE_SELECT_MAX_K, std::max(3 * k, k + 128));
+    return std::min(KNN_WAVE_SELECT_MAX_K, std::max(2 * k, k + 64));
+}
 
 // Does a search of the view take the prefiltered path?  A one-query-tile streaming search (the 32-query build) by inner
 // product over an index whose fp16 copies cover every row, from nb >= 2^18 rows on (below that the fp32 scan's fixed costs
 // dominate and the tail's launches would not pay).  Batch, symmetric, difference, HNSW and range searches never do.
 // (the shape's half of the question; whether the copies exist and the search seeds no other is asked where the handle is: search_view.
 // dp: floats per padded row)
-static bool s16_eligible(const PlanCtx &c, int pass_mode, int64_t nb, int64_t nq, int k, int row_mul, int level, int dp)
+static bool s16_eligible(const PlanCtx &c, int pass_mode, int64_t nb, int64_t nq, int k, int row_mul, int level, int dp, int fmt = 16)
 {
     if (pass_mode || level != 0 || row_mul != 1) return false;
     if (c.metric != KNN_METRIC_INNER_PRODUCT || c.approx16 || (c.flags & KNN_TUNE_NO_SCAN16)) return false;
-    if (nq < 1 || nq > 32 || (c.force_qt != 0 && c.force_qt != 32) || s16_kprime(k) <= k) return false; // (k' = k: no room for a window)
+    if (nq < 1 || nq > 32 || (c.force_qt != 0 && c.force_qt != 32) || s16_kprime(k, fmt) <= k) return false; // (k' = k: no room for a window)
     if ((size_t)dp * 4 + 64 > 65536) return false; // (the widest row the path has served: rescore16_kernel walks a row in 1024-float slabs, its LDS does not grow with dp)
     return nb >= (1 << 18) || (c.flags & KNN_TUNE_SCAN16_ANY_NB);
 }
@@ -384,6 +391,9 @@ static SearchPlan plan_search(const PlanCtx &c, int64_t nb, int64_t nq, int k, i
         }
     }
     if (pass_mode == 2 && !pub_rounds) sstride = 0; // (a gated fallback runs no sample pass: its memsets could not be gated)
+    // (nor does the 16-bit pass over 12-bit copies: they lie in tiles of 256 consecutive rows, which a strided view cannot
+    // address -- without a tile-minimum seed that pass starts unseeded)
+    if (pass_mode == 1 && c.s16_fmt == 12 && !pub_rounds) sstride = 0;
     if (pub_rounds) {
         sstride = 0;
         // the bound sits near the k / (publications x tile rows) quantile; the first tile(s) of every chunk are filtered

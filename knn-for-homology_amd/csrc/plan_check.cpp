@@ -261,6 +261,19 @@ static void check_range(const PlanCtx &c, int64_t nq)
     INVARIANT(range_segcap(p, nq) >= 1);
 }
 
+// `plan_check s16`: lines "nb nq k flags" -> the prefilter's eligibility and k' for the fp16 and the 12-bit row copies
+static int run_s16()
+{
+    long long nb, nq;
+    int k, flags;
+    while (scanf("%lld %lld %d %d", &nb, &nq, &k, &flags) == 4) {
+        const PlanCtx c = make_ctx(nb, nq, KNN_METRIC_INNER_PRODUCT, flags, 0, 0, 0, false);
+        printf("%lld %lld %d %d: fp16 kprime %d eligible %d, 12-bit kprime %d eligible %d\n", nb, nq, k, flags, s16_kprime(k, 16),
+               (int)s16_eligible(c, 0, nb, nq, k, 1, 0, 1024, 16), s16_kprime(k, 12), (int)s16_eligible(c, 0, nb, nq, k, 1, 0, 1024, 12));
+    }
+    return 0;
+}
+
 static int run_sweep()
 {
     const int64_t nbs[] = {1, 255, 256, 257, 1023, 4096, 8192, 16385, 1 << 15, 1 << 18, (1 << 18) + 1, 1250000, 10000000, 2147483647};
@@ -303,7 +316,8 @@ int main(int argc, char **argv)
     if (argc == 2 && !strcmp(argv[1], "cases")) return run_cases();
     if (argc == 2 && !strcmp(argv[1], "sym")) return run_sym();
     if (argc == 2 && !strcmp(argv[1], "range")) return run_range();
+    if (argc == 2 && !strcmp(argv[1], "s16")) return run_s16();
     if (argc == 2 && !strcmp(argv[1], "sweep")) return run_sweep();
-    fprintf(stderr, "usage: plan_check cases|sym|range < lines | plan_check sweep\n");
+    fprintf(stderr, "usage: plan_check cases|sym|range|s16 < lines | plan_check sweep\n");
     return 2;
 }

@@ -76,7 +76,9 @@ class HipShardBackend:
 
     def __init__(self, d, metric):
         self.index = _faiss.IndexFlat(d, metric)
-        self.index.set_scan16(1)  # fp16 copies of the shard: its streaming searches take the exact 16-bit prefilter
+        # 12-bit copies of the shard: its streaming searches take the exact 16-bit prefilter at a quarter fewer bytes than with
+        # fp16 copies.  A caller who wants fp16 copies, or none, calls index.set_scan16(1) / (0) before the first add
+        self.index.set_scan16(2)
         self.metric = metric
         self.device = torch.device("cuda", int(_lib.lib().knn_device_of(self.index._h)))
         self._lanes = None
