@@ -470,6 +470,56 @@ int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores, int64_t nq
                       const int64_t *totals, const double *thresholds, int32_t nthr,
                       double *precision_out, double *recall_out,
                       int64_t *selected_out, int64_t *tp_out, int64_t *empty_out);
+/* One stable order over every hit of a result set, with look-ups: pfam/pfam.py:561-598 (the dataset-wide precision-recall
+ * curve), the cumulative curves is_correct[argsort(key)].cumsum() (cath/cath.py:656-675, 738-771; pfam/pfam.py:166-177,
+ * 213-236) and the order statistics behind numpy.quantile(scores[:, :limit], ...) (pfam/proteins.py:626-648).  All
+ * pointers are host pointers.  scores is [rows][k], float32 (key_type KNN_RANK_F32) or float64 (KNN_RANK_F64); correct
+ * (may be NULL) is uint8 [rows][k], non-zero meaning correct.
+ *   elements    the N = rows * limit cells of columns 0 .. limit-1 (1 <= limit <= k); the flat position of cell
+ *               (row, column) is p = row * limit + column.  N <= 2^31 - 1.
+ *   key         the order-preserving unsigned image of the score, 32 or 64 bits: -0.0 is taken as +0.0 first (numpy
+ *               compares them equal); every NaN, of either sign and any payload, gets the one largest key, so NaN sorts
+ *               last, as in numpy.argsort; sub-normals order by their value, +-inf by theirs.  descending != 0
+ *               complements the image of every key but NaN's: NaN still sorts last, the rest in the order of
+ *               numpy.argsort(-scores, kind="stable").
+ *   order       ascending by key; equal keys in ascending flat position.  This is numpy.argsort(scores[:, :limit]
+ *               .flatten(), kind="stable").  The reference calls numpy's default sort, whose order among equal scores is
+ *               unspecified (and differs from the stable one on tied float64 input); here it is fixed.
+ *   C(r)        the number of correct cells among the ranks 0 .. r of the order (inclusive)
+ *   outputs     each only when asked for:
+ *               order_out int64 [N] (NULL: not wanted): order_out[r] = the flat position of the element of rank r
+ *               cum_out int64 [N] (NULL: not wanted): cum_out[r] = C(r)
+ *               nt > 0: for each targets[j] (int64), idx_out[j] = the first r with C(r) >= targets[j] -- 0 for a target
+ *               <= 0, N for a target that no r reaches -- and cum_at_out[j] = C(min(idx_out[j], N - 1))
+ *               nr > 0: sorted_at_out[j] (in the scores' type) = the score of the element of rank ranks[j], its bits
+ *               untouched (a -0.0 or a NaN's payload come back as they went in)
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: an unknown key_type; rows < 1;
+ * k < 1 or k > INT32_MAX; limit outside [1, k]; rows * limit > 2^31 - 1; nt or nr outside [0, INT32_MAX]; a null scores;
+ * nt > 0 with a null targets, idx_out or cum_at_out; nr > 0 with a null ranks or sorted_at_out; cum_out or nt > 0 without
+ * correct; a rank outside [0, N).
+ * The whole problem stays on the device for the call: the two arrays -- as given, or, when limit <= k / 2, their first
+ * `limit` columns packed on the host -- two key and two payload buffers of N entries, 256 counts per tile of 2048
+ * elements, and what the outputs asked for need; plan_rank in csrc/plan.h has every buffer's bytes and the call allocates
+ * exactly those.  A failed allocation returns KNN_ERR_HIP with nothing left allocated.
+ * Hot path (rank.inc): a least-significant-digit radix sort with 8-bit digits over (key, position << 1 | correct) pairs.
+ * rank_hist_kernel counts the digits of every pass in one read; a pass whose digit is the same in all keys is skipped.
+ * A pass is rank_count_kernel (per-tile digit counts), a two-level exclusive scan of the [256][tiles] table in
+ * digit-major order, and rank_scatter_kernel (stable rank inside the tile: bit-matching ballots inside a wave, per-wave
+ * digit counts through LDS).  C(r) is a two-level inclusive scan of the sorted flags; the targets are binary searches in
+ * C.  No workgroup waits on another; no floating-point number is rounded (the one
+ * floating-point instruction is the v != v that finds a NaN). */
+#define KNN_RANK_F32 0
+#define KNN_RANK_F64 1
+int knn_eval_rank(const void *scores, int32_t key_type, int64_t rows, int64_t k, int64_t limit, const uint8_t *correct,
+                  int32_t descending, int64_t *order_out, int64_t *cum_out,
+                  const int64_t *targets, int64_t nt, int64_t *idx_out, int64_t *cum_at_out,
+                  const int64_t *ranks, int64_t nr, void *sorted_at_out);
+/* measurement (tools/bench_rank.py): how the calling thread's last successful knn_eval_rank ran -- the passes it ran and
+ * the ones it skipped (together the bytes of a key), the tiles of a pass, and milliseconds ms[6]: on the host's clock the
+ * device allocations and the packing of the columns; by HIP events the upload of the two arrays, the sort (histograms
+ * and passes), the scan of the flags, the look-ups with their downloads.  The buffers are freed as the call returns:
+ * that time is in no figure. */
+int knn_last_rank_info(int32_t *passes_run, int32_t *passes_skipped, int64_t *tiles, float *ms /* [6] */);
 /* cath/cath.py:404-438 bootstrap_scores, the replicates behind the "+-" of the accuracy table (:441-458): per method and
  * per resample of the evaluable queries, the raw and the superfamily-normalized top-1 accuracy.  All arrays are host
  * arrays.  is_correct uint8 [nm][n]: row m is method m's verdict for each of the n evaluable queries, a non-zero byte

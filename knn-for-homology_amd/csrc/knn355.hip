@@ -5589,6 +5589,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "assemble.inc"
 #include "slices_eval.inc"
 #include "pr_curve.inc"
+#include "rank.inc"
 #include "bootstrap.inc"
 #include "pca.inc"
 #include "fuse.inc"

@@ -692,6 +692,68 @@ static int64_t range_segcap(const RangePlan &pl, int64_t nq)
     return std::max<int64_t>(1, std::min<int64_t>(chunk_rows, (int64_t)(KNN_RANGE_STAGE_BYTES / 12) / (nq * pl.nchunks)));
 }
 
+// ---- device-wide rank (rank.inc) ---------------------------------------------------
+static const int RANK_TILE = 2048;       // elements per workgroup of a counting or scatter pass: 256 threads x 8
+static const int RANK_SCAN_BLOCK = 1024; // entries per workgroup of the two-level scans: 256 threads x 4
+static const int RANK_SCAN_TOP = 256;    // block sums per step of the one workgroup that scans them
+static const int RANK_HIST_GRID = 1024;  // workgroups, at most, of the histogram of every pass
+
+struct RankPlan {
+    int64_t n;             // rows * limit elements
+    int64_t ntiles;        // tiles of RANK_TILE elements: the grid of a pass
+    int64_t table_entries; // 256 * ntiles digit counts
+    int64_t table_blocks;  // scan blocks over the table
+    int64_t cum_blocks;    // scan blocks over the n flags (0 without the running count)
+    int passes;            // 8-bit digits of a key: the passes at most
+    int key_bytes;
+    // the upload: with limit <= k / 2 the host packs the first `limit` columns of every row and the device copy is
+    // [rows][limit]; otherwise the arrays go up as they are, [rows][k], and the kernels skip the columns past the limit
+    bool pack;
+    int64_t dev_k; // row stride, in cells, of the device copy
+    // every device buffer of a call but the look-ups' own vectors (targets, ranks and their outputs): rank_run allocates
+    // exactly these
+    size_t scores_bytes, correct_bytes; // the device copies of the two arrays (correct: 0 without one)
+    size_t keys_bytes, pay_bytes;       // ONE key / payload buffer; the sort ping-pongs between two of each
+    size_t table_bytes, partial_bytes;  // the digit counts; the block sums of whichever scan has more blocks
+    size_t hist_bytes;                  // the digit histograms of every pass
+    size_t cum_bytes;                   // C(r) as 32-bit counts (0 without the running count)
+    size_t wide_bytes;                  // one int64 [n] staging buffer for order_out / cum_out (0 when neither is wanted)
+    size_t resident_bytes;              // the sum: scores + correct + 2 keys + 2 payloads + the rest
+};
+
+// false: not a legal problem (rows, k or limit below 1, limit above k, k above INT32_MAX, a key width other than 4 or 8 bytes,
+// rows * limit above 2^31 - 1 -- the payload keeps the position in 31 bits beside the flag -- or rows * k cells beyond size_t)
+static bool plan_rank(int64_t rows, int64_t k, int64_t limit, int key_bytes, bool has_correct, bool want_cum, bool want_wide, RankPlan *out)
+{
+    if (rows < 1 || k < 1 || limit < 1 || limit > k || k > (int64_t)INT32_MAX || (key_bytes != 4 && key_bytes != 8)) return false;
+    if (rows > (int64_t)INT32_MAX / limit) return false;
+    if (rows > (int64_t)(INT64_MAX / 16) / k) return false;
+    RankPlan pl;
+    pl.n = rows * limit;
+    pl.ntiles = (pl.n + RANK_TILE - 1) / RANK_TILE;
+    pl.table_entries = 256 * pl.ntiles;
+    pl.table_blocks = (pl.table_entries + RANK_SCAN_BLOCK - 1) / RANK_SCAN_BLOCK;
+    pl.cum_blocks = want_cum ? (pl.n + RANK_SCAN_BLOCK - 1) / RANK_SCAN_BLOCK : 0;
+    pl.passes = key_bytes;
+    pl.key_bytes = key_bytes;
+    pl.pack = 2 * limit <= k;
+    pl.dev_k = pl.pack ? limit : k;
+    const size_t n = (size_t)pl.n, cells = (size_t)rows * (size_t)pl.dev_k;
+    pl.scores_bytes = cells * (size_t)key_bytes;
+    pl.correct_bytes = has_correct ? cells : 0;
+    pl.keys_bytes = n * (size_t)key_bytes;
+    pl.pay_bytes = n * 4;
+    pl.table_bytes = (size_t)pl.table_entries * 4;
+    pl.partial_bytes = (size_t)std::max(pl.table_blocks, pl.cum_blocks) * 4;
+    pl.hist_bytes = (size_t)pl.passes * 256 * 4;
+    pl.cum_bytes = want_cum ? n * 4 : 0;
+    pl.wide_bytes = want_wide ? n * 8 : 0;
+    pl.resident_bytes = pl.scores_bytes + pl.correct_bytes + 2 * pl.keys_bytes + 2 * pl.pay_bytes + pl.table_bytes + pl.partial_bytes + pl.hist_bytes +
+                        pl.cum_bytes + pl.wide_bytes;
+    *out = pl;
+    return true;
+}
+
 // Which flat_scan_kernel build serves a launch is pick_scan_kernel's choice (knn355.hip) from (query tile, metric, bf16 rows,
 // one query tile, width of the difference build or 0, pass of a prefiltered search); this is its legality rule: nullptr, or
 // why no build serves the combination (the width of a difference build does not enter: every width has its build).

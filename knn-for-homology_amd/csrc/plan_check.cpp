@@ -6,6 +6,9 @@
 //                      max_wgs and the 64-bit FNV-1a hash of the items' integers
 //   plan_check range   reads lines "n nq metric batch [num_cus]": the range scan's plan of one block of nq queries -- kernel qt dt
 //                      nqtiles nchunks tiles_base tiles_rem grid diff lds segcap
+//   plan_check rank    reads lines "rows k limit key_bytes has_correct want_cum want_wide": the size plan of the device-wide rank -- n
+//                      ntiles table_entries table_blocks cum_blocks passes pack dev_k and the bytes of the scores, correct, one key buffer,
+//                      one payload buffer, table, block sums, histograms, running count, int64 staging and all of them, or "refused"
 //   plan_check sweep   walks a grid of shapes and flags and exits non-zero on a broken invariant
 // The device has 256 CUs throughout, but for a `range` line that names another count.  Built with the host compiler and -fsanitize=address,undefined (make plan_check).
 #include "plan.h"
@@ -261,6 +264,57 @@ static void check_range(const PlanCtx &c, int64_t nq)
     INVARIANT(range_segcap(p, nq) >= 1);
 }
 
+// the size plan of the device-wide rank: the tiles cover [0, n) and no more, the table is 256 counts per tile, the scan blocks
+// cover what they scan, every index a kernel forms fits its 32-bit type, the packing rule, and every buffer's bytes
+static void check_rank(int64_t rows, int64_t k, int64_t limit, int key_bytes, int outs)
+{
+    const bool has_correct = outs & 1, want_cum = has_correct && (outs & 2), want_wide = outs & 4;
+    RankPlan p;
+    const bool ok = plan_rank(rows, k, limit, key_bytes, has_correct, want_cum, want_wide, &p);
+    const auto where = [&] {
+        return describe("rank rows %lld k %lld limit %lld key %d outs %d", (long long)rows, (long long)k, (long long)limit, key_bytes, outs);
+    };
+    g_checked++;
+    const bool legal = rows >= 1 && k >= 1 && limit >= 1 && limit <= k && k <= INT32_MAX && (key_bytes == 4 || key_bytes == 8) &&
+                       (__int128)rows * limit <= INT32_MAX && (__int128)rows * k <= INT64_MAX / 16;
+    INVARIANT(ok == legal);
+    if (!ok || !legal) return;
+    INVARIANT(p.n == rows * limit && p.n <= INT32_MAX);
+    INVARIANT(p.ntiles >= 1 && p.ntiles * RANK_TILE >= p.n && (p.ntiles - 1) * RANK_TILE < p.n);
+    INVARIANT(p.ntiles * RANK_TILE <= (int64_t)UINT32_MAX); // (a tile's last element index, valid or not, is a uint32_t)
+    INVARIANT(p.table_entries == 256 * p.ntiles);
+    INVARIANT(p.table_blocks * RANK_SCAN_BLOCK >= p.table_entries && (p.table_blocks - 1) * RANK_SCAN_BLOCK < p.table_entries);
+    INVARIANT(want_cum ? (p.cum_blocks * RANK_SCAN_BLOCK >= p.n && (p.cum_blocks - 1) * RANK_SCAN_BLOCK < p.n) : p.cum_blocks == 0);
+    INVARIANT(p.table_blocks <= INT32_MAX && p.cum_blocks <= INT32_MAX); // grids
+    INVARIANT(p.passes == key_bytes);
+    // packed exactly when that at least halves the upload; the device copy holds every column a kernel reads
+    INVARIANT(p.pack == (2 * limit <= k) && p.dev_k == (p.pack ? limit : k) && p.dev_k >= limit && p.dev_k <= INT32_MAX);
+    const size_t n = (size_t)p.n, cells = (size_t)rows * (size_t)p.dev_k;
+    INVARIANT(p.scores_bytes == cells * (size_t)key_bytes && p.correct_bytes == (has_correct ? cells : 0));
+    INVARIANT(p.keys_bytes == n * (size_t)key_bytes && p.pay_bytes == n * 4 && p.table_bytes == (size_t)p.table_entries * 4);
+    INVARIANT(p.partial_bytes == (size_t)std::max(p.table_blocks, p.cum_blocks) * 4 && p.hist_bytes == (size_t)key_bytes * 1024);
+    INVARIANT(p.cum_bytes == (want_cum ? n * 4 : 0) && p.wide_bytes == (want_wide ? n * 8 : 0));
+    INVARIANT(p.resident_bytes == p.scores_bytes + p.correct_bytes + 2 * p.keys_bytes + 2 * p.pay_bytes + p.table_bytes + p.partial_bytes + p.hist_bytes +
+                                      p.cum_bytes + p.wide_bytes);
+}
+
+static int run_rank()
+{
+    long long rows, k, limit;
+    int key_bytes, has_correct, want_cum, want_wide;
+    while (scanf("%lld %lld %lld %d %d %d %d", &rows, &k, &limit, &key_bytes, &has_correct, &want_cum, &want_wide) == 7) {
+        RankPlan p;
+        if (!plan_rank(rows, k, limit, key_bytes, has_correct != 0, want_cum != 0, want_wide != 0, &p)) {
+            printf("refused\n");
+            continue;
+        }
+        printf("%lld %lld %lld %lld %lld %d %d %lld %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", (long long)p.n, (long long)p.ntiles, (long long)p.table_entries,
+               (long long)p.table_blocks, (long long)p.cum_blocks, p.passes, (int)p.pack, (long long)p.dev_k, p.scores_bytes, p.correct_bytes, p.keys_bytes,
+               p.pay_bytes, p.table_bytes, p.partial_bytes, p.hist_bytes, p.cum_bytes, p.wide_bytes, p.resident_bytes);
+    }
+    return 0;
+}
+
 // `plan_check s16`: lines "nb nq k flags" -> the prefilter's eligibility and k' for the fp16 and the 12-bit row copies
 static int run_s16()
 {
@@ -307,6 +361,20 @@ static int run_sweep()
                             for (int can_stream = 0; can_stream < 2; can_stream++) check_sym(make_ctx(nb, nb, metric, flags, 0, 0, 0, false), k, can_stream != 0);
                     check_range(make_ctx(nb, nq, metric, 0, 0, 0, 0, false), nq);
                 }
+    // the device-wide rank: sizes around every internal width, the largest legal one, and illegal ones
+    const int64_t rank_rows[] = {0, 1, 2, 7, RANK_SCAN_BLOCK - 1, RANK_SCAN_BLOCK, RANK_SCAN_BLOCK + 1, RANK_TILE - 1, RANK_TILE, RANK_TILE + 1, 3 * RANK_TILE + 5,
+                                 (int64_t)RANK_SCAN_TOP * RANK_SCAN_BLOCK + 1, (int64_t)(RANK_SCAN_TOP * (RANK_SCAN_BLOCK / 256) + 1) * RANK_TILE + 5, 200000,
+                                 7158278, 2147483647, 2147483648LL, INT64_MAX};
+    const int64_t rank_limits[] = {0, 1, 2, 10, 300, 301, 2147483647, INT64_MAX};
+    for (int64_t rows : rank_rows)
+        for (int64_t limit : rank_limits) {
+            // k around the limit and around the packing rule's 2 * limit, and at the edge of what a kernel's int holds
+            std::vector<int64_t> ks = {limit};
+            if (limit <= (int64_t)INT32_MAX) ks = {limit - 1, limit, limit + 1, 2 * limit - 1, 2 * limit, (int64_t)INT32_MAX, (int64_t)INT32_MAX + 1};
+            for (int64_t k : ks)
+                for (int key_bytes : {2, 4, 8})
+                    for (int outs = 0; outs < 8; outs++) check_rank(rows, k, limit, key_bytes, outs);
+        }
     printf("plan_check sweep: %lld plans checked, %lld broken\n", g_checked, g_broken);
     return g_broken ? 1 : 0;
 }
@@ -317,7 +385,8 @@ int main(int argc, char **argv)
     if (argc == 2 && !strcmp(argv[1], "sym")) return run_sym();
     if (argc == 2 && !strcmp(argv[1], "range")) return run_range();
     if (argc == 2 && !strcmp(argv[1], "s16")) return run_s16();
+    if (argc == 2 && !strcmp(argv[1], "rank")) return run_rank();
     if (argc == 2 && !strcmp(argv[1], "sweep")) return run_sweep();
-    fprintf(stderr, "usage: plan_check cases|sym|range|s16 < lines | plan_check sweep\n");
+    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank < lines | plan_check sweep\n");
     return 2;
 }

@@ -15,6 +15,9 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   evaluate_slices         pfam/slices/slices.py:101-142 (evaluate: slice-level is_correct, is_ignore and AUC1)
   compute_correctness_array  pfam/proteins.py:201-207 (per-hit "is this a homologue" matrix)
   precision_recall_curve     pfam/proteins.py:626-648 (mean precision / recall per query over score thresholds)
+  ranked_precision_recall    pfam/pfam.py:570-583 (the dataset-wide precision-recall curve over every hit, ranked at once)
+  ranked_cumulative          cath/cath.py:656-675, 738-771; pfam/pfam.py:166-177, 213-236 (is_correct[argsort(key)].cumsum())
+  score_quantiles            pfam/proteins.py:626-648 (numpy.quantile over every score: precision_recall_curve's thresholds)
   combine_hits               pfam/proteins.py:216-240 ("combined": MMseqs2 hits with E < 0.1, filled up with k-NN hits)
   merge_hits                 pfam/proteins.py:340-372 ("both aligned": two lists sorted together, repeated ids dropped)
 """
@@ -548,6 +551,183 @@ def precision_recall_curve(correct: ndarray, scores: ndarray, correct_totals: nd
     if want_counts:
         return back(recall), back(precision), thresholds, tuple(back(c) for c in counts)
     return back(recall), back(precision), thresholds
+
+
+# ---- one stable order over every hit: knn_eval_rank (include/knn355.h) ------------------------------------------------
+RANK_MAX_ELEMENTS = 2 ** 31 - 1
+
+
+def _rank_arrays(scores, correct, limit, flat_ok, who):
+    """-> (scores float32 / float64 [rows, k], correct uint8 [rows, k] or None, limit); 1-D input becomes one column"""
+    scores = np.asarray(scores)
+    if flat_ok and scores.ndim == 1:
+        scores = scores.reshape(-1, 1)
+    if scores.ndim != 2:
+        raise ValueError(f"{who}: scores must be {'1-D or ' if flat_ok else ''}2-D, not {scores.ndim}-D")
+    rows, k = scores.shape
+    if rows < 1 or k < 1:
+        raise ValueError(f"{who}: scores must hold one value at least, not shape {scores.shape}")
+    if correct is not None:
+        correct = np.asarray(correct)
+        if flat_ok and correct.ndim == 1:
+            correct = correct.reshape(-1, 1)
+        if correct.shape != scores.shape:
+            raise ValueError(f"{who}: correct {correct.shape} and scores {scores.shape} must have the same shape")
+    limit = k if limit is None else int(limit)
+    if limit < 1 or limit > k:
+        raise ValueError(f"{who}: limit must be in [1, k = {k}], not {limit}")
+    if rows * limit > RANK_MAX_ELEMENTS:
+        raise ValueError(f"{who}: {rows} x {limit} values are more than 2^31 - 1")
+    scores = np.ascontiguousarray(scores, np.float32 if scores.dtype == np.float32 else np.float64)
+    if correct is not None:
+        correct = np.ascontiguousarray(correct != 0 if correct.dtype != np.bool_ else correct).view(np.uint8)
+    return scores, correct, limit
+
+
+def _rank(scores, correct, limit, descending=False, want_order=False, want_cum=False, targets=None, ranks=None):
+    """knn_eval_rank on checked arrays -> (order, cum, idx, cum_at, sorted_at), None for what was not asked for"""
+    rows, k = scores.shape
+    n = rows * limit
+    order = np.empty(n, np.int64) if want_order else None
+    cum = np.empty(n, np.int64) if want_cum else None
+    idx = cum_at = sorted_at = None
+    nt = nr = 0
+    if targets is not None and len(targets):
+        targets = np.ascontiguousarray(targets, np.int64)
+        nt = targets.size
+        idx, cum_at = np.empty(nt, np.int64), np.empty(nt, np.int64)
+    if ranks is not None and len(ranks):
+        ranks = np.ascontiguousarray(ranks, np.int64)
+        nr = ranks.size
+        sorted_at = np.empty(nr, scores.dtype)
+
+    def ptr(a):
+        return a.ctypes.data if a is not None else None
+
+    _lib.check(_lib.lib().knn_eval_rank(scores.ctypes.data, 1 if scores.dtype == np.float64 else 0, rows, k, limit, ptr(correct),
+                                        1 if descending else 0, ptr(order), ptr(cum), ptr(targets) if nt else None, nt, ptr(idx),
+                                        ptr(cum_at), ptr(ranks) if nr else None, nr, ptr(sorted_at)))
+    return order, cum, idx, cum_at, sorted_at
+
+
+def last_rank_info():
+    """How this thread's last ranked_precision_recall / ranked_cumulative / score_quantiles ran on the device: passes run
+    and skipped, tiles, and milliseconds: the device allocations and the host's packing of the first `limit` columns (host
+    clock), then upload, sort, scan and look-ups (HIP events)."""
+    from ctypes import byref, c_float, c_int32, c_int64
+    run, skipped, tiles, ms = c_int32(), c_int32(), c_int64(), (c_float * 6)()
+    _lib.check(_lib.lib().knn_last_rank_info(byref(run), byref(skipped), byref(tiles), ms))
+    return {"passes_run": run.value, "passes_skipped": skipped.value, "tiles": tiles.value, "alloc_ms": ms[0], "pack_ms": ms[1],
+            "upload_ms": ms[2], "sort_ms": ms[3], "scan_ms": ms[4], "lookup_ms": ms[5]}
+
+
+def _recall_targets(levels: ndarray, total: int) -> ndarray:
+    """int64 per level t: the smallest integer c >= 0 with c / total >= t, tested with the float64 division the
+    reference's recall array is made of -- so `first r with C(r) >= c` is numpy.searchsorted(C / total, t)."""
+    c = np.maximum(np.ceil(levels * total), 0).astype(np.int64)
+    while True:
+        down = (c > 0) & ((c - 1) / total >= levels)
+        if not down.any():
+            break
+        c[down] -= 1
+    while True:
+        up = c / total < levels
+        if not up.any():
+            break
+        c[up] += 1
+    return c
+
+
+def ranked_precision_recall(correct: ndarray, scores: ndarray, total_to_be_found: int, limit: int = None, points: int = 10000,
+                            descending: bool = False) -> Tuple[ndarray, ndarray]:
+    """The dataset-wide precision-recall curve of pfam/pfam.py:570-583 -> (recall, precision), float64 [points].
+
+    Every hit of scores[:, :limit] (float32 or float64 [nq, k]; limit=None: all k columns) is ranked at once, ascending
+    (e-values; descending=True for similarities, the order of numpy.argsort(-scores, kind="stable")); C(r) is the number
+    of correct hits (correct bool / uint8 [nq, k]) among the ranks 0 .. r; recall(r) = C(r) / total_to_be_found and
+    precision(r) = C(r) / (r + 1).  The curve is read at the first rank whose recall reaches each of
+    numpy.linspace(0, 1, points), clipped to the last rank, as the reference's searchsorted and clip do.
+    The sort and the running count run on the device (knn_eval_rank); the host turns each level into the integer count
+    it asks for and divides, with the reference's own int64 / float64 divisions: the results are its bits.
+    Equal scores rank in flat order (row, then column), and NaN ranks last: the reference leaves the order of equal scores
+    to numpy's default, unstable, sort; here it is the stable one."""
+    scores, correct, limit = _rank_arrays(scores, correct, limit, False, "ranked_precision_recall")
+    if correct is None:
+        raise ValueError("ranked_precision_recall: correct is required")
+    total = int(total_to_be_found)
+    if total < 1:
+        raise ValueError("ranked_precision_recall: total_to_be_found must be positive: recall divides by it")
+    points = int(points)
+    if points < 1:
+        raise ValueError("ranked_precision_recall: points must be positive")
+    n = scores.shape[0] * limit
+    targets = _recall_targets(np.linspace(0, 1, points), total)
+    _, _, idx, cum_at, _ = _rank(scores, correct, limit, descending, targets=targets)
+    idx = np.minimum(idx, n - 1)  # (cum_at is C at the clipped rank already)
+    return cum_at / total, cum_at / (idx + 1)
+
+
+def ranked_cumulative(correct: ndarray, keys: ndarray, descending: bool = False, want_order: bool = False):
+    """is_correct[numpy.argsort(key, kind="stable")].cumsum() for 1-D or 2-D input (2-D is flattened row by row), the
+    cumulative curves of cath/cath.py:656-675, 738-771 and pfam/pfam.py:166-177, 213-236 -> int64 [N], and the order
+    itself (int64 [N], flat positions) behind it when want_order.  descending=True ranks by -key; NaN ranks last either
+    way, -0.0 equals +0.0, equal keys keep their flat order."""
+    keys, correct, limit = _rank_arrays(keys, correct, None, True, "ranked_cumulative")
+    if correct is None:
+        raise ValueError("ranked_cumulative: correct is required")
+    order, cum, _, _, _ = _rank(keys, correct, limit, descending, want_order=want_order, want_cum=True)
+    return (cum, order) if want_order else cum
+
+
+def _quantile_positions(n: int, q: ndarray):
+    """numpy 2.2.6's `linear` method (numpy/lib/_function_base_impl.py: _quantile, _get_indexes, _get_gamma): the two
+    ranks around each q and the weight between them.  The position is (n - 1) * q; at or past the last rank both ranks
+    are -1, the last one, and the weight is still position - (-1)."""
+    virtual = (n - 1) * q
+    previous = np.floor(virtual)
+    following = previous + 1
+    above = virtual >= n - 1
+    previous[above] = -1
+    following[above] = -1
+    previous, following = previous.astype(np.intp), following.astype(np.intp)
+    return previous, following, virtual - previous
+
+
+def _quantile_lerp(a: ndarray, b: ndarray, t: ndarray, last) -> ndarray:
+    """numpy 2.2.6's _lerp on the order statistics a, b (in the scores' type) with float64 weights t: the difference is
+    taken in the scores' type, a + diff * t in float64 below t = 0.5 and b - diff * (1 - t) from there on; a NaN as the
+    last order statistic makes every quantile NaN."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        diff = np.subtract(b, a)
+        out = np.asarray(np.add(a, diff * t), np.float64)
+        high = t >= 0.5
+        out[high] = np.subtract(b, diff * (1 - t), dtype=np.float64)[high]
+    if np.isnan(last):
+        out[:] = last
+    return out
+
+
+def score_quantiles(scores: ndarray, q: ndarray, limit: int = None) -> ndarray:
+    """numpy.quantile(scores[:, :limit], q), the default `linear` method, for float32 or float64 scores (2-D, or 1-D) and
+    q in [0, 1] -> float64 [len(q)].  precision_recall_curve's default thresholds are
+    score_quantiles(scores, numpy.linspace(0, 1, smoothness + 1), limit).
+
+    The device ranks every score (knn_eval_rank) and returns the two order statistics around each q; the host
+    interpolates between them as numpy does.  Bit for bit numpy 2.2.6's result, whose arithmetic this restates
+    (_quantile_positions, _quantile_lerp); another numpy may round the position or the interpolation differently."""
+    scores, _, limit = _rank_arrays(scores, None, limit, True, "score_quantiles")
+    q = np.array(q, dtype=np.float64)
+    if q.ndim != 1:
+        raise ValueError("score_quantiles: q must be 1-D")
+    if q.size and not (np.all(q >= 0) and np.all(q <= 1)):
+        raise ValueError("score_quantiles: q must be in [0, 1]")
+    if not q.size:
+        return np.empty(0, np.float64)
+    n = scores.shape[0] * limit
+    previous, following, gamma = _quantile_positions(n, q)
+    ranks = np.concatenate([previous, following, [-1]]) % n
+    _, _, _, _, at = _rank(scores, None, limit, ranks=ranks)
+    return _quantile_lerp(at[:q.size], at[q.size:2 * q.size], gamma, at[-1])
 
 
 KNN_FUSE_PREFIX_FILL, KNN_FUSE_SORTED_UNION = 0, 1  # include/knn355.h
