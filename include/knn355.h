@@ -625,6 +625,48 @@ int knn_pca_project(const float *x, int64_t n, int32_t d, const float *mean, con
  * projection kernel summed over the slabs */
 int knn_pca_last_ms(float *moments_ms, float *project_ms);
 
+/* ---- mean pooling over row ranges: per-protein and per-domain embeddings ------------------
+ * The step that produces the matrix an index stores: pfam/embed_pfam_seqvec.py:29-40 (embedding[start - 1 : stop]
+ * .mean(axis=0) per Pfam domain), pfam/embed_t5_l2.py:68-71 (normalize_L2 on every residue row, then the mean over
+ * residues), reduce_per_protein in pfam/embed_pfam_t5.py:40-43, pfam/embed_t5_fp16.py:45-47 and cath/embed.py:92-94.
+ * x is the residue matrix [rows][d], float32 (dtype 0) or float16 (dtype 1), and is never written; range o is the rows
+ * starts[o] .. stops[o] - 1 (0-based, stop exclusive); ranges may overlap, repeat and come in any order; out is float32
+ * [n][d].  The contract, per output o and column c, with L = stops[o] - starts[o]:
+ *     acc = v(starts[o], c)                       (the first row's value, not 0 + it: -0.0 survives)
+ *     acc = acc + v(r, c)  for r = starts[o] + 1 .. stops[o] - 1 in ascending order: one fp32 add each, no fma, no
+ *                          wider accumulator, no reordering
+ *     out[o][c] = acc / (float)L                  (one correctly rounded fp32 division)
+ * which is numpy's x[start:stop].mean(axis=0) on a C-contiguous float32 array with d >= 2 (tests/test_pool_reference.py
+ * checks that claim against numpy itself).  Plain (flags 0): v(r, c) = x[r][c]; float16 converts to float32 exactly.
+ * KNN_POOL_NORMALIZE: v(r, c) = x[r][c] * s_r rounded to fp32, s_r being knn_normalize_l2's factor of row r (the fma chain
+ * in the order 0,4,1,5,2,6,3,7, s = (float)(1.0 / sqrtf(nrm)); a row whose nrm is not > 0 is used as it is; an infinite nrm
+ * gives the factor 0): the result is knn_normalize_l2 followed by the plain pooling, bit for bit.  fp32 subnormals are kept.
+ * KNN_ERR_INVALID, with a message, before anything is allocated or launched and with out untouched: dtype other than 0 or
+ * 1; flags other than 0 or KNN_POOL_NORMALIZE; d outside [2, KNN_POOL_MAX_D]; rows < 0 or n < 0 or n > 2^31 - 1; a null
+ * pointer when n > 0; row_stride < d; (host entry) a range without 0 <= start < stop <= rows or with stop - start >= 2^24.
+ * n = 0 returns 0 and launches nothing.
+ * knn_pool_ranges: host pointers.  x goes up in chunks (64 MiB; KNN355_POOL_CHUNK_ROWS, a positive decimal integer, sets
+ * the rows per chunk) on the copy pipeline's host-to-device stream while the previous chunk is pooled; a range belongs to
+ * the chunk that holds it and a range longer than a chunk is a chunk of its own, so a call never holds all of x on the
+ * device.  Rows shared by ranges of different chunks go up once per chunk.
+ * knn_pool_ranges_dev: device pointers on the current device, work enqueued on `stream` (NULL: the null stream).
+ * row_stride is the distance between rows of x in elements; out is contiguous.  The ranges are checked on the device
+ * (pool_check_kernel: the same rules) into a status word that the call reads behind its last launch, waiting for an event
+ * it records there: a bad range is KNN_ERR_INVALID naming the lowest bad index; its output row is left untouched, no
+ * row of x is read for it, and every other output row is written as usual.
+ * Hot path (pool.inc): pool_ranges_kernel, one wave per (range, 256 columns), rows walked in order with the loads of eight
+ * rows in flight; a range is never split by rows, so few long ranges are latency-bound. */
+#define KNN_POOL_NORMALIZE 1
+#define KNN_POOL_MAX_D (1 << 20)
+int knn_pool_ranges(const void *x_host, int32_t dtype, int64_t rows, int32_t d, const int64_t *starts_host,
+                    const int64_t *stops_host, int64_t n, int32_t flags, float *out_host /* [n * d] */);
+int knn_pool_ranges_dev(const void *x_dev, int32_t dtype, int64_t rows, int32_t d, int64_t row_stride,
+                        const int64_t *starts_dev, const int64_t *stops_dev, int64_t n, int32_t flags, float *out_dev,
+                        void *stream);
+/* measurement (tools/bench_pool.py): HIP-event milliseconds of the calling thread's last successful knn_pool_ranges
+ * (uploads, kernels and the download, each summed over the chunks) or knn_pool_ranges_dev (kernels; the other two are 0) */
+int knn_pool_last_ms(float *upload_ms, float *kernel_ms, float *download_ms);
+
 /* ---- MMseqs2 prefilter database: SURVEY section 8(f) N3 ----------------------------
  * seqvec_search/mmseqs/_write_prefilter_db.py:52-97 write_prefilter_db: data file
  * ("<prefilter>.0") and index file ("<prefilter>.index"); queries[i] is the faiss row of

@@ -57,6 +57,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(1))) f32x4 *gptr4; // explicit global (not flat) loads
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 #define KEY_PAD 0xFFFFFFFFFFFFFFFFull
 #define KEY_WORD_INF 0xFF800000u // f2ord(+inf): the first score word that is no score (select_topk_kernel's load)
@@ -89,17 +90,22 @@ __device__ __forceinline__ float ord2f(uint32_t o)
 }
 
 // nrm(x) = dot(x, x) in the contract's chain order: one lane walks one row.
-template <bool ALIGNED>
-__device__ __forceinline__ float lane_norm_row(const float *__restrict__ r, int d)
+// T: float, or _Float16 rows converted to float (exactly) as they are read (pool.inc).
+template <bool ALIGNED, typename T = float>
+__device__ __forceinline__ float lane_norm_row(const T *__restrict__ r, int d)
 {
     float acc = 0.0f;
     int k0 = 0;
     for (; k0 + 8 <= d; k0 += 8) {
         float a[8];
-        if constexpr (ALIGNED) {
+        if constexpr (ALIGNED && sizeof(T) == 4) {
             f32x4 lo = *(const f32x4 *)(r + k0), hi = *(const f32x4 *)(r + k0 + 4);
 #pragma unroll
             for (int m = 0; m < 4; m++) { a[m] = lo[m]; a[4 + m] = hi[m]; }
+        } else if constexpr (ALIGNED) {
+            f16x4 lo = *(const f16x4 *)(r + k0), hi = *(const f16x4 *)(r + k0 + 4);
+#pragma unroll
+            for (int m = 0; m < 4; m++) { a[m] = (float)lo[m]; a[4 + m] = (float)hi[m]; }
         } else {
 #pragma unroll
             for (int m = 0; m < 8; m++) a[m] = r[k0 + m];
@@ -5594,3 +5600,4 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "pca.inc"
 #include "fuse.inc"
 #include "range.inc"
+#include "pool.inc"

@@ -754,6 +754,73 @@ static bool plan_rank(int64_t rows, int64_t k, int64_t limit, int key_bytes, boo
     return true;
 }
 
+// ---- mean pooling over row ranges (pool.inc) ---------------------------------------
+static const int POOL_COLS = 256;      // columns of one wave: 64 lanes x 4
+static const int POOL_GROUP = 8;       // rows whose loads are issued in front of the first add of the group
+static const int POOL_NORM_ROWS = 64;  // rows per batch of norms of the normalizing build
+static const int POOL_MAX_WAVES = 16;  // waves of a workgroup, at most (normalizing build; the plain one takes 4)
+static const int64_t POOL_MAX_LEN = (int64_t)1 << 24; // a range is shorter than this: (float)L is exact
+
+struct PoolPlan {
+    int ncb;        // column blocks of POOL_COLS columns: ceil(d / 256)
+    int waves;      // waves of a workgroup = neighbouring column blocks of one range
+    int64_t grid_x; // ranges
+    int grid_y;     // workgroups per range: ceil(ncb / waves)
+    bool aligned;   // a lane reads its four columns as one 16-byte (fp16: 8-byte) load; false: element by element
+};
+
+// false: not a legal launch (n outside [1, 2^31 - 1], d outside [2, KNN_POOL_MAX_D], a row stride below d, an element size
+// other than 2 or 4 bytes).  The plain build puts up to 4 neighbouring column blocks of a range into one workgroup.  The
+// normalizing build shares a batch's 64 norms between the waves of a workgroup, so it takes every column block of the range
+// it can: the smallest power of two (it divides 64) that covers ncb, 16 at most; waves past the last column block compute
+// norms and add nothing.  Aligned: the base is a multiple of four elements and so is the row stride.
+static bool plan_pool(int64_t n, int64_t d, int64_t row_stride, uintptr_t base, int elem_bytes, bool normalize, PoolPlan *out)
+{
+    if (n < 1 || n > (int64_t)INT32_MAX || d < 2 || d > KNN_POOL_MAX_D || row_stride < d || (elem_bytes != 2 && elem_bytes != 4)) return false;
+    PoolPlan pl;
+    pl.ncb = (int)((d + POOL_COLS - 1) / POOL_COLS);
+    if (normalize) {
+        pl.waves = 1;
+        while (pl.waves < pl.ncb && pl.waves < POOL_MAX_WAVES) pl.waves *= 2;
+    } else {
+        pl.waves = std::min(pl.ncb, 4);
+    }
+    pl.grid_x = n;
+    pl.grid_y = (pl.ncb + pl.waves - 1) / pl.waves;
+    pl.aligned = base % (uintptr_t)(4 * elem_bytes) == 0 && row_stride % 4 == 0;
+    *out = pl;
+    return true;
+}
+
+// The host entry's cut of the residue matrix into uploads.  order: the ranges by ascending (start, stop, index); a chunk is
+// a run of `order` (first, count) and the rows [row0, row1) that hold every range of the run.  A chunk spans at most
+// chunk_rows rows, but for a single range longer than that, which is a chunk of its own.  Ranges are valid (0 <= start <
+// stop) and chunk_rows >= 1.  Overlapping ranges that fall into different chunks have their shared rows uploaded twice.
+struct PoolChunk {
+    int64_t row0, row1, first, count;
+};
+static void pool_assign_chunks(const int64_t *starts, const int64_t *stops, int64_t n, int64_t chunk_rows, std::vector<int64_t> &order,
+                               std::vector<PoolChunk> &chunks)
+{
+    order.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        if (starts[a] != starts[b]) return starts[a] < starts[b];
+        if (stops[a] != stops[b]) return stops[a] < stops[b];
+        return a < b;
+    });
+    chunks.clear();
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t o = order[(size_t)i];
+        if (!chunks.empty() && stops[o] - chunks.back().row0 <= chunk_rows) {
+            chunks.back().row1 = std::max(chunks.back().row1, stops[o]);
+            chunks.back().count++;
+        } else {
+            chunks.push_back({starts[o], stops[o], i, 1});
+        }
+    }
+}
+
 // Which flat_scan_kernel build serves a launch is pick_scan_kernel's choice (knn355.hip) from (query tile, metric, bf16 rows,
 // one query tile, width of the difference build or 0, pass of a prefiltered search); this is its legality rule: nullptr, or
 // why no build serves the combination (the width of a difference build does not enter: every width has its build).

@@ -9,6 +9,11 @@
 //   plan_check rank    reads lines "rows k limit key_bytes has_correct want_cum want_wide": the size plan of the device-wide rank -- n
 //                      ntiles table_entries table_blocks cum_blocks passes pack dev_k and the bytes of the scores, correct, one key buffer,
 //                      one payload buffer, table, block sums, histograms, running count, int64 staging and all of them, or "refused"
+//   plan_check pool    reads lines "n d row_stride base elem_bytes normalize": the pooling launch -- ncb waves grid_x grid_y aligned,
+//                      or "refused"
+//   plan_check poolchunks  reads "n chunk_rows" and n lines "start stop": the host pooling entry's uploads, one line per chunk --
+//                      "row0 row1 count: the indices of its ranges" (the host code of knn_pool_ranges that is separable from its
+//                      launches, under the sanitizers here)
 //   plan_check sweep   walks a grid of shapes and flags and exits non-zero on a broken invariant
 // The device has 256 CUs throughout, but for a `range` line that names another count.  Built with the host compiler and -fsanitize=address,undefined (make plan_check).
 #include "plan.h"
@@ -315,6 +320,147 @@ static int run_rank()
     return 0;
 }
 
+// ---- mean pooling (pool.inc) ----
+// `plan_check pool`: lines "n d row_stride base elem_bytes normalize" -> ncb waves grid_x grid_y aligned, or "refused"
+static int run_pool()
+{
+    long long n, d, stride;
+    unsigned long long base;
+    int elem, normalize;
+    while (scanf("%lld %lld %lld %llu %d %d", &n, &d, &stride, &base, &elem, &normalize) == 6) {
+        PoolPlan p;
+        if (!plan_pool(n, d, stride, (uintptr_t)base, elem, normalize != 0, &p)) {
+            printf("refused\n");
+            continue;
+        }
+        printf("%d %d %lld %d %d\n", p.ncb, p.waves, (long long)p.grid_x, p.grid_y, (int)p.aligned);
+    }
+    return 0;
+}
+
+// `plan_check poolchunks`: the line "n chunk_rows", then n lines "start stop" -> per chunk "row0 row1 count: the ranges' indices"
+static int run_poolchunks()
+{
+    long long n, chunk_rows;
+    if (scanf("%lld %lld", &n, &chunk_rows) != 2 || n < 0 || chunk_rows < 1) return 2;
+    std::vector<int64_t> starts((size_t)n), stops((size_t)n), order;
+    for (long long i = 0; i < n; i++) {
+        long long a, b;
+        if (scanf("%lld %lld", &a, &b) != 2) return 2;
+        starts[(size_t)i] = a;
+        stops[(size_t)i] = b;
+    }
+    std::vector<PoolChunk> chunks;
+    pool_assign_chunks(starts.data(), stops.data(), n, chunk_rows, order, chunks);
+    for (const PoolChunk &c : chunks) {
+        printf("%lld %lld %lld:", (long long)c.row0, (long long)c.row1, (long long)c.count);
+        for (int64_t i = 0; i < c.count; i++) printf(" %lld", (long long)order[(size_t)(c.first + i)]);
+        printf("\n");
+    }
+    return 0;
+}
+
+// every (range, column) pair of a launch is owned by exactly one (workgroup, wave, lane, element); the waves divide 64 in the
+// normalizing build; the grid fits; aligned is the pointer's and the stride's doing
+static void check_pool(int64_t n, int64_t d, int64_t stride, uintptr_t base, int elem, bool normalize)
+{
+    PoolPlan p;
+    const auto where = [&] {
+        return describe("pool n %lld d %lld stride %lld base %llx elem %d normalize %d", (long long)n, (long long)d, (long long)stride, (unsigned long long)base, elem,
+                        (int)normalize);
+    };
+    g_checked++;
+    const bool legal = n >= 1 && n <= INT32_MAX && d >= 2 && d <= KNN_POOL_MAX_D && stride >= d && (elem == 2 || elem == 4);
+    if (!plan_pool(n, d, stride, base, elem, normalize, &p)) {
+        INVARIANT(!legal);
+        return;
+    }
+    INVARIANT(legal);
+    INVARIANT(p.grid_x == n && p.grid_y >= 1 && p.grid_y <= 65535 && p.waves >= 1 && p.waves <= POOL_MAX_WAVES);
+    INVARIANT(p.ncb == (d + POOL_COLS - 1) / POOL_COLS && p.grid_y == (p.ncb + p.waves - 1) / p.waves);
+    INVARIANT(!normalize || POOL_NORM_ROWS % p.waves == 0);
+    INVARIANT(normalize || p.waves <= 4);
+    INVARIANT((int64_t)(p.grid_y - 1) * p.waves < p.ncb); // (no workgroup without a column block)
+    INVARIANT(p.aligned == (base % (uintptr_t)(4 * elem) == 0 && stride % 4 == 0));
+    // the kernel's own arithmetic: c0 = (y * waves + wave) * 256 + 4 * lane, nvalid = min(4, d - c0)
+    if (d > 8192 && (n != 1 || base != 0x1000)) return; // (the widest rows once per build, not per pointer and count)
+    std::vector<uint8_t> owners((size_t)d, 0);
+    for (int y = 0; y < p.grid_y; y++)
+        for (int w = 0; w < p.waves; w++)
+            for (int lane = 0; lane < 64; lane++) {
+                const int64_t c0 = ((int64_t)y * p.waves + w) * POOL_COLS + 4 * lane;
+                for (int64_t e = 0; e < std::min<int64_t>(4, d - c0); e++) owners[(size_t)(c0 + e)]++;
+            }
+    bool once = true;
+    for (uint8_t v : owners) once = once && v == 1;
+    INVARIANT(once);
+}
+
+// every range in exactly one chunk and inside its rows; chunks within the budget, but for a chunk that begins with a longer range
+static void check_pool_chunks(const std::vector<int64_t> &starts, const std::vector<int64_t> &stops, int64_t chunk_rows)
+{
+    std::vector<int64_t> order;
+    std::vector<PoolChunk> chunks;
+    const int64_t n = (int64_t)starts.size();
+    const auto where = [&] { return describe("pool chunks: %lld ranges, first %lld-%lld, chunk_rows %lld", (long long)n, (long long)starts[0], (long long)stops[0], (long long)chunk_rows); };
+    g_checked++;
+    pool_assign_chunks(starts.data(), stops.data(), n, chunk_rows, order, chunks);
+    std::vector<int> seen((size_t)n, 0);
+    int64_t next = 0;
+    bool ok = (int64_t)order.size() == n;
+    for (const PoolChunk &c : chunks) {
+        ok = ok && c.first == next && c.count >= 1 && c.first + c.count <= n;
+        if (!ok) break;
+        next += c.count;
+        int64_t hi = 0;
+        for (int64_t i = 0; i < c.count; i++) {
+            const int64_t o = order[(size_t)(c.first + i)];
+            ok = ok && o >= 0 && o < n && starts[(size_t)o] >= c.row0 && stops[(size_t)o] <= c.row1;
+            if (!ok) break;
+            seen[(size_t)o]++;
+            hi = std::max(hi, stops[(size_t)o]);
+        }
+        const int64_t o0 = order[(size_t)c.first];
+        ok = ok && hi == c.row1 && starts[(size_t)o0] == c.row0;
+        ok = ok && (c.row1 - c.row0 <= chunk_rows || (stops[(size_t)o0] - starts[(size_t)o0] > chunk_rows && stops[(size_t)o0] == c.row1));
+    }
+    ok = ok && next == n;
+    for (int v : seen) ok = ok && v == 1;
+    INVARIANT(ok);
+}
+
+static void sweep_pool()
+{
+    const int64_t ds[] = {-1, 0, 1, 2, 3, 4, 8, 20, 255, 256, 257, 1023, 1024, 1025, 1028, 3072, 4095, 4097, 5000, KNN_POOL_MAX_D, KNN_POOL_MAX_D + 1};
+    for (int64_t d : ds)
+        for (int64_t n : {(int64_t)0, (int64_t)1, (int64_t)7, (int64_t)INT32_MAX, (int64_t)INT32_MAX + 1})
+            for (int64_t extra : {(int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)2, (int64_t)4})
+                for (uintptr_t base : {(uintptr_t)0x1000, (uintptr_t)0x1002, (uintptr_t)0x1004, (uintptr_t)0x1008, (uintptr_t)0x1010})
+                    for (int elem : {1, 2, 4, 8})
+                        for (int normalize = 0; normalize < 2; normalize++) check_pool(n, d, d + extra, base, elem, normalize != 0);
+    // chunk assignment: seeded ranges (overlapping, unordered, duplicates, all rows) against every budget around their lengths
+    uint64_t state = 12345;
+    auto rnd = [&](int64_t m) {
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        return (int64_t)((state >> 33) % (uint64_t)m);
+    };
+    for (int round = 0; round < 40; round++) {
+        const int64_t rows = 1 + rnd(400), n = 1 + rnd(40);
+        std::vector<int64_t> starts, stops;
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t a = rnd(rows);
+            starts.push_back(a);
+            stops.push_back(a + 1 + rnd(std::min<int64_t>(rows - a, 1 + rnd(120))));
+        }
+        starts.push_back(0);
+        stops.push_back(rows);
+        starts.push_back(starts[0]);
+        stops.push_back(stops[0]);
+        for (int64_t chunk_rows : {(int64_t)1, (int64_t)2, (int64_t)7, (int64_t)64, (int64_t)119, (int64_t)120, rows - 1, rows, rows + 1, (int64_t)1 << 40})
+            if (chunk_rows >= 1) check_pool_chunks(starts, stops, chunk_rows);
+    }
+}
+
 // `plan_check s16`: lines "nb nq k flags" -> the prefilter's eligibility and k' for the fp16 and the 12-bit row copies
 static int run_s16()
 {
@@ -375,6 +521,8 @@ static int run_sweep()
                 for (int key_bytes : {2, 4, 8})
                     for (int outs = 0; outs < 8; outs++) check_rank(rows, k, limit, key_bytes, outs);
         }
+    // the pooling launch of every (n, d, stride, base, element size, build) and the host entry's chunks
+    sweep_pool();
     printf("plan_check sweep: %lld plans checked, %lld broken\n", g_checked, g_broken);
     return g_broken ? 1 : 0;
 }
@@ -386,7 +534,9 @@ int main(int argc, char **argv)
     if (argc == 2 && !strcmp(argv[1], "range")) return run_range();
     if (argc == 2 && !strcmp(argv[1], "s16")) return run_s16();
     if (argc == 2 && !strcmp(argv[1], "rank")) return run_rank();
+    if (argc == 2 && !strcmp(argv[1], "pool")) return run_pool();
+    if (argc == 2 && !strcmp(argv[1], "poolchunks")) return run_poolchunks();
     if (argc == 2 && !strcmp(argv[1], "sweep")) return run_sweep();
-    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank < lines | plan_check sweep\n");
+    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank|pool|poolchunks < lines | plan_check sweep\n");
     return 2;
 }
