@@ -667,6 +667,55 @@ int knn_pool_ranges_dev(const void *x_dev, int32_t dtype, int64_t rows, int32_t 
  * (uploads, kernels and the download, each summed over the chunks) or knn_pool_ranges_dev (kernels; the other two are 0) */
 int knn_pool_last_ms(float *upload_ms, float *kernel_ms, float *download_ms);
 
+/* ---- one-dimensional Gaussian kernel density estimates -----------------------------------
+ * pfam/reverse_evaluate.py:63-70, 113-118, 139-142: DataFrame({...}).plot.density(), which pandas turns into
+ * scipy.stats.gaussian_kde(column).evaluate(grid) on a 1000-point grid per column.  Two stateless entries with host
+ * pointers: the statistics the bandwidth and the grid are made of, and the evaluation.  Between them the host computes
+ * the factor, h = sqrt(var) * factor, inv_h = 1 / h, norm = 1 / (n * h * sqrt(2 pi)) and the grid in float64 (density.py).
+ * x is float32 (dtype 0) or float64 (dtype 1) and is never written; column c of row r is x[r * row_stride + c], c < ncols,
+ * so a column view of a row-major matrix is (pointer to its first element, ncols 1, row_stride = the matrix's width).
+ * Every step below is one IEEE double multiply, add or subtract; nothing is fused.
+ *   widening    values are widened to float64 as they are loaded (float32 to float64 is exact)
+ *   groups      consecutive groups of L = 4096 * ceil(n / (4096 * 256)) rows, the PCA contract's
+ *   min, max    exact (of two zeros of different sign either may be returned)
+ *   mean        per column, a group's sum is the float64 sum of its rows in ascending order starting from the first
+ *               row's value; the group sums are added in ascending group order starting from the first group's; the
+ *               sum is divided by (double)n
+ *   var         a second pass over d = x - mean, d * d, summed in the same way and divided by (double)(n - 1)
+ *   term        z = (g - x_i) * inv_h;  t = (z * z) * -0.5;  term = kexp(t)
+ *   kexp(t)     for t <= 0.  t < -745.0 gives exactly 0.0.  Otherwise k = rint(t * LOG2E) (ties to even),
+ *               r = (t - k * LN2_HI) - k * LN2_LO, p = the degree-13 Horner polynomial in r with the coefficients
+ *               (double)(1 / i!), every step p = p * r + c_i as a multiply and an add, result ldexp(p, k): exact for
+ *               k >= -1021, one rounding (to nearest even) into the subnormal range below that.
+ *               LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42fee00000p-1 (low 21 bits zero: k * LN2_HI is exact),
+ *               LN2_LO = 0x1.a39ef35793c76p-33.  At most 1.2 ulp from exp (tests/test_kde_reference.py measures it).
+ *   sum         per (column, grid point): the rows are cut into chunks of 16 384 consecutive rows.  Inside a chunk there
+ *               are 256 partial sums, partial j adding the terms of the rows i with i % 256 == j in ascending i,
+ *               starting from +0.0; the 256 partials are combined by the binary tree of adjacent pairs (strides 1, 2,
+ *               4, ..., 128: p[j] += p[j + stride] for j a multiple of 2 * stride); the chunk sums are added in chunk
+ *               order starting from the first chunk's; out = sum * norm.  The chunk size and the 256 are constants of
+ *               this contract, not functions of the device.
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: dtype other than 0 or 1;
+ * n < 2 or n > KNN_KDE_MAX_ROWS; ncols outside [1, KNN_KDE_MAX_COLS]; row_stride < ncols; m outside
+ * [1, KNN_KDE_MAX_POINTS]; a null pointer; a NaN or an infinity in a used element of x or in the grid; an inv_h or a
+ * norm that is not positive and finite (which is what a zero variance or a bad factor gives).
+ * Both entries upload the rows as they lie on the host, from the first used element to the last ((n - 1) * row_stride +
+ * ncols elements: for a column view of a wide matrix that is the matrix), once per call, on the copy pipeline's
+ * host-to-device stream; knn_kde_eval holds ncols * ceil(n / 16384) * m * 8 bytes of chunk sums beside them.
+ * Hot path (kde.inc): kde_eval_kernel, one workgroup of 256 threads per (16 grid points, chunk, column), 16 float64
+ * accumulators per lane, float64 VALU only (no hardware transcendental, no atomics); kde_reduce_kernel. */
+#define KNN_KDE_MAX_COLS 4096
+#define KNN_KDE_MAX_ROWS (65535LL * 16384)
+#define KNN_KDE_MAX_POINTS (1 << 24)
+int knn_kde_stats(const void *x, int32_t dtype, int64_t n, int32_t ncols, int64_t row_stride, double *min /* [ncols] */,
+                  double *max, double *mean, double *var /* ddof = 1 */);
+int knn_kde_eval(const void *x, int32_t dtype, int64_t n, int32_t ncols, int64_t row_stride,
+                 const double *grid /* [ncols * m] */, int64_t m, const double *inv_h /* [ncols] */,
+                 const double *norm /* [ncols] */, double *out /* [ncols * m] */);
+/* measurement (tools/bench_kde.py): HIP-event milliseconds of the calling thread's last successful knn_kde_stats,
+ * stats_ms[2] = upload, kernels, and of its last knn_kde_eval, eval_ms[3] = uploads, evaluation kernel, reduce */
+int knn_kde_last_ms(float *stats_ms, float *eval_ms);
+
 /* ---- MMseqs2 prefilter database: SURVEY section 8(f) N3 ----------------------------
  * seqvec_search/mmseqs/_write_prefilter_db.py:52-97 write_prefilter_db: data file
  * ("<prefilter>.0") and index file ("<prefilter>.index"); queries[i] is the faiss row of

@@ -144,6 +144,9 @@ def _declare(L):
         "knn_pool_ranges": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
         "knn_pool_ranges_dev": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
         "knn_pool_last_ms": (c_int32, [f32p, f32p, f32p]),
+        "knn_kde_stats": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "knn_kde_eval": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+        "knn_kde_last_ms": (c_int32, [f32p, f32p]),
         "knn_eval_fuse": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
         "knn_write_prefilter_db": (c_int32, [c_char_p, c_char_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32]),

@@ -821,6 +821,39 @@ static void pool_assign_chunks(const int64_t *starts, const int64_t *stops, int6
     }
 }
 
+// ---- one-dimensional kernel density estimates (kde.inc) -----------------------------
+// Constants of the arithmetic contract above knn_kde_stats (include/knn355.h), not functions of the device.
+static const int KDE_CHUNK = 16384; // consecutive rows whose terms are summed by one workgroup
+static const int KDE_LANES = 256;   // partial sums of a chunk = threads of the workgroup
+static const int KDE_TILE = 16;     // grid points of one workgroup = accumulators of a lane
+
+struct KdePlan {
+    int64_t group_rows; // rows per group of the statistics: 4096 * ceil(n / (4096 * 256)), the rule of the PCA contract
+    int groups;         // ceil(n / group_rows), at most 256
+    int64_t tiles;      // ceil(m / KDE_TILE): grid.x of the evaluation
+    int64_t chunks;     // ceil(n / KDE_CHUNK): grid.y
+    int tail_rows;      // rows of the last chunk, 1 .. KDE_CHUNK
+    int tail_points;    // grid points of the last tile, 1 .. KDE_TILE
+    int64_t part_bytes; // part[ncols][chunks][m] float64
+};
+
+// false: not a legal launch (n < 2, ncols outside [1, KNN_KDE_MAX_COLS], m outside [1, KNN_KDE_MAX_POINTS], more than 65 535
+// chunks: n above KNN_KDE_MAX_ROWS)
+static bool plan_kde(int64_t n, int64_t ncols, int64_t m, KdePlan *out)
+{
+    if (n < 2 || n > KNN_KDE_MAX_ROWS || ncols < 1 || ncols > KNN_KDE_MAX_COLS || m < 1 || m > KNN_KDE_MAX_POINTS) return false;
+    KdePlan pl;
+    pl.group_rows = 4096 * ((n + 4096 * 256 - 1) / (4096 * 256));
+    pl.groups = (int)((n + pl.group_rows - 1) / pl.group_rows);
+    pl.tiles = (m + KDE_TILE - 1) / KDE_TILE;
+    pl.chunks = (n + KDE_CHUNK - 1) / KDE_CHUNK;
+    pl.tail_rows = (int)(n - (pl.chunks - 1) * KDE_CHUNK);
+    pl.tail_points = (int)(m - (pl.tiles - 1) * KDE_TILE);
+    pl.part_bytes = ncols * pl.chunks * m * 8;
+    *out = pl;
+    return true;
+}
+
 // Which flat_scan_kernel build serves a launch is pick_scan_kernel's choice (knn355.hip) from (query tile, metric, bf16 rows,
 // one query tile, width of the difference build or 0, pass of a prefiltered search); this is its legality rule: nullptr, or
 // why no build serves the combination (the width of a difference build does not enter: every width has its build).

@@ -11,6 +11,8 @@
 //                      one payload buffer, table, block sums, histograms, running count, int64 staging and all of them, or "refused"
 //   plan_check pool    reads lines "n d row_stride base elem_bytes normalize": the pooling launch -- ncb waves grid_x grid_y aligned,
 //                      or "refused"
+//   plan_check kde     reads lines "n ncols m": the density launch -- group_rows groups tiles chunks tail_rows tail_points part_bytes,
+//                      or "refused"
 //   plan_check poolchunks  reads "n chunk_rows" and n lines "start stop": the host pooling entry's uploads, one line per chunk --
 //                      "row0 row1 count: the indices of its ranges" (the host code of knn_pool_ranges that is separable from its
 //                      launches, under the sanitizers here)
@@ -360,6 +362,52 @@ static int run_poolchunks()
     return 0;
 }
 
+// ---- kernel density estimates (kde.inc) ----
+// `plan_check kde`: lines "n ncols m" -> group_rows groups tiles chunks tail_rows tail_points part_bytes, or "refused"
+static int run_kde()
+{
+    long long n, ncols, m;
+    while (scanf("%lld %lld %lld", &n, &ncols, &m) == 3) {
+        KdePlan p;
+        if (!plan_kde(n, ncols, m, &p)) {
+            printf("refused\n");
+            continue;
+        }
+        printf("%lld %d %lld %lld %d %d %lld\n", (long long)p.group_rows, p.groups, (long long)p.tiles, (long long)p.chunks, p.tail_rows, p.tail_points,
+               (long long)p.part_bytes);
+    }
+    return 0;
+}
+
+// every row is in one group and one chunk, every grid point in one tile; the grid fits a launch
+static void check_kde(int64_t n, int64_t ncols, int64_t m)
+{
+    const auto where = [&] { return describe("kde n %lld ncols %lld m %lld", (long long)n, (long long)ncols, (long long)m); };
+    KdePlan p;
+    const bool legal = n >= 2 && n <= KNN_KDE_MAX_ROWS && ncols >= 1 && ncols <= KNN_KDE_MAX_COLS && m >= 1 && m <= KNN_KDE_MAX_POINTS;
+    if (!plan_kde(n, ncols, m, &p)) {
+        INVARIANT(!legal);
+        return;
+    }
+    INVARIANT(legal);
+    INVARIANT(p.group_rows % 4096 == 0 && p.groups >= 1 && p.groups <= 256);
+    INVARIANT((int64_t)(p.groups - 1) * p.group_rows < n && (int64_t)p.groups * p.group_rows >= n);
+    INVARIANT(p.chunks >= 1 && p.chunks <= 65535 && (p.chunks - 1) * KDE_CHUNK + p.tail_rows == n && p.tail_rows >= 1 && p.tail_rows <= KDE_CHUNK);
+    INVARIANT(p.tiles >= 1 && p.tiles <= INT32_MAX && (p.tiles - 1) * KDE_TILE + p.tail_points == m && p.tail_points >= 1 && p.tail_points <= KDE_TILE);
+    INVARIANT(ncols <= 65535 && p.part_bytes == ncols * p.chunks * m * 8);
+}
+
+static void sweep_kde()
+{
+    const int64_t ns[] = {0, 1, 2, 255, 256, 257, 4096, 4097, 16383, 16384, 16385, 40000, 200000, 4096 * 256, 4096 * 256 + 1, 1048581,
+                          KNN_KDE_MAX_ROWS - 1, KNN_KDE_MAX_ROWS, KNN_KDE_MAX_ROWS + 1};
+    const int64_t ms[] = {0, 1, 15, 16, 17, 1000, KNN_KDE_MAX_POINTS, KNN_KDE_MAX_POINTS + 1};
+    const int64_t cs[] = {0, 1, 3, 12, KNN_KDE_MAX_COLS, KNN_KDE_MAX_COLS + 1};
+    for (int64_t n : ns)
+        for (int64_t m : ms)
+            for (int64_t c : cs) check_kde(n, c, m);
+}
+
 // every (range, column) pair of a launch is owned by exactly one (workgroup, wave, lane, element); the waves divide 64 in the
 // normalizing build; the grid fits; aligned is the pointer's and the stride's doing
 static void check_pool(int64_t n, int64_t d, int64_t stride, uintptr_t base, int elem, bool normalize)
@@ -523,6 +571,8 @@ static int run_sweep()
         }
     // the pooling launch of every (n, d, stride, base, element size, build) and the host entry's chunks
     sweep_pool();
+    // the density launch: groups, chunks and tiles cover every row and grid point once
+    sweep_kde();
     printf("plan_check sweep: %lld plans checked, %lld broken\n", g_checked, g_broken);
     return g_broken ? 1 : 0;
 }
@@ -536,7 +586,8 @@ int main(int argc, char **argv)
     if (argc == 2 && !strcmp(argv[1], "rank")) return run_rank();
     if (argc == 2 && !strcmp(argv[1], "pool")) return run_pool();
     if (argc == 2 && !strcmp(argv[1], "poolchunks")) return run_poolchunks();
+    if (argc == 2 && !strcmp(argv[1], "kde")) return run_kde();
     if (argc == 2 && !strcmp(argv[1], "sweep")) return run_sweep();
-    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank|pool|poolchunks < lines | plan_check sweep\n");
+    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank|pool|poolchunks|kde < lines | plan_check sweep\n");
     return 2;
 }
