@@ -184,31 +184,7 @@ __global__ void levels_eval_kernel(const int64_t *__restrict__ hits, int64_t nq,
 }
 
 // ---- host wrappers: host buffers in and out, rows processed in slabs -------------------------
-struct EvalBufs {
-    std::vector<std::pair<void *, size_t>> dev;
-    bool oom = false; // a get() has failed
-    ~EvalBufs() { for (auto &b : dev) if (b.first) (void)hipFree(b.first); }
-    void *get(size_t bytes)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-            oom = true;
-            return nullptr;
-        }
-        dev.push_back({p, bytes});
-        return p;
-    }
-};
-// a device-only buffer
-#define EVAL_ALLOC(var, type, bytes)                                                    \
-    type var = (type)bufs.get(bytes);                                                   \
-    if (!var) return set_err(KNN_ERR_HIP, "eval: out of device memory")
-#define EVAL_TRY(expr)                                                                  \
-    do {                                                                                \
-        const int rc_ = (expr);                                                         \
-        if (rc_) return rc_;                                                            \
-    } while (0)
-
+// (EvalBufs, EVAL_ALLOC, EVAL_TRY: knn355.hip, the head of the host side)
 // The slab walker: the columns that travel between the host and the device.  A column is declared once -- host pointer,
 // bytes per row, input or output -- which allocates `cap` rows of it through EvalBufs and registers its copy; upload and
 // download then move the rows [r0, r0 + m) of every input and of every output column (synchronous copies on the null

@@ -235,7 +235,7 @@ static size_t kde_span_bytes(int dtype, int64_t n, int ncols, int64_t row_stride
 }
 
 static int kde_stats_enqueue(const void *x, int dtype, int64_t n, int ncols, int64_t stride, const KdePlan &pl, double *stats_host, EvalBufs &bufs,
-                             hipStream_t s, RefineEvents &ev)
+                             hipStream_t s, EventList &ev)
 {
     const size_t gc = (size_t)pl.groups * ncols;
     EVAL_ALLOC(d_x, void *, kde_span_bytes(dtype, n, ncols, stride));
@@ -272,19 +272,13 @@ extern "C" int knn_kde_stats(const void *x, int32_t dtype, int64_t n, int32_t nc
     if (rc) return rc;
     if (!min_out || !max_out || !mean_out || !var_out) return set_err(KNN_ERR_INVALID, "kde_stats: null pointer");
     if ((rc = ensure_device(g_device))) return rc;
+    std::vector<double> stats((size_t)4 * ncols); // the caller's arrays are written when the whole call has succeeded
     // the upload rides the copy pipeline's host-to-device stream when no host search holds it; the kernels follow it on
     // the same stream (the null stream otherwise)
-    PipeLease lease;
-    if ((rc = lease_pipes(g_device, true, lease))) return rc;
-    hipStream_t s = lease.cp ? lease.cp->h2d : nullptr;
-    EvalBufs bufs; // (freed behind the wait below)
-    RefineEvents ev;
-    std::vector<double> stats((size_t)4 * ncols); // the caller's arrays are written when the whole call has succeeded
-    rc = kde_stats_enqueue(x, dtype, n, ncols, row_stride, pl, stats.data(), bufs, s, ev);
-    const hipError_t e = hipStreamSynchronize(s); // (always: a copy already queued reads the caller's rows)
-    if (rc) return rc;
-    if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("kde_stats: ") + hipGetErrorString(e));
-    for (int i = 0; i < 2; i++) HIP_TRY(hipEventElapsedTime(&g_kde_stats_ms[i], ev.ev[i], ev.ev[i + 1]));
+    HostCall call;
+    if ((rc = call.lease(g_device, true))) return rc;
+    rc = kde_stats_enqueue(x, dtype, n, ncols, row_stride, pl, stats.data(), call.bufs, call.s, call.ev);
+    if ((rc = call.finish("kde_stats", rc, g_kde_stats_ms, 2))) return rc;
     for (int c = 0; c < ncols; c++) {
         min_out[c] = stats[c];
         max_out[c] = stats[(size_t)ncols + c];
@@ -295,7 +289,7 @@ extern "C" int knn_kde_stats(const void *x, int32_t dtype, int64_t n, int32_t nc
 }
 
 static int kde_eval_enqueue(const void *x, int dtype, int64_t n, int ncols, int64_t stride, const double *grid, int64_t m, const double *inv_h,
-                            const double *norm, const KdePlan &pl, double *out, EvalBufs &bufs, hipStream_t s, RefineEvents &ev)
+                            const double *norm, const KdePlan &pl, double *out, EvalBufs &bufs, hipStream_t s, EventList &ev)
 {
     const size_t cm = (size_t)ncols * m;
     EVAL_ALLOC(d_x, void *, kde_span_bytes(dtype, n, ncols, stride));
@@ -333,17 +327,10 @@ extern "C" int knn_kde_eval(const void *x, int32_t dtype, int64_t n, int32_t nco
             return set_err(KNN_ERR_INVALID, "kde_eval: inv_h and norm must be positive and finite (a zero variance or a bad factor)");
     if (!kde_all_finite(grid, 1, (int64_t)ncols * m, 0)) return set_err(KNN_ERR_INVALID, "kde_eval: the grid holds a NaN or an infinity");
     if ((rc = ensure_device(g_device))) return rc;
-    PipeLease lease;
-    if ((rc = lease_pipes(g_device, true, lease))) return rc;
-    hipStream_t s = lease.cp ? lease.cp->h2d : nullptr;
-    EvalBufs bufs; // (freed behind the wait below)
-    RefineEvents ev;
-    rc = kde_eval_enqueue(x, dtype, n, ncols, row_stride, grid, m, inv_h, norm, pl, out, bufs, s, ev);
-    const hipError_t e = hipStreamSynchronize(s); // (always: copies already queued read the caller's arrays)
-    if (rc) return rc;
-    if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("kde_eval: ") + hipGetErrorString(e));
-    for (int i = 0; i < 3; i++) HIP_TRY(hipEventElapsedTime(&g_kde_eval_ms[i], ev.ev[i], ev.ev[i + 1]));
-    return 0;
+    HostCall call;
+    if ((rc = call.lease(g_device, true))) return rc;
+    rc = kde_eval_enqueue(x, dtype, n, ncols, row_stride, grid, m, inv_h, norm, pl, out, call.bufs, call.s, call.ev);
+    return call.finish("kde_eval", rc, g_kde_eval_ms, 3);
 }
 
 extern "C" int knn_kde_last_ms(float *stats_ms, float *eval_ms)

@@ -3181,6 +3181,62 @@ static int set_err(int code, const std::string &msg)
             return set_err(KNN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+// ---- what one call owns: every host entry releases its transient device memory, events and streams
+// through these and HostCall below, whichever way it returns
+// device buffers of one call, straight from hipMalloc and hipFree'd with it
+struct EvalBufs {
+    std::vector<std::pair<void *, size_t>> dev;
+    bool oom = false; // a get() has failed
+    ~EvalBufs() { for (auto &b : dev) if (b.first) (void)hipFree(b.first); }
+    void *get(size_t bytes)
+    {
+        void *p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
+            oom = true;
+            return nullptr;
+        }
+        dev.push_back({p, bytes});
+        return p;
+    }
+};
+// a device-only buffer
+#define EVAL_ALLOC(var, type, bytes)                                                    \
+    type var = (type)bufs.get(bytes);                                                   \
+    if (!var) return set_err(KNN_ERR_HIP, "eval: out of device memory")
+#define EVAL_TRY(expr)                                                                  \
+    do {                                                                                \
+        const int rc_ = (expr);                                                         \
+        if (rc_) return rc_;                                                            \
+    } while (0)
+
+// HIP events of one call, in the order they were recorded
+struct EventList {
+    std::vector<hipEvent_t> ev;
+    ~EventList()
+    {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    int mark(hipStream_t s, unsigned flags = 0)
+    {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        ev.push_back(e);
+        HIP_TRY(hipEventRecord(e, s));
+        return 0;
+    }
+};
+// after the streams have drained: the times between the events of every pair (0, 1), (2, 3), ... summed into *ms
+static int sum_pairs(const EventList &ev, float *ms)
+{
+    *ms = 0.0f;
+    for (size_t i = 0; i + 1 < ev.ev.size(); i += 2) {
+        float t = 0;
+        HIP_TRY(hipEventElapsedTime(&t, ev.ev[i], ev.ev[i + 1]));
+        *ms += t;
+    }
+    return 0;
+}
+
 // Device scratch buffers are recycled through a small per-device pool: the reference's scripts
 // build a fresh index per embedding file (cath/search.py:20-24), and hipMalloc/hipFree of the
 // gigabyte-sized candidate-list workspace would otherwise dominate their end-to-end time.
@@ -3219,6 +3275,38 @@ struct DevPool {
     }
 };
 static DevPool g_pool;
+
+// database storage goes through the same pool as the scratch buffers
+static void *pool_alloc(size_t bytes, int device, size_t *got)
+{
+    if (void *q = g_pool.take(bytes, device, got)) return q;
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    *got = bytes;
+    return p;
+}
+
+// A pool_alloc that goes back to the pool with its scope (null: the allocation failed, or 0 bytes were asked for), unless
+// release() has handed it to a new owner.  The destructor waits for nothing: whoever enqueued work on the buffer has
+// drained that stream first.
+struct PoolBuf {
+    void *p = nullptr;
+    size_t got = 0;
+    int device = 0;
+    PoolBuf(size_t bytes, int dev) : device(dev) { if (bytes) p = pool_alloc(bytes, dev, &got); }
+    PoolBuf(const PoolBuf &) = delete;
+    PoolBuf &operator=(const PoolBuf &) = delete;
+    ~PoolBuf() { if (p) g_pool.give(p, got, device); }
+    explicit operator bool() const { return p != nullptr; }
+    template <typename T> T *get() const { return (T *)p; }
+    void *release(size_t *bytes)
+    {
+        void *q = p;
+        *bytes = got;
+        p = nullptr;
+        return q;
+    }
+};
 
 extern "C" int64_t knn_trim(void)
 {
@@ -3335,6 +3423,22 @@ struct StreamPool {
     }
 };
 static StreamPool g_streams;
+
+// A stream of the pool for one scope (null: the take failed, or `want` was false); it goes back drained.
+struct StreamLease {
+    int device;
+    hipStream_t s;
+    explicit StreamLease(int dev, bool want = true) : device(dev), s(want ? g_streams.take(dev) : nullptr) {}
+    StreamLease(const StreamLease &) = delete;
+    StreamLease &operator=(const StreamLease &) = delete;
+    ~StreamLease()
+    {
+        if (!s) return;
+        (void)hipStreamSynchronize(s);
+        g_streams.give(device, s);
+    }
+    operator hipStream_t() const { return s; }
+};
 
 struct knn_index_s {
     int d = 0, dp = 0, metric = 0, device = 0;
@@ -3487,7 +3591,6 @@ extern "C" int knn_normalize_l2_dev(float *x_dev, int64_t n, int32_t d, void *st
     return 0;
 }
 
-static void *pool_alloc(size_t bytes, int device, size_t *got);
 extern "C" int knn_normalize_l2(float *x_host, int64_t n, int32_t d)
 {
     if (n < 0 || d <= 0) return set_err(KNN_ERR_INVALID, "normalize_l2: bad shape");
@@ -3501,27 +3604,14 @@ extern "C" int knn_normalize_l2(float *x_host, int64_t n, int32_t d)
     // + knn_flat_reconstruct: one crossing each way -- pfam/proteins_search.py's flat mode does.)
     const int64_t rows_per = std::max<int64_t>(1, (int64_t)(64ull << 20) / ((int64_t)d * 4));
     const int64_t nbuf = std::min(n, rows_per);
-    float *buf[2] = {nullptr, nullptr};
-    size_t got[2] = {0, 0};
-    hipStream_t st[2] = {nullptr, nullptr};
-    auto cleanup = [&]() {
-        for (int i = 0; i < 2; i++) {
-            if (st[i]) {
-                (void)hipStreamSynchronize(st[i]);
-                g_streams.give(g_device, st[i]);
-            }
-            if (buf[i]) g_pool.give(buf[i], got[i], g_device);
-        }
-    };
     const int lanes = n > nbuf ? 2 : 1;
-    for (int i = 0; i < lanes; i++) {
-        buf[i] = (float *)pool_alloc((size_t)nbuf * d * 4, g_device, &got[i]);
-        st[i] = g_streams.take(g_device);
-        if (!buf[i] || !st[i]) {
-            cleanup();
-            return set_err(KNN_ERR_HIP, "normalize_l2: out of device memory");
-        }
-    }
+    // (the streams are declared behind the buffers: they go first, drained, whichever way the call returns)
+    const size_t bytes = (size_t)nbuf * d * 4;
+    PoolBuf buf0(bytes, g_device), buf1(lanes > 1 ? bytes : 0, g_device);
+    StreamLease st0(g_device), st1(g_device, lanes > 1);
+    if (!buf0 || !st0 || (lanes > 1 && (!buf1 || !st1))) return set_err(KNN_ERR_HIP, "normalize_l2: out of device memory");
+    float *buf[2] = {buf0.get<float>(), buf1.get<float>()};
+    const hipStream_t st[2] = {st0, st1};
     int turn = 0;
     for (int64_t i0 = 0; i0 < n; i0 += nbuf, turn ^= (lanes - 1)) {
         const int64_t m = std::min(nbuf, n - i0);
@@ -3529,22 +3619,15 @@ extern "C" int knn_normalize_l2(float *x_host, int64_t n, int32_t d)
         if (e == hipSuccess) e = hipMemcpyAsync(buf[turn], x_host + i0 * d, (size_t)m * d * 4, hipMemcpyHostToDevice, st[turn]);
         if (e == hipSuccess) {
             rc = normalize_dev_impl(buf[turn], m, d, d, st[turn]);
-            if (rc) { cleanup(); return rc; }
+            if (rc) return rc;
             e = hipMemcpyAsync(x_host + i0 * d, buf[turn], (size_t)m * d * 4, hipMemcpyDeviceToHost, st[turn]);
         }
-        if (e != hipSuccess) {
-            cleanup();
-            return set_err(KNN_ERR_HIP, std::string("normalize_l2 copy: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("normalize_l2 copy: ") + hipGetErrorString(e));
     }
     for (int i = 0; i < lanes; i++) {
         hipError_t e = hipStreamSynchronize(st[i]);
-        if (e != hipSuccess) {
-            cleanup();
-            return set_err(KNN_ERR_HIP, std::string("normalize_l2: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("normalize_l2: ") + hipGetErrorString(e));
     }
-    cleanup();
     return 0;
 }
 
@@ -3621,16 +3704,6 @@ extern "C" int knn_flat_view(knn_handle parent, knn_handle *out)
     return 0;
 }
 
-// database storage goes through the same pool as the scratch buffers
-static void *pool_alloc(size_t bytes, int device, size_t *got)
-{
-    if (void *q = g_pool.take(bytes, device, got)) return q;
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    *got = bytes;
-    return p;
-}
-
 static void free_index_buffers(knn_index_s *h)
 {
     if (!h->is_view) h->storage_gen->fetch_add(1);
@@ -3699,41 +3772,47 @@ extern "C" int knn_reset(knn_handle h)
     return 0;
 }
 
-static int grow_index(knn_index_s *h, int64_t need_rows)
+// The handle's rows move to fresh storage of new_cap rows (> cap_rows; the caller holds h->mu and has set the device): the
+// common tail of grow_index and knn_flat_reserve.  A failure leaves the handle as it was, and the new buffers go back.
+static int move_storage(knn_index_s *h, int64_t new_cap, const char *who)
 {
-    if (need_rows <= h->cap_rows) return 0;
-    int64_t new_cap = std::max<int64_t>(need_rows, h->cap_rows + h->cap_rows / 2);
-    if (h->cap_rows == 0) new_cap = need_rows; // first add: exact fit (the reference adds once)
-    size_t row_bytes = (size_t)h->dp * 4;
-    size_t xb_got = 0, yn_got = 0;
-    float *nxb = (float *)pool_alloc((size_t)new_cap * row_bytes, h->device, &xb_got);
-    if (!nxb) {
-        new_cap = need_rows;
-        nxb = (float *)pool_alloc((size_t)new_cap * row_bytes, h->device, &xb_got);
-        if (!nxb) return set_err(KNN_ERR_HIP, "add: out of device memory");
-    }
-    float *nyn = (float *)pool_alloc(((size_t)new_cap + 64) * 4, h->device, &yn_got);
-    if (!nyn) {
-        g_pool.give(nxb, xb_got, h->device);
-        return set_err(KNN_ERR_HIP, "add: out of device memory");
-    }
-    if (h->ntotal > 0) {
+    const size_t row_bytes = (size_t)h->dp * 4;
+    PoolBuf bxb((size_t)new_cap * row_bytes, h->device);
+    if (!bxb) return set_err(KNN_ERR_HIP, std::string(who) + ": out of device memory");
+    PoolBuf byn(((size_t)new_cap + 64) * 4, h->device);
+    if (!byn) return set_err(KNN_ERR_HIP, std::string(who) + ": out of device memory");
+    float *nxb = bxb.get<float>(), *nyn = byn.get<float>();
+    auto copy = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(nxb, h->xb, (size_t)h->ntotal * row_bytes, hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(nyn, h->yn, (size_t)h->ntotal * 4, hipMemcpyDeviceToDevice, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-    }
+        return 0;
+    };
+    if (h->ntotal > 0)
+        if (int rc = copy()) {
+            (void)hipStreamSynchronize(h->stream); // (a copy already queued writes a buffer that goes back to the pool)
+            return rc;
+        }
     if (h->xb) {
         h->storage_gen->fetch_add(1); // views of the old storage are dead
         (void)hipDeviceSynchronize(); // ... and nothing may still be scanning it
         g_pool.give(h->xb, h->xb_bytes, h->device);
     }
     if (h->yn) g_pool.give(h->yn, h->yn_bytes, h->device);
-    h->xb = nxb;
-    h->yn = nyn;
-    h->xb_bytes = xb_got;
-    h->yn_bytes = yn_got;
+    h->xb = (float *)bxb.release(&h->xb_bytes);
+    h->yn = (float *)byn.release(&h->yn_bytes);
     h->cap_rows = new_cap;
     return 0;
+}
+
+static int grow_index(knn_index_s *h, int64_t need_rows)
+{
+    if (need_rows <= h->cap_rows) return 0;
+    int64_t new_cap = std::max<int64_t>(need_rows, h->cap_rows + h->cap_rows / 2);
+    if (h->cap_rows == 0) new_cap = need_rows; // first add: exact fit (the reference adds once)
+    int rc = move_storage(h, new_cap, "add");
+    if (rc && new_cap > need_rows) rc = move_storage(h, need_rows, "add"); // (the guess was too large: the exact fit)
+    return rc;
 }
 
 // bf16 copies of rows [r0, r0 + n) of an approximate index (kept beside the fp32 rows: reconstruct, norms and the
@@ -4621,11 +4700,7 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
     g_trace_grid = (int)std::min<size_t>(nitems, (size_t)sp.max_wgs);
 #endif
     // 2 + 3. the launches, each followed by the final selection of the rows it completes (verified against the sample's bound)
-    hipEvent_t gev[SYM_MAX_GROUPS] = {};
-    struct GroupEvents { // (the events of this call go with it, whichever way it returns -- ADVICE r4)
-        hipEvent_t *e;
-        ~GroupEvents() { for (int i = 0; i < SYM_MAX_GROUPS; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } gev_guard{gev};
+    EventList gev; // with several groups: one behind each group's selection
     for (int g = 0; g < groups; g++) {
         const size_t g0 = (size_t)h->sym_gstart[(size_t)g], g1 = (size_t)h->sym_gstart[(size_t)g + 1];
         for (size_t i0 = g0; i0 < g1; i0 += (size_t)sp.max_wgs) {
@@ -4644,10 +4719,7 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
         sel.qthr = qthr + r0; sel.fail = (int *)h->ws_flag.p;
         rc = launch_select(sel, s, &h->ws_tmp);
         if (rc) return rc;
-        if (groups > 1) {
-            HIP_TRY(hipEventCreateWithFlags(&gev[g], hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(gev[g], s));
-        }
+        if (groups > 1 && (rc = gev.mark(s, hipEventDisableTiming))) return rc;
     }
     h->last_kernel = sp.name; h->last_qt = sp.ts; h->last_dt = sp.ts; h->last_chunks = h->sym_run; h->last_grid = (int)nitems;
     h->last_seed_stride = sp.st; h->last_seed_stat = sp.j; h->last_sample_rows = sp.S;
@@ -4659,7 +4731,7 @@ static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I
     hipError_t e = hipSuccess;
     for (int g = 0; g < groups; g++) {
         const int64_t r0 = sym_group_row0(sp, n, g), r1 = sym_group_row0(sp, n, g + 1);
-        if (e == hipSuccess) e = hipStreamWaitEvent(d2h, gev[g], 0);
+        if (e == hipSuccess) e = hipStreamWaitEvent(d2h, gev.ev[(size_t)g], 0);
         if (e == hipSuccess && r1 > r0) e = hipMemcpyAsync(D_host + (size_t)r0 * k, D_dev + (size_t)r0 * k, (size_t)(r1 - r0) * k * 4, hipMemcpyDeviceToHost, d2h);
         if (e == hipSuccess && r1 > r0) e = hipMemcpyAsync(I_host + (size_t)r0 * k, I_dev + (size_t)r0 * k, (size_t)(r1 - r0) * k * 8, hipMemcpyDeviceToHost, d2h);
     }
@@ -4705,6 +4777,43 @@ static int lease_pipes(int device, bool want, PipeLease &lease)
     lease.cp = &cp;
     return 0;
 }
+
+// The scaffold of a host entry that keeps nothing behind: enqueue on `s` (uploads may ride pipes.cp->h2d), then finish().
+// ORDER: streams are drained before any buffer goes back to the pool or to hipFree -- the pool may hand a buffer to
+// another handle at once -- and a stream of g_streams goes back behind the buffers.  finish() drains; the members then go
+// in reverse: events, buffers, the stream, the pipes.  (An entry without a HostCall declares its StreamLease behind its
+// PoolBufs: the lease's destructor drains, and it runs first.)
+struct HostCall {
+    PipeLease pipes;
+    StreamLease own;
+    EvalBufs bufs;
+    EventList ev;
+    hipStream_t s; // where the call's kernels run: its own stream, else the leased h2d stream, else the caller's / the null stream
+    // on a stream the caller names (null: the null stream)
+    explicit HostCall(hipStream_t caller = nullptr) : own(0, false), s(caller) {}
+    // on a stream of g_streams (s is null when there is none)
+    explicit HostCall(int device) : own(device), s(own) {}
+    // the device's copy pipes, if wanted and free; a call without a stream of its own then runs on their h2d stream
+    int lease(int device, bool want)
+    {
+        EVAL_TRY(lease_pipes(device, want, pipes));
+        if (pipes.cp && !own) s = pipes.cp->h2d;
+        return 0;
+    }
+    // Behind the enqueueing, whatever it returned (rc): waits for the h2d stream and for s -- always, copies already queued
+    // read and write the caller's arrays -- then reports rc, else the first HIP error as "who: ...", else fills ms[i] with
+    // the time between ev[i] and ev[i + 1], i < n_ms.
+    int finish(const char *who, int rc, float *ms, int n_ms)
+    {
+        hipError_t e = pipes.cp && pipes.cp->h2d != s ? hipStreamSynchronize(pipes.cp->h2d) : hipSuccess;
+        const hipError_t es = hipStreamSynchronize(s);
+        if (rc) return rc;
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        for (int i = 0; i < n_ms; i++) HIP_TRY(hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]));
+        return 0;
+    }
+};
 
 // The result download of a batched search whose batches follow one another on the search stream `s` (hnsw_search_device,
 // lsh_search_batches).  Piped (cp given): two sets of result buffers, and while batch b runs on `s` the results of batch
@@ -5093,31 +5202,7 @@ extern "C" int knn_flat_reserve(knn_handle h, int64_t nrows)
     HIP_TRY(hipSetDevice(h->device));
     if (nrows <= h->cap_rows) return 0;
     // exact-size allocation (grow_index over-allocates only when it has to guess)
-    const size_t row_bytes = (size_t)h->dp * 4;
-    size_t xb_got = 0, yn_got = 0;
-    float *nxb = (float *)pool_alloc((size_t)nrows * row_bytes, h->device, &xb_got);
-    if (!nxb) return set_err(KNN_ERR_HIP, "reserve: out of device memory");
-    float *nyn = (float *)pool_alloc(((size_t)nrows + 64) * 4, h->device, &yn_got);
-    if (!nyn) {
-        g_pool.give(nxb, xb_got, h->device);
-        return set_err(KNN_ERR_HIP, "reserve: out of device memory");
-    }
-    if (h->ntotal > 0) {
-        HIP_TRY(hipMemcpyAsync(nxb, h->xb, (size_t)h->ntotal * row_bytes, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(nyn, h->yn, (size_t)h->ntotal * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    if (h->xb) {
-        h->storage_gen->fetch_add(1);
-        (void)hipDeviceSynchronize();
-        g_pool.give(h->xb, h->xb_bytes, h->device);
-    }
-    if (h->yn) g_pool.give(h->yn, h->yn_bytes, h->device);
-    h->xb = nxb;
-    h->yn = nyn;
-    h->xb_bytes = xb_got;
-    h->yn_bytes = yn_got;
-    h->cap_rows = nrows;
+    if (int rc = move_storage(h, nrows, "reserve")) return rc;
     return scan16_sync_rows(h, h->ntotal, 0, h->stream); // (the fp16 copies grow with the rows)
 }
 
@@ -5203,9 +5288,11 @@ extern "C" int knn_flat_read_rate(knn_handle h, int32_t reps, float *best_ms, in
     *best_ms = 0.0f;
     if (!bytes) return 0;
     if (h->ws_flag.ensure(64, h->done, h->stream)) return set_err(KNN_ERR_HIP, "read_rate: out of device memory");
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    EventList ev; // one pair, recorded again around every launch
+    int rc = ev.mark(h->stream);
+    if (!rc) rc = ev.mark(h->stream);
+    if (rc) return rc;
+    const hipEvent_t e0 = ev.ev[0], e1 = ev.ev[1];
     float best = FLT_MAX;
     for (int grid : {2048, 4096, 8192})
         for (int r = 0; r < std::max(1, reps); r++) {
@@ -5217,8 +5304,6 @@ extern "C" int knn_flat_read_rate(knn_handle h, int32_t reps, float *best_ms, in
             HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
             best = std::min(best, ms);
         }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *best_ms = best;
     return 0;
 }
@@ -5268,22 +5353,14 @@ extern "C" int knn_mfma_rate(int32_t warm_ms, float *tflops, float *clock_mhz)
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g_device);
     const int grid = 2 * std::max(1, cus), iters = 8000; // (two workgroups per CU: two waves per SIMD, as in the scan)
-    size_t got_o = 0, got_c = 0;
-    float *o = (float *)pool_alloc(64, g_device, &got_o);
-    unsigned long long *c = (unsigned long long *)pool_alloc((size_t)grid * 16, g_device, &got_c);
-    hipStream_t s = g_streams.take(g_device);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        if (s) { (void)hipStreamSynchronize(s); g_streams.give(g_device, s); }
-        if (o) g_pool.give(o, got_o, g_device);
-        if (c) g_pool.give(c, got_c, g_device);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    if (!o || !c || !s || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        cleanup();
-        return set_err(KNN_ERR_HIP, "mfma_rate: out of resources");
-    }
+    // (the stream is declared behind the buffers: it goes first, drained, whichever way the call returns)
+    PoolBuf bo(64, g_device), bc((size_t)grid * 16, g_device);
+    StreamLease s(g_device);
+    EventList ev; // one pair, recorded again around every launch
+    if (!bo || !bc || !s || ev.mark(s) || ev.mark(s)) return set_err(KNN_ERR_HIP, "mfma_rate: out of resources");
+    float *o = bo.get<float>();
+    unsigned long long *c = bc.get<unsigned long long>();
+    const hipEvent_t e0 = ev.ev[0], e1 = ev.ev[1];
     // back-to-back launches until warm_ms of them have run (the clock settles under load), then the best of eight
     const double flop = (double)grid * 4 /* waves */ * iters * 16.0 * (32.0 * 32 * 2 * 2);
     float best = FLT_MAX, total = 0.0f;
@@ -5297,10 +5374,7 @@ extern "C" int knn_mfma_rate(int32_t warm_ms, float *tflops, float *clock_mhz)
         if (e == hipSuccess) e = hipEventSynchronize(e1);
         float ms = 0.0f;
         if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) {
-            cleanup();
-            return set_err(KNN_ERR_HIP, std::string("mfma_rate: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("mfma_rate: ") + hipGetErrorString(e));
         total += ms;
         if (total < (float)warm_ms) continue;
         timed++;
@@ -5313,7 +5387,6 @@ extern "C" int knn_mfma_rate(int32_t warm_ms, float *tflops, float *clock_mhz)
             }
         }
     }
-    cleanup();
     *tflops = (float)(flop / (best * 1e-3) / 1e12);
     if (clock_mhz) *clock_mhz = (float)mhz;
     return 0;

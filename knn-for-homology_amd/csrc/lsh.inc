@@ -444,18 +444,12 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
     if (h->ws_x.ensure((size_t)std::min(n, slab) * h->d * 4) || h->ws_xp.ensure((size_t)std::min(n, slab) * h->dp * 4))
         return set_err(KNN_ERR_HIP, "lsh: out of device memory");
     hipStream_t s = h->stream;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    struct EventGuard {
-        hipEvent_t *e;
-        ~EventGuard() { for (int i = 0; i < 3; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } guard{ev};
-    if (ms)
-        for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]));
     for (int64_t i0 = 0; i0 < n; i0 += slab) {
         const int64_t m = std::min(slab, n - i0);
-        if (ms) HIP_TRY(hipEventRecord(ev[0], s));
+        EventList ev; // with ms: in front of the slab's upload, behind it, behind its kernel
+        if (ms) EVAL_TRY(ev.mark(s));
         HIP_TRY(hipMemcpyAsync(h->ws_x.p, x_host + i0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
-        if (ms) HIP_TRY(hipEventRecord(ev[1], s));
+        if (ms) EVAL_TRY(ev.mark(s));
         const float *xp = (const float *)h->ws_x.p;
         if (h->dp != h->d) {
             int rc = pad_rows_dev((const float *)h->ws_x.p, m, h->d, (float *)h->ws_xp.p, h->dp, s);
@@ -479,12 +473,12 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
             hipLaunchKernelGGL(lsh_encode_kernel, dim3(grid), dim3(256), lds, s, p);
         }
         HIP_TRY(hipGetLastError());
-        if (ms) HIP_TRY(hipEventRecord(ev[2], s));
+        if (ms) EVAL_TRY(ev.mark(s));
         HIP_TRY(hipStreamSynchronize(s));
         if (ms) {
             float up = 0, pr = 0;
-            HIP_TRY(hipEventElapsedTime(&up, ev[0], ev[1]));
-            HIP_TRY(hipEventElapsedTime(&pr, ev[1], ev[2]));
+            HIP_TRY(hipEventElapsedTime(&up, ev.ev[0], ev.ev[1]));
+            HIP_TRY(hipEventElapsedTime(&pr, ev.ev[1], ev.ev[2]));
             ms[0] += up;
             ms[1] += pr;
         }
@@ -529,41 +523,28 @@ extern "C" int knn_lsh_train(knn_lsh_s *h, const float *x_host, int64_t n)
         return set_err(KNN_ERR_UNSUPPORTED, "lsh_train: the projections of the training rows take " + std::to_string(need) +
                                                 " bytes, more than half of the " + std::to_string(free_b) +
                                                 " bytes free on the device: train on a sample of the rows");
-    struct Scratch { // (freed whichever way the call returns)
-        float *P = nullptr, *thr = nullptr;
-        int32_t *status = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Scratch()
-        {
-            if (P) (void)hipFree(P);
-            if (thr) (void)hipFree(thr);
-            if (status) (void)hipFree(status);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } sc;
-    if (hipMalloc((void **)&sc.P, need) != hipSuccess || hipMalloc((void **)&sc.thr, (size_t)h->nbits * 4) != hipSuccess ||
-        hipMalloc((void **)&sc.status, (size_t)h->nbits * 4) != hipSuccess)
-        return set_err(KNN_ERR_HIP, "lsh_train: out of device memory");
-    HIP_TRY(hipEventCreate(&sc.e0));
-    HIP_TRY(hipEventCreate(&sc.e1));
+    EvalBufs bufs;
+    EventList ev; // around the median kernel
+    float *d_P = (float *)bufs.get(need), *d_thr = (float *)bufs.get((size_t)h->nbits * 4);
+    int32_t *d_status = (int32_t *)bufs.get((size_t)h->nbits * 4);
+    if (bufs.oom) return set_err(KNN_ERR_HIP, "lsh_train: out of device memory");
     float ms[3] = {0, 0, 0};
     // the projections are taken without thresholds whatever the handle holds: lsh_project_kernel does not read them
-    int rc = lsh_encode_host_rows(h, x_host, n, nullptr, sc.P, ldp, ms);
+    int rc = lsh_encode_host_rows(h, x_host, n, nullptr, d_P, ldp, ms);
     if (rc) return rc;
     hipStream_t s = h->stream;
     LshMedianParams mp;
-    mp.proj = sc.P; mp.n = n; mp.ldp = ldp; mp.thr = sc.thr; mp.status = sc.status;
-    HIP_TRY(hipEventRecord(sc.e0, s));
+    mp.proj = d_P; mp.n = n; mp.ldp = ldp; mp.thr = d_thr; mp.status = d_status;
+    EVAL_TRY(ev.mark(s));
     hipLaunchKernelGGL(lsh_median_kernel, dim3(h->nbits), dim3(256), 0, s, mp); // (the padding columns are skipped)
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.e1, s));
+    EVAL_TRY(ev.mark(s));
     std::vector<float> thr((size_t)h->nbits);
     std::vector<int32_t> status((size_t)h->nbits);
-    HIP_TRY(hipMemcpyAsync(thr.data(), sc.thr, thr.size() * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(status.data(), sc.status, status.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(thr.data(), d_thr, thr.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipEventElapsedTime(&ms[2], sc.e0, sc.e1));
+    HIP_TRY(hipEventElapsedTime(&ms[2], ev.ev[0], ev.ev[1]));
     for (int b = 0; b < h->nbits; b++)
         if (status[b])
             return set_err(KNN_ERR_INVALID, std::string("lsh_train: ") + (status[b] == 1 ? "a projection onto bit " : "the median (+inf and -inf around the middle) of bit ") +
@@ -695,7 +676,7 @@ static int launch_hamming(const HammingParams &p, int grid, size_t lds, hipStrea
 // flat given: the batch's kb ids stay on the device, refine_batch scores them against flat's rows with the batch's fp32
 // queries -- still on the device from the encode step -- and its best k are the result.  Either way only [m][k] goes down.
 static int lsh_search_batches(knn_lsh_s *h, knn_index_s *flat, const float *q_host, int64_t nq, int64_t kb, int64_t k, float *D_host,
-                              int64_t *I_host, RefineEvents &rev)
+                              int64_t *I_host, EventList &rev)
 {
     hipStream_t s = h->stream;
     const int QT = 32, DT = 256;
@@ -795,7 +776,7 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
         fill_empty_host(D_host, I_host, nq * k, KNN_METRIC_L2); // (Hamming distances: smaller is better)
         return 0;
     }
-    RefineEvents none;
+    EventList none;
     return lsh_search_batches(h, nullptr, q_host, nq, k, k, D_host, I_host, none);
 }
 
@@ -822,10 +803,10 @@ extern "C" int knn_lsh_search_refine(knn_lsh_s *h, knn_handle flat, const float 
         return 0;
     }
     HIP_TRY(hipStreamSynchronize(flat->stream)); // (the rows are read on the LSH handle's stream: whatever the flat handle's own stream still does to them first)
-    RefineEvents rev;
+    EventList rev;
     rc = lsh_search_batches(h, flat, q_host, nq, kb, k, D_host, I_host, rev);
     if (rc) return rc;
-    return rev.sum(flat->refine_ms);
+    return refine_sum_ms(rev, flat->refine_ms);
 }
 
 // IndexLSH::reset: the handle keeps its rotation, thresholds and the codes' allocation

@@ -219,7 +219,7 @@ static int pca_check_shape(const char *who, int64_t n, int64_t n_min, int32_t d)
 }
 
 // everything of knn_pca_moments that runs on stream s, enqueued; the caller waits for s whatever this returns
-static int pca_moments_enqueue(const float *x, int64_t n, int d, float *mean, double *cov, EvalBufs &bufs, hipStream_t s, RefineEvents &ev)
+static int pca_moments_enqueue(const float *x, int64_t n, int d, float *mean, double *cov, EvalBufs &bufs, hipStream_t s, EventList &ev)
 {
     const int64_t L = pca_group_rows(n);
     const int groups = (int)((n + L - 1) / L);
@@ -257,17 +257,10 @@ extern "C" int knn_pca_moments(const float *x, int64_t n, int32_t d, float *mean
     if ((rc = ensure_device(g_device))) return rc;
     // the upload rides the copy pipeline's host-to-device stream when no host search holds it; the kernels follow it on
     // the same stream (the null stream otherwise)
-    PipeLease lease;
-    if ((rc = lease_pipes(g_device, true, lease))) return rc;
-    hipStream_t s = lease.cp ? lease.cp->h2d : nullptr;
-    EvalBufs bufs; // (freed behind the wait below)
-    RefineEvents ev;
-    rc = pca_moments_enqueue(x, n, d, mean, cov, bufs, s, ev);
-    const hipError_t e = hipStreamSynchronize(s); // (always: a copy already queued reads and writes the caller's arrays)
-    if (rc) return rc;
-    if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("pca_moments: ") + hipGetErrorString(e));
-    for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&g_pca_moments_ms[i], ev.ev[i], ev.ev[i + 1]));
-    return 0;
+    HostCall call;
+    if ((rc = call.lease(g_device, true))) return rc;
+    rc = pca_moments_enqueue(x, n, d, mean, cov, call.bufs, call.s, call.ev);
+    return call.finish("pca_moments", rc, g_pca_moments_ms, 4);
 }
 
 extern "C" int knn_pca_project(const float *x, int64_t n, int32_t d, const float *mean, const float *components, int32_t nc, float *out)
@@ -288,7 +281,7 @@ extern "C" int knn_pca_project(const float *x, int64_t n, int32_t d, const float
     float *d_out = w.out(out, (size_t)nc * 4);
     EVAL_TRY(w.ready());
     EVAL_TRY(tab.upload(0, 1));
-    RefineEvents ev;
+    EventList ev;
     for (int64_t r0 = 0; r0 < n; r0 += slab) {
         const int64_t m = std::min(slab, n - r0);
         EVAL_TRY(w.upload(r0, m));
@@ -298,14 +291,7 @@ extern "C" int knn_pca_project(const float *x, int64_t n, int32_t d, const float
         EVAL_TRY(ev.mark(nullptr));
         EVAL_TRY(w.download(r0, m));
     }
-    float total = 0;
-    for (size_t i = 0; i + 1 < ev.ev.size(); i += 2) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, ev.ev[i], ev.ev[i + 1]));
-        total += t;
-    }
-    g_pca_project_ms = total;
-    return 0;
+    return sum_pairs(ev, &g_pca_project_ms);
 }
 
 extern "C" int knn_pca_last_ms(float *moments_ms, float *project_ms)

@@ -205,43 +205,38 @@ extern "C" int knn_pool_ranges_dev(const void *x_dev, int32_t dtype, int64_t row
     if (!plan_pool(n, d, row_stride, (uintptr_t)x_dev, dtype ? 2 : 4, flags & KNN_POOL_NORMALIZE, &pl)) return set_err(KNN_ERR_INVALID, "pool_ranges_dev: no plan");
     int device = 0;
     HIP_TRY(hipGetDevice(&device));
-    hipStream_t s = (hipStream_t)stream;
-    size_t got = 0;
-    unsigned long long *d_status = (unsigned long long *)pool_alloc(64, device, &got);
-    if (!d_status) return set_err(KNN_ERR_HIP, "pool_ranges_dev: out of device memory");
-    RefineEvents ev;
     unsigned long long status = 0;
+    HostCall call((hipStream_t)stream);
+    hipStream_t s = call.s;
+    PoolBuf status_buf(64, device); // (goes back behind finish()'s wait)
+    unsigned long long *d_status = status_buf.get<unsigned long long>();
+    if (!d_status) return set_err(KNN_ERR_HIP, "pool_ranges_dev: out of device memory");
     auto enqueue = [&]() -> int {
         HIP_TRY(hipMemsetAsync(d_status, 0xFF, 8, s));
         hipLaunchKernelGGL(pool_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, starts_dev, stops_dev, n, rows, d_status);
         HIP_TRY(hipGetLastError());
-        EVAL_TRY(ev.mark(s));
+        EVAL_TRY(call.ev.mark(s));
         const PoolArgs a = {x_dev, rows, row_stride, (int)d, starts_dev, stops_dev, nullptr, out_dev};
         EVAL_TRY(pool_launch(pl, dtype, flags & KNN_POOL_NORMALIZE, a, s));
-        EVAL_TRY(ev.mark(s));
+        EVAL_TRY(call.ev.mark(s));
         HIP_TRY(hipMemcpyAsync(&status, d_status, 8, hipMemcpyDeviceToHost, s));
-        EVAL_TRY(ev.mark(s)); // the result's event: the status word is read behind it
         return 0;
     };
-    rc = enqueue();
-    // (always: the copy already queued writes this frame's status word, and d_status goes back to the pool)
-    const hipError_t e = ev.ev.empty() ? hipStreamSynchronize(s) : hipEventSynchronize(ev.ev.back());
-    const hipError_t e2 = rc ? hipStreamSynchronize(s) : hipSuccess;
-    g_pool.give(d_status, got, device);
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return set_err(KNN_ERR_HIP, std::string("pool_ranges_dev: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    // (finish() always waits: the copy already queued writes this frame's status word)
+    float kernel_ms = 0.0f; // (g_pool_ms is the last SUCCESSFUL call's)
+    if ((rc = call.finish("pool_ranges_dev", enqueue(), &kernel_ms, 1))) return rc;
     if (status != ~0ull)
         return set_err(KNN_ERR_INVALID, "pool_ranges_dev: range " + std::to_string(status) + " is not 0 <= start < stop <= rows with stop - start < 2^24");
     g_pool_ms[0] = g_pool_ms[2] = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&g_pool_ms[1], ev.ev[0], ev.ev[1]));
+    g_pool_ms[1] = kernel_ms;
     return 0;
 }
 
 // everything of knn_pool_ranges that is enqueued; the caller waits for both streams whatever this returns.
 // s: the kernels and the download; up: the uploads (the copy pipeline's host-to-device stream, or s itself)
 static int pool_host_enqueue(const char *x, int dtype, int d, const std::vector<int64_t> &order, const std::vector<PoolChunk> &chunks, const int64_t *starts,
-                             const int64_t *stops, int64_t n, int flags, float *out, EvalBufs &bufs, hipStream_t s, CopyPipes *cp, RefineEvents &ev_up,
-                             RefineEvents &ev_k, RefineEvents &ev_down, std::vector<int64_t> &meta)
+                             const int64_t *stops, int64_t n, int flags, float *out, EvalBufs &bufs, hipStream_t s, CopyPipes *cp, EventList &ev_up,
+                             EventList &ev_k, EventList &ev_down, std::vector<int64_t> &meta)
 {
     const size_t esz = dtype ? 2 : 4, row_bytes = (size_t)d * esz;
     int64_t max_rows = 0, max_count = 0;
@@ -299,17 +294,6 @@ static int pool_host_enqueue(const char *x, int dtype, int d, const std::vector<
     return 0;
 }
 
-static int pool_sum_pairs(const RefineEvents &ev, float *ms)
-{
-    *ms = 0.0f;
-    for (size_t i = 0; i + 1 < ev.ev.size(); i += 2) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, ev.ev[i], ev.ev[i + 1]));
-        *ms += t;
-    }
-    return 0;
-}
-
 extern "C" int knn_pool_ranges(const void *x_host, int32_t dtype, int64_t rows, int32_t d, const int64_t *starts_host, const int64_t *stops_host, int64_t n,
                                int32_t flags, float *out_host)
 {
@@ -326,21 +310,16 @@ extern "C" int knn_pool_ranges(const void *x_host, int32_t dtype, int64_t rows, 
     pool_assign_chunks(starts_host, stops_host, n, pool_chunk_rows((size_t)d * (dtype ? 2 : 4)), order, chunks);
     // the uploads ride the copy pipeline's host-to-device stream when no host search holds it and there is something to
     // overlap; the kernels and the download run on a stream of this call's
-    PipeLease lease;
-    if ((rc = lease_pipes(g_device, chunks.size() > 1, lease))) return rc;
-    hipStream_t s = g_streams.take(g_device);
-    if (!s) return set_err(KNN_ERR_HIP, "pool_ranges: no stream");
-    EvalBufs bufs; // (freed behind the waits below)
-    RefineEvents ev_up, ev_k, ev_down;
-    rc = pool_host_enqueue((const char *)x_host, dtype, d, order, chunks, starts_host, stops_host, n, flags, out_host, bufs, s, lease.cp, ev_up, ev_k, ev_down, meta);
-    // (always: copies already queued read and write the caller's arrays)
-    const hipError_t e1 = lease.cp ? hipStreamSynchronize(lease.cp->h2d) : hipSuccess, e2 = hipStreamSynchronize(s);
-    g_streams.give(g_device, s);
-    if (rc) return rc;
-    if (e1 != hipSuccess || e2 != hipSuccess) return set_err(KNN_ERR_HIP, std::string("pool_ranges: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    EVAL_TRY(pool_sum_pairs(ev_up, &g_pool_ms[0]));
-    EVAL_TRY(pool_sum_pairs(ev_k, &g_pool_ms[1]));
-    EVAL_TRY(pool_sum_pairs(ev_down, &g_pool_ms[2]));
+    HostCall call(g_device);
+    if (!call.s) return set_err(KNN_ERR_HIP, "pool_ranges: no stream");
+    if ((rc = call.lease(g_device, chunks.size() > 1))) return rc;
+    EventList ev_k, ev_down; // (call.ev: the uploads')
+    rc = pool_host_enqueue((const char *)x_host, dtype, d, order, chunks, starts_host, stops_host, n, flags, out_host, call.bufs, call.s, call.pipes.cp, call.ev,
+                           ev_k, ev_down, meta);
+    if ((rc = call.finish("pool_ranges", rc, nullptr, 0))) return rc;
+    EVAL_TRY(sum_pairs(call.ev, &g_pool_ms[0]));
+    EVAL_TRY(sum_pairs(ev_k, &g_pool_ms[1]));
+    EVAL_TRY(sum_pairs(ev_down, &g_pool_ms[2]));
     return 0;
 }
 

@@ -342,7 +342,7 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
     // every buffer of the plan, by the plan's own sizes (plan_rank; plan_check walks them)
     const auto t_alloc = std::chrono::steady_clock::now();
     EvalBufs bufs;
-    RefineEvents ev;
+    EventList ev;
     EVAL_ALLOC(d_scores, F *, pl.scores_bytes);
     uint8_t *d_correct = nullptr;
     if (pl.correct_bytes) {

@@ -107,41 +107,26 @@ __global__ __launch_bounds__(256, 2) void refine_rescore_kernel(RefineParams p)
 }
 
 // ---- host -------------------------------------------------------------------------------
-// HIP events of one call: three per batch -- in front of the rescore launch, between it and the selection, behind it
-struct RefineEvents {
-    std::vector<hipEvent_t> ev;
-    ~RefineEvents()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+// The events of one call (refine_batch): three per batch -- in front of the rescore launch, between it and the selection,
+// behind it.  After the stream has drained: the batches' times summed into ms[0] (rescore), ms[1] (selection)
+static int refine_sum_ms(const EventList &ev, float *ms)
+{
+    ms[0] = ms[1] = 0.0f;
+    for (size_t i = 0; i + 2 < ev.ev.size(); i += 3) {
+        float a = 0, b = 0;
+        HIP_TRY(hipEventElapsedTime(&a, ev.ev[i], ev.ev[i + 1]));
+        HIP_TRY(hipEventElapsedTime(&b, ev.ev[i + 1], ev.ev[i + 2]));
+        ms[0] += a;
+        ms[1] += b;
     }
-    int mark(hipStream_t s)
-    {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        HIP_TRY(hipEventRecord(e, s));
-        return 0;
-    }
-    // after the stream has drained: the batches' times summed into ms[0] (rescore), ms[1] (selection)
-    int sum(float *ms)
-    {
-        ms[0] = ms[1] = 0.0f;
-        for (size_t i = 0; i + 2 < ev.size(); i += 3) {
-            float a = 0, b = 0;
-            HIP_TRY(hipEventElapsedTime(&a, ev[i], ev[i + 1]));
-            HIP_TRY(hipEventElapsedTime(&b, ev[i + 1], ev[i + 2]));
-            ms[0] += a;
-            ms[1] += b;
-        }
-        return 0;
-    }
-};
+    return 0;
+}
 
 // the candidates labels_dev [m][kb] of the padded queries xq_dev [m][dp] (both on the device) -> the best k of each
 // query in D_dev / I_dev [m][k], on stream s.  The caller holds flat->mu and has checked the labels' range or got them
 // from a search over the same number of rows.
 static int refine_batch(knn_index_s *flat, const float *xq_dev, const int64_t *labels_dev, int64_t m, int kb, int k, float *D_dev,
-                        int64_t *I_dev, hipStream_t s, RefineEvents &ev)
+                        int64_t *I_dev, hipStream_t s, EventList &ev)
 {
     if (flat->ws_rfkeys.ensure((size_t)m * kb * 8, flat->done, s)) return set_err(KNN_ERR_HIP, "refine: out of device memory");
     RefineParams p;
@@ -205,7 +190,7 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
         h->ws_rfI.ensure((size_t)mb * kb * 8, h->done, s) || h->ws_rfD.ensure((size_t)mb * k * 4, h->done, s) ||
         h->ws_rfI2.ensure((size_t)mb * k * 8, h->done, s))
         return set_err(KNN_ERR_HIP, "flat_refine: out of device memory");
-    RefineEvents ev;
+    EventList ev;
     for (int64_t b0 = 0; b0 < nq; b0 += QB) {
         const int64_t m = std::min(QB, nq - b0);
         HIP_TRY(hipMemcpyAsync(h->ws_rfq.p, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
@@ -224,7 +209,7 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
         HIP_TRY(hipMemcpyAsync(I_host + b0 * k, h->ws_rfI2.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    return ev.sum(h->refine_ms);
+    return refine_sum_ms(ev, h->refine_ms);
 }
 
 // measurement (tools/refine_probe.py): HIP-event milliseconds of the last successful knn_flat_refine /
