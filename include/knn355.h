@@ -470,6 +470,59 @@ int knn_eval_pr_curve(const uint8_t *is_correct, const float *scores, int64_t nq
                       const int64_t *totals, const double *thresholds, int32_t nthr,
                       double *precision_out, double *recall_out,
                       int64_t *selected_out, int64_t *tp_out, int64_t *empty_out);
+/* pfam/proteins.py:689-729, the accuracy per score bucket: how many cells of (is_correct, scores) fall into each of nb
+ * score buckets, and how many of those are correct.  All pointers are host pointers.  scores is [nq][k], float32
+ * (key_type KNN_RANK_F32) or float64 (KNN_RANK_F64), is_correct uint8 [nq][k], lo and hi [nb], both outputs int64 [nb].
+ *   cells       only columns 0 .. limit-1 of each row are read (1 <= limit <= k); a cell is correct when its
+ *               is_correct byte is non-zero
+ *   membership  a cell with score s is in bucket b iff lo[b] < (double)s && (double)s <= hi[b], both comparisons in double,
+ *               as numpy compares a float32 array with the float64 scalars the reference's loop iterates over.  A NaN
+ *               score is in no bucket; +-inf and -0.0 follow the comparisons.
+ *   edges       two arrays, not nb + 1 edges: the reference's lower edge is linspace(0, 1 - 1/s, s)[b] and its upper edge
+ *               that + 1/s, and the upper edge of a bucket and the lower edge of the next often differ in the last bit
+ *               (at s = 300: 28 pairs overlap, 62 leave a gap).  A cell may therefore be in two buckets or in none, and
+ *               the last upper edge may lie one ulp below 1.0.  lo and hi are each non-decreasing and free of NaN, with
+ *               lo[b] <= hi[b]; equal neighbours and lo[b] == hi[b] (an empty bucket) are legal.  With that the buckets
+ *               of a cell are h .. a - 1, a = #{i : lo[i] < s}, h = #{i : hi[i] < s}: two binary searches.
+ *   outputs     count_out[b] = the number of member cells, correct_out[b] = the number of correct member cells (both
+ *               required).  Integers only: the result does not depend on the launch shape, the slab size or the order of
+ *               the atomics.
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: an unknown key_type; nq < 1;
+ * k < 1, k > INT32_MAX, limit < 1, limit > k; nb < 1 or nb > 4096; a null pointer; a NaN edge; lo or hi decreasing;
+ * lo[b] > hi[b] for some b.
+ * Slabs: as above (KNN355_EVAL_SLAB_ROWS included), and at most 2^31 cells each; the counters stay on the device across
+ * the slabs.
+ * Hot path: bucket_hist_kernel (buckets.inc), one wave per row: the two searches over the edges in LDS, packed 64-bit
+ * LDS atomics into two threshold histograms (KNN355_BUCKET_AGG=1: equal (a, h) pairs merged inside the wave first), integer
+ * atomicAdd into global counters; the two prefix sums over nb + 1 words and their difference are host work. */
+int knn_eval_bucket_counts(const void *scores, int32_t key_type, const uint8_t *is_correct, int64_t nq, int64_t k,
+                           int64_t limit, const double *lo, const double *hi, int32_t nb,
+                           int64_t *count_out, int64_t *correct_out);
+/* pfam/proteins.py:502-507 make_accuracy_over_hit, the mean fraction of a query's homologues found after j hits, and the
+ * per-query counts behind proteins.py:476-496 (recall_per_query, loss_aligning).  All pointers are host pointers.
+ * is_correct is uint8 [nq][k], totals int64 [nq] (the number of homologues of each query).
+ *   C(q,j)      the number of correct cells (non-zero bytes) of row q in columns 0 .. j; only columns 0 .. limit-1 are read
+ *   t(q,j)      (double)C(q,j) / (double)totals[q], IEEE double, correctly rounded
+ *   mean        S(j) starts at +0.0 and adds t(0,j), t(1,j), ... in row order; mean_out[j] = S(j) / (double)nq, double
+ *               [limit], required.  This is the order numpy uses for mean(axis=0) of a C-ordered 2-D array, so for
+ *               limit >= 2 the result has the bits of the reference's expression.  (For limit = 1 numpy collapses the
+ *               array to one dimension and sums pairwise; the contract stays "row order".)
+ *   rows        row_correct_out[q] = C(q, limit-1), int64 [nq], may be NULL
+ *   columns     column_correct_out[j] = the sum over q of C(q,j), int64 [limit], may be NULL
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: nq < 1; k < 1, k > INT32_MAX,
+ * limit < 1, limit > k; a null is_correct, totals or mean_out; totals[q] < 1 for some q.
+ * Slabs: as above (KNN355_EVAL_SLAB_ROWS included), and at most 256 MiB of t each; the running S stays on the device and
+ * is carried across the slabs in row order.  No floating-point atomics.
+ * Hot path (buckets.inc): hit_terms_kernel, one wave per row, C by ballot and popcount over groups of 64 columns, t into
+ * a [slab rows][limit] scratch, the row counts, the correct cells per column (whose prefix sum is the column sums);
+ * hit_fold_kernel, one workgroup per 32 columns, carries tiles of the scratch into LDS one tile ahead while 32 threads
+ * add the rows to S in order: only the adds are serial. */
+int knn_eval_hit_curve(const uint8_t *is_correct, int64_t nq, int64_t k, int64_t limit, const int64_t *totals,
+                       double *mean_out, int64_t *row_correct_out, int64_t *column_correct_out);
+/* measurement (tools/bench_buckets.py): milliseconds by HIP events of the calling thread's last successful
+ * knn_eval_bucket_counts (counts_ms[3]) and knn_eval_hit_curve (curve_ms[3]): uploads, kernels, downloads, each summed
+ * over the slabs. */
+int knn_eval_buckets_last_ms(float *counts_ms /* [3] */, float *curve_ms /* [3] */);
 /* One stable order over every hit of a result set, with look-ups: pfam/pfam.py:561-598 (the dataset-wide precision-recall
  * curve), the cumulative curves is_correct[argsort(key)].cumsum() (cath/cath.py:656-675, 738-771; pfam/pfam.py:166-177,
  * 213-236) and the order statistics behind numpy.quantile(scores[:, :limit], ...) (pfam/proteins.py:626-648).  All

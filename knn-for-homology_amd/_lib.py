@@ -133,6 +133,10 @@ def _declare(L):
         "knn_eval_sets_matrix":(c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
         "knn_eval_pr_curve": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+        "knn_eval_bucket_counts": (c_int32, [c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_void_p,
+                                             c_void_p]),
+        "knn_eval_hit_curve": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "knn_eval_buckets_last_ms": (c_int32, [f32p, f32p]),
         "knn_eval_rank": (c_int32, [c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
         "knn_last_rank_info": (c_int32, [POINTER(c_int32), POINTER(c_int32), i64p, f32p]),

@@ -28,6 +28,7 @@
 //   assemble.inc                    protein-level hits from slice searches (knn_eval_assemble).
 //   slices_eval.inc                 slice-level correctness and AUC1 of slice searches (knn_eval_slice_annotate, knn_eval_slices).
 //   pr_curve.inc                    the precision-recall threshold sweep over (is_correct, scores) (knn_eval_pr_curve).
+//   buckets.inc                     accuracy per score bucket and the accuracy-over-hits curve (knn_eval_bucket_counts, knn_eval_hit_curve).
 //   fuse.inc                        the two hit-list fusions of the results scripts: prefix-then-fill, sorted union (knn_eval_fuse).
 //   pca.inc                         mean, covariance (fp32 MFMA) and projection behind decomposition.PCA (knn_pca_moments, knn_pca_project).
 //   kde.inc                         1-D Gaussian kernel density estimates behind density.gaussian_kde (knn_kde_stats, knn_kde_eval).
@@ -5669,6 +5670,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "assemble.inc"
 #include "slices_eval.inc"
 #include "pr_curve.inc"
+#include "buckets.inc"
 #include "rank.inc"
 #include "bootstrap.inc"
 #include "pca.inc"

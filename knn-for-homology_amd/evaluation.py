@@ -15,6 +15,9 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   evaluate_slices         pfam/slices/slices.py:101-142 (evaluate: slice-level is_correct, is_ignore and AUC1)
   compute_correctness_array  pfam/proteins.py:201-207 (per-hit "is this a homologue" matrix)
   precision_recall_curve     pfam/proteins.py:626-648 (mean precision / recall per query over score thresholds)
+  bucketed_accuracy          pfam/proteins.py:689-729 (accuracy and its standard error per cosine-similarity bucket)
+  accuracy_over_hits         pfam/proteins.py:502-507 (make_accuracy_over_hit: mean fraction of homologues found after j hits)
+  recall_per_query           pfam/proteins.py:476-496 (recall over the first 300 hits, per query)
   ranked_precision_recall    pfam/pfam.py:570-583 (the dataset-wide precision-recall curve over every hit, ranked at once)
   ranked_cumulative          cath/cath.py:656-675, 738-771; pfam/pfam.py:166-177, 213-236 (is_correct[argsort(key)].cumsum())
   score_quantiles            pfam/proteins.py:626-648 (numpy.quantile over every score: precision_recall_curve's thresholds)
@@ -23,7 +26,7 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
 """
 from collections import Counter, namedtuple
 from itertools import groupby
-from typing import Dict, Iterable, List, Sequence, Set, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Sequence, Set, Tuple
 
 import numpy as np
 from numpy import ndarray
@@ -551,6 +554,133 @@ def precision_recall_curve(correct: ndarray, scores: ndarray, correct_totals: nd
     if want_counts:
         return back(recall), back(precision), thresholds, tuple(back(c) for c in counts)
     return back(recall), back(precision), thresholds
+
+
+# ---- accuracy per score bucket, accuracy over hits: knn_eval_bucket_counts, knn_eval_hit_curve (include/knn355.h) ------
+class BucketedAccuracy(NamedTuple):
+    """bucketed_accuracy's result, one entry per bucket: the edges (lo, hi], the member cells, the correct ones, and their
+    mean and standard error of the mean (NaN where there is nothing to divide by)."""
+    lo: ndarray
+    hi: ndarray
+    count: ndarray
+    correct: ndarray
+    precision: ndarray
+    sem: ndarray
+
+    def reference_arrays(self):
+        """(precision, sem) of the non-empty buckets only, in order: the two arrays the reference builds by `continue`-ing
+        over empty buckets (t5_quantized_precision, t5_quantized_precision_sem)."""
+        keep = self.count > 0
+        return self.precision[keep], self.sem[keep]
+
+
+def _correct_bytes(correct, who):
+    correct = np.asarray(correct)
+    if correct.ndim != 2:
+        raise ValueError(f"{who}: correct must be 2-D")
+    return np.ascontiguousarray(correct != 0 if correct.dtype != np.bool_ else correct).view(np.uint8)
+
+
+def _limit(limit, k):
+    limit = int(limit)
+    if limit < 1 or limit > k:
+        raise ValueError(f"limit must be in [1, k = {k}], not {limit}")
+    return limit
+
+
+def bucketed_accuracy(correct: ndarray, scores: ndarray, limit: int = 300, smoothness: int = 300, lo: ndarray = None,
+                      hi: ndarray = None) -> BucketedAccuracy:
+    """The reference's cosine_bucketed_accuracy loop (pfam/proteins.py:689-729) as one GPU pass -> BucketedAccuracy.
+
+    correct bool / uint8 [nq, k] (compute_correctness_array), scores float32 or float64 [nq, k] (anything else is taken as
+    float64); only the first `limit` columns count.  A cell is in bucket b when lo[b] < score <= hi[b], compared in
+    double.  By default lo = numpy.linspace(0, 1 - (1 / smoothness), smoothness) and hi = lo + (1 / smoothness), the
+    reference's own expressions: neighbouring edges then differ in the last bit here and there, so that a cell can be in
+    two buckets or in none, and a score of exactly 1.0 can miss the last bucket -- as in the reference.  Edges of one's own
+    are each non-decreasing, free of NaN and lo <= hi, 1 .. 4096 of them.
+    precision = correct / count in float64, the bits of the reference's bool.mean(), NaN where count == 0.  sem =
+    sqrt(c (n - c) / (n (n - 1))) / sqrt(n) from the two integers, NaN for n < 2: scipy.stats.sem of a boolean array in
+    closed form, equal to scipy's pairwise-summed value within a few ulp, not bit for bit."""
+    correct = _correct_bytes(correct, "bucketed_accuracy")
+    scores = np.asarray(scores)
+    scores = np.ascontiguousarray(scores, np.float32 if scores.dtype == np.float32 else np.float64)
+    nq, k = correct.shape
+    if scores.shape != correct.shape:
+        raise ValueError(f"scores {scores.shape} and correct {correct.shape} must have the same shape")
+    if nq < 1:
+        raise ValueError("bucketed_accuracy needs one query at least")
+    limit = _limit(limit, k)
+    if lo is None and hi is None:
+        lo = np.linspace(0, 1 - (1 / smoothness), smoothness)
+        hi = lo + (1 / smoothness)
+    elif lo is None or hi is None:
+        raise ValueError("give both lo and hi, or neither")
+    lo = np.ascontiguousarray(lo, np.float64)
+    hi = np.ascontiguousarray(hi, np.float64)
+    if lo.ndim != 1 or lo.shape != hi.shape or not 1 <= lo.size <= 4096:
+        raise ValueError("lo and hi must be 1-D of one length, with 1 .. 4096 entries")
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("edges must not hold NaN")
+    if (np.diff(lo) < 0).any() or (np.diff(hi) < 0).any() or (lo > hi).any():
+        raise ValueError("lo and hi must each be non-decreasing, with lo <= hi")
+    nb = lo.size
+    count = np.empty(nb, np.int64)
+    right = np.empty(nb, np.int64)
+    _lib.check(_lib.lib().knn_eval_bucket_counts(scores.ctypes.data, 1 if scores.dtype == np.float64 else 0, correct.ctypes.data, nq, k,
+                                                 limit, lo.ctypes.data, hi.ctypes.data, nb, count.ctypes.data, right.ctypes.data))
+    n = count.astype(np.float64)
+    c = right.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision = c / n
+        sem = np.sqrt(c * (n - c) / (n * (n - 1))) / np.sqrt(n)
+    precision[count == 0] = np.nan
+    sem[count < 2] = np.nan
+    return BucketedAccuracy(lo, hi, count, right, precision, sem)
+
+
+def _hit_curve(correct, correct_totals, limit, who):
+    correct = _correct_bytes(correct, who)
+    nq, k = correct.shape
+    if nq < 1:
+        raise ValueError(f"{who} needs one query at least")
+    limit = _limit(limit, k)
+    totals = _per_query(correct_totals, np.int64, nq, "correct_totals")
+    if (totals < 1).any():
+        raise ValueError("correct_totals must be positive: the curve divides by them")
+    mean = np.empty(limit, np.float64)
+    rows = np.empty(nq, np.int64)
+    _lib.check(_lib.lib().knn_eval_hit_curve(correct.ctypes.data, nq, k, limit, totals.ctypes.data, mean.ctypes.data, rows.ctypes.data, None))
+    return mean, rows, totals
+
+
+def accuracy_over_hits(correct: ndarray, correct_totals: ndarray, limit: int = 300, want_rows: bool = False):
+    """The reference's make_accuracy_over_hit(correct[:, :limit]) (pfam/proteins.py:502-507) -> float64 [limit]: entry j is
+    the mean over the queries of (correct hits among the first j + 1) / correct_totals.
+
+    correct bool / uint8 [nq, k], correct_totals [nq], at least 1 each.  The mean is the sum of the quotients in row order
+    over nq, the order numpy takes for mean(axis=0) of a 2-D array: for limit >= 2 the result has the bits of the
+    reference's expression.  For limit = 1 numpy collapses the array and sums pairwise, so there the last bits can differ;
+    the order here stays the row order.  want_rows=True appends the int64 [nq] number of correct hits per query among the
+    first `limit` (recall_per_query's numerator)."""
+    mean, rows, _ = _hit_curve(correct, correct_totals, limit, "accuracy_over_hits")
+    return (mean, rows) if want_rows else mean
+
+
+def recall_per_query(correct: ndarray, correct_totals: ndarray, limit: int = 300) -> ndarray:
+    """correct[:, :limit].sum(axis=1) / correct_totals (pfam/proteins.py:478) -> float64 [nq]: the counts from the device,
+    the division numpy's own, so the bits are the reference's.  Its mean and scipy.stats.sem stay with the caller."""
+    _, rows, _ = _hit_curve(correct, correct_totals, limit, "recall_per_query")
+    return rows / np.asarray(correct_totals)
+
+
+def last_buckets_ms():
+    """Milliseconds by HIP events of this thread's last bucketed_accuracy and last accuracy_over_hits / recall_per_query:
+    {"bucket_counts": {upload_ms, kernel_ms, download_ms}, "hit_curve": {...}}."""
+    from ctypes import c_float
+    a, b = (c_float * 3)(), (c_float * 3)()
+    _lib.check(_lib.lib().knn_eval_buckets_last_ms(a, b))
+    names = ("upload_ms", "kernel_ms", "download_ms")
+    return {"bucket_counts": dict(zip(names, a)), "hit_curve": dict(zip(names, b))}
 
 
 # ---- one stable order over every hit: knn_eval_rank (include/knn355.h) ------------------------------------------------
