@@ -253,7 +253,13 @@ knn_handle knn_hnsw_storage(knn_hnsw_handle h);
 void knn_hnsw_free(knn_hnsw_handle h);
 /* graph tables for write_index / read_index: levels[n], offsets[n+1], nbrs[nslots]
  * (-1 = empty), cum_nb[nlevels_tab] (slots below each level), assign_probas.  A list ends at its
- * first -1 (FAISS's walk stops there): what an imported level-0 list holds behind one is dropped */
+ * first -1 (FAISS's walk stops there): what an imported level-0 list holds behind one is dropped.
+ * knn_hnsw_graph_import takes the tables of a graph whose storage rows are already in place
+ * (knn_hnsw_storage + knn_flat_add) into an EMPTY graph.  It returns KNN_ERR_INVALID, and leaves
+ * the graph empty so that corrected tables can follow, when: a level is outside the level table;
+ * nslots is not what the levels add up to; an id is outside [-1, ntotal); (entry_point, max_level)
+ * is not a node and its top level; or a list at level l >= 1 names, in any slot, a node whose top
+ * level is below l -- a walk at level l reads that node's level-l list, which it does not own. */
 int knn_hnsw_graph_sizes(knn_hnsw_handle h, int64_t *ntotal, int64_t *nslots, int32_t *nlevels_tab);
 int knn_hnsw_graph_export(knn_hnsw_handle h, int32_t *levels, int64_t *offsets, int32_t *nbrs,
                           int32_t *cum_nb, double *assign_probas);

@@ -2658,20 +2658,32 @@ extern "C" int knn_hnsw_graph_import(knn_hnsw_s *H, int64_t ntotal, const int32_
     HnswGraph &g = H->g;
     if (g.ntotal() != 0) return set_err(KNN_ERR_INVALID, "hnsw_graph_import: graph not empty");
     if (ntotal != H->flat->ntotal) return set_err(KNN_ERR_INVALID, "hnsw_graph_import: storage holds a different number of rows");
+    // every refusal from here on leaves the graph empty
+    auto refuse = [&](const char *why) {
+        const int M = g.M;
+        g = HnswGraph();
+        g.init(M);
+        return set_err(KNN_ERR_INVALID, why);
+    };
     for (int64_t i = 0; i < ntotal; i++) {
-        if (levels[i] < 0 || levels[i] + 1 >= (int)g.cum_nb.size()) return set_err(KNN_ERR_INVALID, "hnsw_graph_import: bad level");
+        if (levels[i] < 0 || levels[i] + 1 >= (int)g.cum_nb.size()) return refuse("hnsw_graph_import: bad level");
         g.append_node(levels[i]);
     }
-    if ((int64_t)g.nbrs.size() != nslots) return set_err(KNN_ERR_INVALID, "hnsw_graph_import: neighbour table size mismatch");
+    if ((int64_t)g.nbrs.size() != nslots) return refuse("hnsw_graph_import: neighbour table size mismatch");
     for (int64_t i = 0; i < nslots; i++) {
-        if (nbrs[i] >= ntotal || nbrs[i] < -1) {
-            const int M = g.M;
-            g = HnswGraph();
-            g.init(M);
-            return set_err(KNN_ERR_INVALID, "hnsw_graph_import: neighbour id out of range");
-        }
+        if (nbrs[i] >= ntotal || nbrs[i] < -1) return refuse("hnsw_graph_import: neighbour id out of range");
         g.nbrs[i] = nbrs[i] < 0 ? HNSW_EMPTY : (uint32_t)nbrs[i];
     }
+    // a walk at level l >= 1 reads list(node, l) of every node it is handed there: a node named at a level it does not have
+    // owns no such slots, and the read would run into the next node's (past the table's end for the last node).  Every slot
+    // counts, the ones behind a hole too: construction appends to these lists.
+    for (int64_t i = 0; i < ntotal; i++)
+        for (int l = 1; l <= g.levels[i]; l++) {
+            const uint32_t *ul = g.list(i, l);
+            for (int c = 0; c < g.nb_neighbors(l); c++)
+                if (ul[c] != HNSW_EMPTY && g.levels[ul[c]] < l)
+                    return refuse("hnsw_graph_import: an upper-level list names a node that does not have that level");
+        }
     // (an imported list may have holes: the fill is the position of the first one, as in FAISS, whose walk stops at the
     // first -1.  What lies behind it is not part of the list and is dropped here: the device beam reads a level-0 list as
     // one whole row and tells links from empty slots by value, so ids left behind a hole would be walked on the device and
@@ -2686,12 +2698,8 @@ extern "C" int knn_hnsw_graph_import(knn_hnsw_s *H, int64_t ntotal, const int32_
     }
     // the walk starts at (entry_point, max_level): both must describe a node of this graph
     const bool empty_ok = ntotal == 0 && entry_point == -1;
-    if (!empty_ok && (entry_point < 0 || entry_point >= ntotal || max_level != g.levels[entry_point])) {
-        const int M = g.M;
-        g = HnswGraph();
-        g.init(M);
-        return set_err(KNN_ERR_INVALID, "hnsw_graph_import: entry point / max level do not match the level table");
-    }
+    if (!empty_ok && (entry_point < 0 || entry_point >= ntotal || max_level != g.levels[entry_point]))
+        return refuse("hnsw_graph_import: entry point / max level do not match the level table");
     g.max_level = ntotal ? max_level : -1;
     g.entry = entry_point;
     H->nbr0_dirty = true;

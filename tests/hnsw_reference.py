@@ -1,5 +1,5 @@
-"""Plain host reference for the HNSW search, for tests/test_hnsw_exact_gpu.py, tests/test_hnsw_gpu.py and
-tests/test_hnsw_reference.py.  NumPy and the CPU oracle only: nothing here touches the library under test.
+"""Plain host reference for the HNSW search, for tests/test_hnsw_exact_gpu.py, tests/test_hnsw_entry_exact_gpu.py,
+tests/test_hnsw_gpu.py and tests/test_hnsw_reference.py.  NumPy and the CPU oracle only: nothing here touches the library under test.
 
 A beam search can be checked exactly without restating its expansion order: with ef >= the number of nodes reachable at level
 0 from the entry nodes the beam never fills, nothing is pruned, every reachable node is scored, and (keep == ef) every one of
@@ -16,6 +16,17 @@ expected                 the oracle's flat search over the rows x[reach], reach 
 assert_output_contract   what ANY HNSW result must satisfy, approximate ones included: ids in [0, n) or -1, padding only at
                          the end and with the pad score, no id twice, (score, id) keys strictly ordered, and every returned
                          score carries exactly the contract's bits for its (query, id)
+
+Which level-0 nodes a search ENTERS at (tests/test_hnsw_entry_exact_gpu.py: graphs whose level 0 is disjoint islands, so
+that the reachable set names the entries):
+
+tables                   the tables knn_hnsw_graph_import takes, for a graph with levels above 0
+scores                   float64 scores of one query against rows, smaller is better (-dot / the sum of squared differences)
+descend                  the greedy descent through the levels above 0, as the host walk runs it
+coarse_entries           the c best of the nodes above level 0 under (score, lower id); None where the descent applies
+entry_reach              the entries -> the sorted union of their level-0 islands
+margins                  real-valued rows: every comparison a rule makes, in float64, against the worst-case rounding bound
+                         of the arithmetic that makes it
 """
 import numpy as np
 
@@ -142,3 +153,136 @@ def assert_output_contract(D, I, x, q, metric, n, oracle):
     wrong = np.flatnonzero(D[valid].view(np.uint32) != want.view(np.uint32))
     assert wrong.size == 0, (f"{wrong.size} of {want.size} returned scores do not carry the contract's bits, first (query, id, got, want): "
                              f"{[(int(qidx[p]), int(I[valid][p]), float(D[valid][p]), float(want[p])) for p in wrong[:4]]}")
+
+
+# ---- the entry rules ------------------------------------------------------------------------------------------------
+COARSE_MIN = 64  # nodes above level 0 from which the coarse rule applies
+
+
+def tables(levels, lists, M):
+    """lists[i][l]: the neighbour ids of node i at level l as given (-1 = empty slot, holes allowed), l = 0 .. levels[i]
+    -> (levels int32 [n], offsets int64 [n + 1], nbrs int32 [offsets[n]]).  A node of top level L owns cum[L + 1] slots,
+    cum = [0, 2M, 3M, 4M, ...]: level 0 at [off, off + 2M), level l >= 1 at [off + cum[l], off + cum[l + 1])."""
+    levels = np.asarray(levels, np.int32)
+    n = len(levels)
+    assert len(lists) == n and (levels >= 0).all()
+    cum = [0] + [(l + 2) * M for l in range(int(levels.max(initial=0)) + 1)]
+    offsets = np.zeros(n + 1, np.int64)
+    offsets[1:] = np.cumsum([cum[int(L) + 1] for L in levels])
+    nbrs = np.full(int(offsets[n]), -1, np.int32)
+    for i in range(n):
+        assert len(lists[i]) == levels[i] + 1, (i, len(lists[i]), int(levels[i]))
+        for l, ids in enumerate(lists[i]):
+            assert len(ids) <= cum[l + 1] - cum[l], (i, l, len(ids))
+            lo = int(offsets[i]) + cum[l]
+            nbrs[lo:lo + len(ids)] = ids
+    return levels, offsets, nbrs
+
+
+def _list(offsets, nbrs, M, i, l):
+    """node i's level-l list up to its first -1"""
+    lo = int(offsets[i]) + (0 if l == 0 else (l + 1) * M)
+    ids = nbrs[lo:lo + (2 * M if l == 0 else M)]
+    holes = np.flatnonzero(ids < 0)
+    return ids[:holes[0]] if holes.size else ids
+
+
+def scores(x, qrow, ids, metric):
+    """float64 [len(ids)]: smaller is better"""
+    y = np.asarray(x, np.float64)[np.asarray(ids, np.int64)]
+    qrow = np.asarray(qrow, np.float64)
+    return -(y @ qrow) if metric == METRIC_INNER_PRODUCT else ((y - qrow[None, :]) ** 2).sum(axis=1)
+
+
+def descend(levels, offsets, nbrs, M, entry_point, max_level, score, walk=None, key=None, trace=None):
+    """The host walk's greedy descent: score the entry; at each level from max_level down to 1 propose the whole list of the
+    current node (up to its first -1), move to the best (score, id) among the proposals if it beats the current (score, id)
+    -- among equal scores the lower id wins, and an equal-score neighbour of lower id REPLACES the current node -- and
+    repeat at the same level; otherwise (an empty list included) go one level down.  -> the node held when level 0 is
+    reached; entry_point itself when max_level == 0.  score(ids) -> float64, smaller is better.
+
+    walk / key are for the tests' wrong rules only: the levels walked instead of max_level .. 1, and the order on
+    (score, id) instead of the tuple order.  trace: a list that receives (current, winner, [the others compared, the
+    current node among them unless it won]) per step."""
+    key = key or (lambda s, i: (s, i))
+    cur = int(entry_point)
+    cur_s = float(score([cur])[0])
+    for level in (range(int(max_level), 0, -1) if walk is None else walk):
+        while True:
+            assert levels[cur] >= level, f"node {cur} (top level {int(levels[cur])}) is walked at level {level}"
+            ids = [int(j) for j in _list(offsets, nbrs, M, cur, level)]
+            best, best_s = cur, cur_s
+            for j, s in zip(ids, score(ids).tolist() if ids else []):
+                if key(s, j) < key(best_s, best):
+                    best, best_s = j, s
+            if trace is not None:
+                trace.append((cur, best, sorted(j for j in set(ids + [cur]) if j != best)))
+            if best == cur:
+                break
+            cur, cur_s = best, best_s
+    return cur
+
+
+def ports_of(levels):
+    """the nodes above level 0, ascending: the rows of the coarse index, in its order"""
+    return np.flatnonzero(np.asarray(levels) >= 1).astype(np.int64)
+
+
+def coarse_entries(levels, x, qrow, c, metric, key=None, shift=0):
+    """-> int64 [min(c, #ports)]: the best of the nodes with levels >= 1 under (score, lower id), scores in float64; None
+    with fewer than 64 of them (the descent applies then).  key / shift are for the tests' wrong rules only: the order
+    on (score, id), and ports[i + shift] named where ports[i] was chosen."""
+    key = key or (lambda s, i: (s, i))
+    ports = ports_of(levels)
+    if ports.size < COARSE_MIN:
+        return None
+    s = scores(x, qrow, ports, metric).tolist()
+    order = sorted(range(ports.size), key=lambda r: key(s[r], int(ports[r])))[:max(0, min(c, ports.size))]
+    return ports[(np.asarray(order, np.int64) + shift) % ports.size]
+
+
+def entry_reach(offsets, nbrs, M, entries):
+    """sorted int64 array: the union of the level-0 islands of the entries"""
+    n = len(offsets) - 1
+    return reachable(np.zeros(n, np.int32), offsets, nbrs, np.array([0, 2 * M], np.int32), entries)
+
+
+def rounding_bound(x, qrow, ids, metric, coarse=False, bf16=False):
+    """float64 [len(ids)]: the worst-case error of the computed score of (qrow, x[ids]).  One fp32 chain of d terms is off by
+    at most d * 2^-24 * sum |t_i|, t_i = q_i y_i (inner product) or (q_i - y_i)^2 (squared L2: the descent's pair scores).
+    The coarse scan may score squared L2 as |q|^2 + |y|^2 - 2 <q, y> instead: its terms sum to at most
+    sum (|q_i| + |y_i|)^2, which bounds the difference form too, so a coarse score is given that sum.  bf16 copies (both
+    operands rounded to 8 bits, 2^-9 each) add 2^-8 times the same sum."""
+    y = np.asarray(x, np.float64)[np.asarray(ids, np.int64)]
+    a = np.asarray(qrow, np.float64)[None, :]
+    if metric == METRIC_INNER_PRODUCT:
+        terms = np.abs(y * a).sum(axis=1)
+    elif coarse:
+        terms = ((np.abs(y) + np.abs(a)) ** 2).sum(axis=1)
+    else:
+        terms = ((y - a) ** 2).sum(axis=1)
+    return (y.shape[1] * 2.0 ** -24 + (2.0 ** -8 if bf16 else 0.0)) * terms
+
+
+def margins(x, qrow, metric, trace=None, cut=None, bf16=False):
+    """-> the smallest gap / bound over the comparisons that decide a rule's choice for one query, gaps in float64.
+    trace (from descend): at every step the winner against each other node compared there (the current node included).
+    cut: (inside, outside), the coarse scan's chosen ports against the others -- only the worst of the chosen and the best
+    of the others matter, and every pair is bounded by them.  The bound of a comparison is the sum of its two scores'
+    rounding bounds.  A caller asserts the result above 4; inf when nothing is compared."""
+    worst = np.inf
+    pairs = []
+    if trace is not None:
+        pairs += [(w, o, False) for _, w, others in trace for o in others]
+    if cut is not None and len(cut[0]) and len(cut[1]):
+        inside, outside = (np.asarray(c, np.int64) for c in cut)
+        si, so = scores(x, qrow, inside, metric), scores(x, qrow, outside, metric)
+        pairs.append((int(inside[np.argmax(si)]), int(outside[np.argmin(so)]), True))
+    for w, o, coarse in pairs:
+        s = scores(x, qrow, [w, o], metric)
+        b = rounding_bound(x, qrow, [w, o], metric, coarse, bf16 and coarse)
+        assert s[1] >= s[0], (w, o, s.tolist())
+        worst = min(worst, float((s[1] - s[0]) / (b[0] + b[1])) if b.sum() > 0 else (np.inf if s[1] > s[0] else 0.0))
+    return worst
+
+

@@ -10,7 +10,11 @@ a  imported graphs: ring, two components, holes, self/duplicate links, full list
 b  query counts and walker reuse, eager and lazy clearing of the visited bitmaps, search after search
 c  built graphs (strongly connected: asserted), both entry rules
 d  the keep / kmin cut between the beam and the exact re-score, k < ef
-e  approximate searches: the output contract on the full result (no recall figure: tests/test_hnsw_gpu.py has those)"""
+e  approximate searches: the output contract on the full result (no recall figure: tests/test_hnsw_gpu.py has those)
+
+Left open here: WHICH node a search enters at.  Every graph of this file gives the same result from any entry node, so the
+coarse scan and the greedy descent through the upper levels are not checked; tests/test_hnsw_entry_exact_gpu.py pins them,
+on graphs whose level 0 is disjoint islands."""
 import numpy as np
 import pytest
 
@@ -294,7 +298,8 @@ def built_rows(n, d, M, metric, rank=None):
 def test_built_graphs(gpu_faiss, oracle, n, M, d, metric):
     """idx.add builds the graph; efSearch = k = n.  The level-0 graph is strongly connected (asserted), so whichever node
     an entry rule picks, everything is reached: the result is the flat search over all rows -- from the exact scan of the
-    nodes above level 0 (or, with fewer than 64 of them, the greedy descent) and under set_entry(0)"""
+    nodes above level 0 (or, with fewer than 64 of them, the greedy descent) and under set_entry(0).  That the rules pick
+    the RIGHT nodes is what tests/test_hnsw_entry_exact_gpu.py checks."""
     x, q = built_rows(n, d, M, metric), _rows(NQ, d, 41)
     idx = gpu_faiss.IndexHNSWFlat(d, M, metric)
     idx.add(x)
