@@ -579,6 +579,62 @@ int knn_eval_rank(const void *scores, int32_t key_type, int64_t rows, int64_t k,
  * and passes), the scan of the flags, the look-ups with their downloads.  The buffers are freed as the call returns:
  * that time is in no figure. */
 int knn_last_rank_info(int32_t *passes_run, int32_t *passes_skipped, int64_t *tiles, float *ms /* [6] */);
+/* Statistics over contiguous ranges of one stable order: the rolling means of seqvec_search/utils.py:103 (rolling_mean =
+ * numpy.convolve(data, ones(W) / W, "valid"), called on arrays in the order of a key at pfam/pfam.py:247-253,
+ * cath/cath.py:799-813 and 913-919), the equal-count slices of hist_evenly (cath/cath.py:863-875, pfam/pfam.py:282-297)
+ * and the fixed length bins of cath/cath.py:831-857.  All pointers are host pointers.  keys is float32 (KNN_RANK_F32) or
+ * float64 (KNN_RANK_F64) [n], 1 <= n <= 2^31 - 1; values (NULL when m = 0) is uint8 [m][n], 0 <= m <=
+ * KNN_WINDOWS_MAX_COLS, a non-zero byte meaning set.
+ *   order       knn_eval_rank's, of the n keys (rows = n, k = limit = 1): stable, -0.0 == +0.0, every NaN last,
+ *               descending != 0 the order of numpy.argsort(-keys, kind="stable").  order_out int64 [n] (NULL: not wanted)
+ *               receives it.
+ *   C_c(r)      the number of set cells of column c among the ranks 0 .. r, an exact integer; C_c(-1) = 0.
+ *   window W    (window > 0; 0: no rolling means) n - W + 1 outputs per column and for the key:
+ *               value_means_out float64 [m][n - W + 1]: (C_c(i + W - 1) - C_c(i - 1)) / W, one float64 division of two
+ *               exact integers, done on the device: the correctly rounded mean of the window.  (The reference's
+ *               convolution adds W terms of fl(1 / W) in an order its BLAS chooses; it differs in the last bits.)
+ *               key_means_out float64 [n - W + 1], with no subtraction anywhere, so that an infinity or a NaN touches
+ *               only the windows that hold it: the ranked keys, float32 widened to float64 first, are cut into blocks of
+ *               W consecutive ranks, block b = r / W (the last one may be short).  Per block two chains of sequential
+ *               float64 additions: P[r] = the sum of the block's elements from its first rank through r, added in rank
+ *               order, and S[r] = the sum from r through the block's last rank, added from the block's end backwards;
+ *               a chain starts with its first element itself (not 0 + element: a -0.0 stays -0.0).  Output i is
+ *               P[i + W - 1] / W when i % W == 0, else (S[i] + P[i + W - 1]) / W.  This is numpy.cumsum along the
+ *               rows of the [blocks, W] reshape, forward and reversed.
+ *   bins        (nbins > 0) either ranges of ranks, starts and stops int64 [nbins] with 0 <= start <= stop <= n (edges
+ *               NULL), or edges in the keys' type [nbins], finite and ascending (starts and stops NULL; ascending order
+ *               only): bin j holds the keys with edges[j] <= key < edges[j + 1], the last one every key >= edges[nbins -
+ *               1]; NaN keys fall in no bin.  An edge goes through the same order-preserving image as the keys, so start
+ *               = the first rank whose key image is not below the edge's (-0.0 and sub-normals as in the sort), stop = the
+ *               next bin's start, and the last bin stops at the first NaN.  start_out and stop_out int64 [nbins] receive
+ *               the ranks (for ranges: the ones given), counts_out int64 [m][nbins] the exact C_c(stop - 1) - C_c(start
+ *               - 1), key_lo_out and key_hi_out (the keys' type [nbins]) the keys at ranks min(start, n - 1) and
+ *               min(stop, n - 1), bits untouched.  Means and standard errors are the caller's (evaluation.even_bins).
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: an unknown key_type; n outside
+ * [1, 2^31 - 1]; m outside [0, KNN_WINDOWS_MAX_COLS]; window outside [0, n]; nbins outside [0, KNN_WINDOWS_MAX_BINS];
+ * neither a window nor bins; a null keys; m > 0 with a null values; a window with a null key_means_out, or with m > 0 and
+ * a null value_means_out; bins with a null output (counts_out only when m > 0), with both or neither of (starts, stops)
+ * and edges, with edges and descending, with an edge that is not finite or lies below the one before it, or with a range
+ * outside 0 <= start <= stop <= n; starts, stops or edges with nbins = 0.
+ * The whole problem stays on the device for the call; plan_windows in csrc/plan.h has every buffer's bytes, the staging
+ * run of the chains, blocks per run or runs per block and the grids, and the call allocates exactly those.
+ * Hot path (windows.inc): the sort of rank.inc; window_gather_kernel (payload -> position -> one uint32 mask of the m
+ * value bytes, and the key as float64, in rank order); m two-level scans of the masks' bits; window_means_kernel;
+ * window_chain_kernel (runs of 2048 ranked keys staged in LDS per direction, one lane per block and direction walking its
+ * chain, the sum carried across runs when W exceeds one) and window_combine_kernel; window_ranges_kernel (binary
+ * searches of the edges' images, C_c at the range ends, the keys at start and stop).  No workgroup waits on another, no
+ * atomic, plain vector stores only. */
+#define KNN_WINDOWS_MAX_COLS 32
+#define KNN_WINDOWS_MAX_BINS (1 << 20)
+int knn_eval_windows(const void *keys, int32_t key_type, int64_t n, const uint8_t *values, int32_t m, int32_t descending,
+                     int64_t window, double *key_means_out, double *value_means_out, int64_t *order_out,
+                     const int64_t *starts, const int64_t *stops, const void *edges, int64_t nbins, int64_t *start_out,
+                     int64_t *stop_out, int64_t *counts_out, void *key_lo_out, void *key_hi_out);
+/* measurement (tools/bench_windows.py): how the calling thread's last successful knn_eval_windows ran -- the staging run
+ * of the chains in ranks, the blocks that share a run and the runs that make a block (one of the two is 1; both 0 without
+ * a window), and milliseconds ms[8]: on the host's clock the device allocations; by HIP events the uploads, the sort, the
+ * gather with the scans, the chains with their combination, the columns' means, the bins, the downloads. */
+int knn_last_windows_info(int64_t *run, int64_t *blocks_per_run, int64_t *runs_per_block, float *ms /* [8] */);
 /* cath/cath.py:404-438 bootstrap_scores, the replicates behind the "+-" of the accuracy table (:441-458): per method and
  * per resample of the evaluable queries, the raw and the superfamily-normalized top-1 accuracy.  All arrays are host
  * arrays.  is_correct uint8 [nm][n]: row m is method m's verdict for each of the n evaluable queries, a non-zero byte

@@ -140,6 +140,9 @@ def _declare(L):
         "knn_eval_rank": (c_int32, [c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
         "knn_last_rank_info": (c_int32, [POINTER(c_int32), POINTER(c_int32), i64p, f32p]),
+        "knn_eval_windows": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "knn_last_windows_info": (c_int32, [i64p, i64p, i64p, f32p]),
         "knn_eval_bootstrap": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
         "knn_pca_moments": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),

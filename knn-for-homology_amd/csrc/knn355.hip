@@ -5672,6 +5672,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "pr_curve.inc"
 #include "buckets.inc"
 #include "rank.inc"
+#include "windows.inc"
 #include "bootstrap.inc"
 #include "pca.inc"
 #include "fuse.inc"

@@ -754,6 +754,105 @@ static bool plan_rank(int64_t rows, int64_t k, int64_t limit, int key_bytes, boo
     return true;
 }
 
+// ---- windowed statistics over the ranked order (windows.inc) -----------------------
+static const int WINDOW_RUN = 2048;   // ranked keys of one staging run: 16 KiB of float64 per direction, 33 KiB per workgroup with the padding
+static const int WINDOW_CHAINS = 256; // chains of a workgroup at most, one per thread: 128 blocks x 2 directions
+static const int WINDOW_PAD_SHIFT = 5; // LDS index of staged element e: e + (e >> 5) -- one float64 of padding per 32
+
+#if defined(__HIPCC__)
+#define PLAN_HD __host__ __device__
+#else
+#define PLAN_HD
+#endif
+
+// The ranks [lo, hi) of a group [g0, g0 + len) that are staged at step `step` for one direction: forward chains take the
+// group's runs from its first rank up, backward chains from its last rank down.  Steps past the group's end are empty
+// (lo == hi).  window_chain_kernel and windows_check.cpp both call this: the kernel has no layout of its own.
+struct WindowPiece {
+    int64_t lo, hi;
+};
+PLAN_HD static inline WindowPiece window_piece(int64_t g0, int64_t len, int64_t run, int64_t step, int backward)
+{
+    WindowPiece p;
+    const int64_t a = step * run < len ? step * run : len, b = (step + 1) * run < len ? (step + 1) * run : len;
+    if (backward) {
+        p.lo = g0 + len - b;
+        p.hi = g0 + len - a;
+    } else {
+        p.lo = g0 + a;
+        p.hi = g0 + b;
+    }
+    return p;
+}
+
+struct WindowsPlan {
+    RankPlan rank;          // the order: plan_rank(n, 1, 1, key_bytes, no flags, no running count, want_order)
+    int64_t n, window, nout; // window 0: no rolling means (nout 0); else nout = n - window + 1
+    int64_t nbins;          // ranges or edges (0: none)
+    int m, key_bytes;
+    // the chains: blocks of `window` consecutive ranks, two chains (forward P, backward S) per block
+    int64_t nblocks;        // ceil(n / window)
+    int64_t run;            // WINDOW_RUN
+    int64_t blocks_per_run; // window <= run: min(run / window, WINDOW_CHAINS / 2) whole blocks share one staged run; else 1
+    int64_t runs_per_block; // window > run: ceil(window / run) runs make one block, the chain's sum carried across; else 1
+    int64_t group;          // ranks of one workgroup: blocks_per_run * window
+    int64_t chain_grid;     // ceil(n / group) workgroups of 256 threads
+    size_t chain_lds;       // 2 directions x (run + run / 32) float64
+    int64_t scan_blocks;    // blocks of RANK_SCAN_BLOCK ranks of one column's scan
+    int64_t gather_grid, means_grid, combine_grid, ranges_grid; // workgroups of 256 (means: x; y is m)
+    // every device buffer of a call beyond the rank's: knn_eval_windows allocates exactly these (0: not allocated)
+    size_t values_bytes;  // the columns, uint8 [m][n]
+    size_t mask_bytes;    // one uint32 per rank: bit c = column c at the rank's position
+    size_t cum_bytes;     // C_c(r), uint32 [m][n]
+    size_t wpartial_bytes; // the block sums of one column's scan
+    size_t keyd_bytes;    // the keys in rank order as float64, padded to a whole 16-byte load
+    size_t chain_bytes;   // ONE of the two chain buffers P and S, float64 [n]
+    size_t means_bytes;   // float64 [m + 1][nout]: the columns' means, then the key's
+    size_t bins_bytes;    // start, stop int64 [nbins]; counts int64 [m][nbins]; key_lo, key_hi and the edges in the keys' type [nbins]
+    size_t resident_bytes; // rank.resident_bytes + values + mask + cum + wpartial + keyd + 2 chains + means + bins
+};
+
+// false: not a legal problem (n outside [1, 2^31 - 1], a key width other than 4 or 8 bytes, m outside [0, KNN_WINDOWS_MAX_COLS],
+// window outside [0, n], nbins outside [0, KNN_WINDOWS_MAX_BINS], or neither a window nor bins)
+static bool plan_windows(int64_t n, int key_bytes, int64_t m, int64_t window, bool want_order, int64_t nbins, WindowsPlan *out)
+{
+    if (m < 0 || m > KNN_WINDOWS_MAX_COLS || window < 0 || window > n || nbins < 0 || nbins > KNN_WINDOWS_MAX_BINS) return false;
+    if (window == 0 && nbins == 0) return false;
+    WindowsPlan pl;
+    if (!plan_rank(n, 1, 1, key_bytes, false, false, want_order, &pl.rank)) return false;
+    pl.n = n;
+    pl.window = window;
+    pl.nout = window ? n - window + 1 : 0;
+    pl.nbins = nbins;
+    pl.m = (int)m;
+    pl.key_bytes = key_bytes;
+    pl.run = WINDOW_RUN;
+    pl.nblocks = window ? (n + window - 1) / window : 0;
+    pl.blocks_per_run = window && window <= pl.run ? std::min<int64_t>(pl.run / window, WINDOW_CHAINS / 2) : (window ? 1 : 0);
+    pl.runs_per_block = window > pl.run ? (window + pl.run - 1) / pl.run : (window ? 1 : 0);
+    pl.group = pl.blocks_per_run * window;
+    pl.chain_grid = window ? (n + pl.group - 1) / pl.group : 0;
+    pl.chain_lds = 2 * (size_t)(pl.run + (pl.run >> WINDOW_PAD_SHIFT)) * 8;
+    pl.scan_blocks = m ? (n + RANK_SCAN_BLOCK - 1) / RANK_SCAN_BLOCK : 0;
+    pl.gather_grid = std::min<int64_t>(65536, (n + 255) / 256);
+    pl.means_grid = m ? (pl.nout + 255) / 256 : 0;
+    pl.combine_grid = (pl.nout + 255) / 256;
+    pl.ranges_grid = (nbins + 255) / 256;
+    const size_t un = (size_t)n;
+    pl.values_bytes = (size_t)m * un;
+    pl.mask_bytes = m ? un * 4 : 0;
+    pl.cum_bytes = (size_t)m * un * 4;
+    pl.wpartial_bytes = (size_t)pl.scan_blocks * 4;
+    pl.keyd_bytes = window ? ((un + 1) & ~(size_t)1) * 8 : 0;
+    pl.chain_bytes = window ? un * 8 : 0;
+    pl.means_bytes = (size_t)(m + 1) * (size_t)pl.nout * 8;
+    pl.bins_bytes = (size_t)nbins * (16 + (size_t)m * 8 + 3 * (size_t)key_bytes);
+    pl.resident_bytes = pl.rank.resident_bytes + pl.values_bytes + pl.mask_bytes + pl.cum_bytes + pl.wpartial_bytes + pl.keyd_bytes + 2 * pl.chain_bytes +
+                        pl.means_bytes + pl.bins_bytes;
+    *out = pl;
+    return true;
+}
+
 // ---- mean pooling over row ranges (pool.inc) ---------------------------------------
 static const int POOL_COLS = 256;      // columns of one wave: 64 lanes x 4
 static const int POOL_GROUP = 8;       // rows whose loads are issued in front of the first add of the group

@@ -206,16 +206,17 @@ __device__ __forceinline__ uint32_t rank_wg_exscan(uint32_t v, uint32_t (*s_w)[4
     return below + inc - v;
 }
 
-// FLAGS: an entry is bit 0 of the word (the sorted payloads), else the word itself (the count table)
+// FLAGS: an entry is bit `bit` of the word (bit 0 of the sorted payloads; a column of windows.inc's masks), else the word
+// itself (the count table)
 template <bool FLAGS>
-__global__ __launch_bounds__(256) void rank_scan_reduce_kernel(const uint32_t *__restrict__ src, uint64_t m, uint32_t *__restrict__ partial)
+__global__ __launch_bounds__(256) void rank_scan_reduce_kernel(const uint32_t *__restrict__ src, uint64_t m, int bit, uint32_t *__restrict__ partial)
 {
     __shared__ uint32_t s_w[2][4];
     const uint64_t i0 = (uint64_t)blockIdx.x * RANK_SCAN_BLOCK + (uint64_t)threadIdx.x * (RANK_SCAN_BLOCK / 256);
     uint32_t s = 0;
 #pragma unroll
     for (int u = 0; u < RANK_SCAN_BLOCK / 256; u++)
-        if (i0 + u < m) s += FLAGS ? (src[i0 + u] & 1u) : src[i0 + u];
+        if (i0 + u < m) s += FLAGS ? ((src[i0 + u] >> bit) & 1u) : src[i0 + u];
     int par = 0;
     uint32_t total;
     (void)rank_wg_exscan(s, s_w, par, &total);
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(256) void rank_scan_top_kernel(uint32_t *partial, u
 
 // FLAGS: dst[i] = the inclusive running count of the flags; else dst[i] = the exclusive running sum (dst may be src)
 template <bool FLAGS>
-__global__ __launch_bounds__(256) void rank_scan_apply_kernel(const uint32_t *src, uint64_t m, const uint32_t *__restrict__ partial, uint32_t *dst)
+__global__ __launch_bounds__(256) void rank_scan_apply_kernel(const uint32_t *src, uint64_t m, int bit, const uint32_t *__restrict__ partial, uint32_t *dst)
 {
     __shared__ uint32_t s_w[2][4];
     const uint64_t i0 = (uint64_t)blockIdx.x * RANK_SCAN_BLOCK + (uint64_t)threadIdx.x * (RANK_SCAN_BLOCK / 256);
@@ -248,7 +249,7 @@ __global__ __launch_bounds__(256) void rank_scan_apply_kernel(const uint32_t *sr
 #pragma unroll
     for (int u = 0; u < RANK_SCAN_BLOCK / 256; u++) {
         v[u] = 0;
-        if (i0 + u < m) v[u] = FLAGS ? (src[i0 + u] & 1u) : src[i0 + u];
+        if (i0 + u < m) v[u] = FLAGS ? ((src[i0 + u] >> bit) & 1u) : src[i0 + u];
         s += v[u];
     }
     int par = 0;
@@ -302,16 +303,17 @@ static thread_local struct {
     float ms[6]; // host clock: allocations, packing; HIP events: upload, sort, scan of the flags, look-ups and downloads
 } g_rank_info = {0, 0, 0, {0, 0, 0, 0, 0, 0}};
 
-// table[0 .. m) becomes its exclusive scan (FLAGS = false, dst = src), or dst[i] = C(i) from the payloads (FLAGS = true)
+// table[0 .. m) becomes its exclusive scan (FLAGS = false, dst = src), or dst[i] = the running count of bit `bit` of src
+// (FLAGS = true: C(i) from bit 0 of the payloads)
 template <bool FLAGS>
-static int rank_scan(const uint32_t *src, uint64_t m, uint32_t *partial, uint32_t *dst)
+static int rank_scan(const uint32_t *src, uint64_t m, uint32_t *partial, uint32_t *dst, int bit = 0)
 {
     const uint32_t nb = (uint32_t)((m + RANK_SCAN_BLOCK - 1) / RANK_SCAN_BLOCK);
-    hipLaunchKernelGGL(rank_scan_reduce_kernel<FLAGS>, dim3(nb), dim3(256), 0, 0, src, m, partial);
+    hipLaunchKernelGGL(rank_scan_reduce_kernel<FLAGS>, dim3(nb), dim3(256), 0, 0, src, m, bit, partial);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(rank_scan_top_kernel, dim3(1), dim3(256), 0, 0, partial, nb);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(rank_scan_apply_kernel<FLAGS>, dim3(nb), dim3(256), 0, 0, src, m, (const uint32_t *)partial, dst);
+    hipLaunchKernelGGL(rank_scan_apply_kernel<FLAGS>, dim3(nb), dim3(256), 0, 0, src, m, bit, (const uint32_t *)partial, dst);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -330,19 +332,26 @@ static int rank_pass(const RankSrc<K> &src, const K *kin, const uint32_t *pin, K
     return 0;
 }
 
+// The order itself, shared by knn_eval_rank and knn_eval_windows (windows.inc): the buffers of a RankPlan that the sort
+// needs, and what the sort leaves in them.
+template <typename K> struct RankSorted {
+    typename RankFloat<K>::F *d_scores = nullptr;
+    uint8_t *d_correct = nullptr;
+    K *d_k0 = nullptr, *d_k1 = nullptr;
+    uint32_t *d_p0 = nullptr, *d_p1 = nullptr, *d_table = nullptr, *d_partial = nullptr;
+    unsigned int *d_hist = nullptr;
+    RankSrc<K> src;                // the device copy of the input
+    const K *keys = nullptr;       // the sorted keys (order-preserving images)
+    const uint32_t *pay = nullptr; // the sorted payloads
+    int nrun = 0;                  // passes run
+    std::chrono::steady_clock::time_point t_pack, t_up;
+};
+
+// scores, correct, two key and two payload buffers, table, block sums, histograms: by the plan's own sizes
 template <typename K>
-static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, const uint8_t *correct, int desc, const RankPlan &pl,
-                    int64_t *order_out, int64_t *cum_out, const int64_t *targets, int64_t nt, int64_t *idx_out, int64_t *cum_at_out,
-                    const int64_t *ranks, int64_t nr, void *sorted_at_out)
+static int rank_alloc(EvalBufs &bufs, const RankPlan &pl, RankSorted<K> &rs)
 {
     typedef typename RankFloat<K>::F F;
-    constexpr int P = (int)sizeof(K);
-    const uint32_t n = (uint32_t)pl.n;
-    const bool want_c = pl.cum_bytes != 0;
-    // every buffer of the plan, by the plan's own sizes (plan_rank; plan_check walks them)
-    const auto t_alloc = std::chrono::steady_clock::now();
-    EvalBufs bufs;
-    EventList ev;
     EVAL_ALLOC(d_scores, F *, pl.scores_bytes);
     uint8_t *d_correct = nullptr;
     if (pl.correct_bytes) {
@@ -356,20 +365,31 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
     EVAL_ALLOC(d_table, uint32_t *, pl.table_bytes);
     EVAL_ALLOC(d_partial, uint32_t *, pl.partial_bytes);
     EVAL_ALLOC(d_hist, unsigned int *, pl.hist_bytes);
-    uint32_t *d_c = nullptr;
-    if (want_c) {
-        d_c = (uint32_t *)bufs.get(pl.cum_bytes);
-        if (!d_c) return set_err(KNN_ERR_HIP, "eval: out of device memory");
-    }
-    int64_t *d_wide = nullptr; // order, then cum: one buffer
-    if (pl.wide_bytes) {
-        d_wide = (int64_t *)bufs.get(pl.wide_bytes);
-        if (!d_wide) return set_err(KNN_ERR_HIP, "eval: out of device memory");
-    }
-    size_t allocated = 0;
-    for (const auto &b : bufs.dev) allocated += b.second;
-    if (allocated != pl.resident_bytes) return set_err(KNN_ERR_INVALID, "rank: the buffers are not the plan's");
-    const auto t_pack = std::chrono::steady_clock::now();
+    rs.d_scores = d_scores;
+    rs.d_correct = d_correct;
+    rs.d_k0 = d_k0;
+    rs.d_k1 = d_k1;
+    rs.d_p0 = d_p0;
+    rs.d_p1 = d_p1;
+    rs.d_table = d_table;
+    rs.d_partial = d_partial;
+    rs.d_hist = d_hist;
+    return 0;
+}
+
+// packs, uploads and sorts; records three events: in front of the upload, behind it, behind the sort
+template <typename K>
+static int rank_sort(const void *scores, int64_t rows, int64_t k, int64_t limit, const uint8_t *correct, int desc, const RankPlan &pl, EventList &ev,
+                     RankSorted<K> &rs)
+{
+    typedef typename RankFloat<K>::F F;
+    constexpr int P = (int)sizeof(K);
+    const uint32_t n = (uint32_t)pl.n;
+    F *d_scores = rs.d_scores;
+    uint8_t *d_correct = rs.d_correct;
+    uint32_t *d_table = rs.d_table, *d_partial = rs.d_partial;
+    unsigned int *d_hist = rs.d_hist;
+    rs.t_pack = std::chrono::steady_clock::now();
     // limit <= k / 2: the first `limit` columns of every row, packed on the host, are all that travels
     const F *up_scores = (const F *)scores;
     const uint8_t *up_correct = correct;
@@ -386,7 +406,7 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
         up_scores = packed_scores.data();
         if (correct) up_correct = packed_correct.data();
     }
-    const auto t_up = std::chrono::steady_clock::now();
+    rs.t_up = std::chrono::steady_clock::now();
     EVAL_TRY(ev.mark(nullptr));
     HIP_TRY(hipMemcpy(d_scores, up_scores, pl.scores_bytes, hipMemcpyHostToDevice));
     if (correct) HIP_TRY(hipMemcpy(d_correct, up_correct, pl.correct_bytes, hipMemcpyHostToDevice));
@@ -410,8 +430,8 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
         run[0] = true;
         nrun = 1;
     }
-    K *kin = nullptr, *kout = d_k0, *kspare = d_k1;
-    uint32_t *pin = nullptr, *pout = d_p0, *pspare = d_p1;
+    K *kin = nullptr, *kout = rs.d_k0, *kspare = rs.d_k1;
+    uint32_t *pin = nullptr, *pout = rs.d_p0, *pspare = rs.d_p1;
     bool first = true;
     for (int b = 0; b < P; b++) {
         if (!run[b]) continue;
@@ -423,8 +443,48 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
         std::swap(kout, kspare);
         std::swap(pout, pspare);
     }
-    const uint32_t *d_pay = pin; // the sorted payloads
+    rs.src = src;
+    rs.keys = kin;
+    rs.pay = pin;
+    rs.nrun = nrun;
     EVAL_TRY(ev.mark(nullptr));
+    return 0;
+}
+
+template <typename K>
+static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, const uint8_t *correct, int desc, const RankPlan &pl,
+                    int64_t *order_out, int64_t *cum_out, const int64_t *targets, int64_t nt, int64_t *idx_out, int64_t *cum_at_out,
+                    const int64_t *ranks, int64_t nr, void *sorted_at_out)
+{
+    typedef typename RankFloat<K>::F F;
+    constexpr int P = (int)sizeof(K);
+    const uint32_t n = (uint32_t)pl.n;
+    const bool want_c = pl.cum_bytes != 0;
+    // every buffer of the plan, by the plan's own sizes (plan_rank; plan_check walks them)
+    const auto t_alloc = std::chrono::steady_clock::now();
+    EvalBufs bufs;
+    EventList ev;
+    RankSorted<K> rs;
+    EVAL_TRY(rank_alloc<K>(bufs, pl, rs));
+    uint32_t *d_c = nullptr;
+    if (want_c) {
+        d_c = (uint32_t *)bufs.get(pl.cum_bytes);
+        if (!d_c) return set_err(KNN_ERR_HIP, "eval: out of device memory");
+    }
+    int64_t *d_wide = nullptr; // order, then cum: one buffer
+    if (pl.wide_bytes) {
+        d_wide = (int64_t *)bufs.get(pl.wide_bytes);
+        if (!d_wide) return set_err(KNN_ERR_HIP, "eval: out of device memory");
+    }
+    size_t allocated = 0;
+    for (const auto &b : bufs.dev) allocated += b.second;
+    if (allocated != pl.resident_bytes) return set_err(KNN_ERR_INVALID, "rank: the buffers are not the plan's");
+    EVAL_TRY(rank_sort<K>(scores, rows, k, limit, correct, desc, pl, ev, rs));
+    const auto t_pack = rs.t_pack, t_up = rs.t_up;
+    const RankSrc<K> src = rs.src;
+    uint32_t *d_partial = rs.d_partial;
+    const uint32_t *d_pay = rs.pay; // the sorted payloads
+    const int nrun = rs.nrun;
     // ---- C(r)
     if (want_c) EVAL_TRY(rank_scan<true>(d_pay, (uint64_t)n, d_partial, d_c));
     EVAL_TRY(ev.mark(nullptr));

@@ -26,7 +26,7 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
 """
 from collections import Counter, namedtuple
 from itertools import groupby
-from typing import Dict, Iterable, List, NamedTuple, Sequence, Set, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Set, Tuple
 
 import numpy as np
 from numpy import ndarray
@@ -807,6 +807,163 @@ def ranked_cumulative(correct: ndarray, keys: ndarray, descending: bool = False,
         raise ValueError("ranked_cumulative: correct is required")
     order, cum, _, _, _ = _rank(keys, correct, limit, descending, want_order=want_order, want_cum=True)
     return (cum, order) if want_order else cum
+
+
+# ---- statistics over contiguous ranges of the ranked order: knn_eval_windows (include/knn355.h) ------------------------
+WINDOWS_MAX_COLUMNS = 32
+
+
+class RollingMeans(NamedTuple):
+    keys: ndarray              # float64 [N - W + 1]: the rolling mean of the ranked keys
+    values: ndarray            # float64 [M, N - W + 1]: the rolling mean of every column in the keys' order
+    order: Optional[ndarray]   # int64 [N] flat positions in rank order (want_order), else None
+
+
+class RankedBins(NamedTuple):
+    start: ndarray    # int64 [bins]: the ranks [start, stop) of every bin
+    stop: ndarray
+    counts: ndarray   # int64 [M, bins]: set cells of every column in the bin
+    mean: ndarray     # float64 [M, bins]: counts / (stop - start); nan for an empty bin
+    stderr: ndarray   # float64 [M, bins]: the standard error of that mean (numpy's std() / sqrt(n)); nan for an empty bin
+    key_lo: ndarray   # the keys' type [bins]: the key at rank start (even_bins), or the bin's lower edge (edge_bins)
+    key_hi: ndarray   # the key at rank stop, or the bin's upper edge (+inf for the last)
+
+
+def _window_arrays(keys, values, who):
+    """-> (keys float32 / float64 [N], values uint8 [M, N] or None for M = 0)"""
+    keys = np.asarray(keys)
+    if keys.ndim not in (1, 2):
+        raise ValueError(f"{who}: keys must be 1-D or 2-D, not {keys.ndim}-D")
+    shape = keys.shape
+    if keys.size < 1:
+        raise ValueError(f"{who}: keys must hold one value at least, not shape {shape}")
+    if keys.size > RANK_MAX_ELEMENTS:
+        raise ValueError(f"{who}: {keys.size} keys are more than 2^31 - 1")
+    if keys.dtype.kind in "iu":  # lengths: exact in float64 below 2^53
+        if int(keys.max()) >= 2 ** 53 or int(keys.min()) <= -2 ** 53:
+            raise ValueError(f"{who}: an integer key of magnitude 2^53 or more has no exact float64")
+        keys = keys.astype(np.float64)
+    elif keys.dtype not in (np.float32, np.float64):
+        raise ValueError(f"{who}: keys must be float32, float64 or integers, not {keys.dtype}")
+    keys = np.ascontiguousarray(keys).reshape(-1)
+    if values is None or (not isinstance(values, ndarray) and len(values) == 0):
+        return keys, None
+    if isinstance(values, ndarray) and values.ndim == 2 and len(shape) == 1:
+        columns = list(values)
+    elif isinstance(values, ndarray) and values.ndim == 3 and len(shape) == 2:
+        columns = list(values)
+    elif isinstance(values, ndarray) and values.ndim == 2 and values.shape[1] == keys.size:  # [M, N] over flattened 2-D keys
+        columns = [v.reshape(shape) for v in values]
+    elif isinstance(values, ndarray):
+        raise ValueError(f"{who}: values {values.shape} must be [M, ...] over keys {shape}")
+    else:
+        columns = [np.asarray(v) for v in values]
+    if len(columns) > WINDOWS_MAX_COLUMNS:
+        raise ValueError(f"{who}: {len(columns)} columns are more than {WINDOWS_MAX_COLUMNS}")
+    if not columns:
+        return keys, None
+    out = np.empty((len(columns), keys.size), np.uint8)
+    for c, v in enumerate(columns):
+        if v.shape != shape:
+            raise ValueError(f"{who}: column {c} has shape {v.shape}, the keys {shape}")
+        if v.dtype != np.bool_ and v.dtype != np.uint8:
+            raise ValueError(f"{who}: column {c} must be bool or uint8, not {v.dtype}")
+        out[c] = v.reshape(-1) != 0
+    return keys, out
+
+
+def _windows(keys, values, descending, window=0, want_order=False, starts=None, stops=None, edges=None):
+    """knn_eval_windows on checked arrays -> (key_means, value_means, order, start, stop, counts, key_lo, key_hi)"""
+    n = keys.size
+    m = 0 if values is None else values.shape[0]
+    nout = n - window + 1 if window else 0
+    key_means = np.empty(nout, np.float64) if window else None
+    value_means = np.empty((m, nout), np.float64) if window else None
+    order = np.empty(n, np.int64) if want_order else None
+    nb = len(edges) if edges is not None else (len(starts) if starts is not None else 0)
+    start = stop = counts = key_lo = key_hi = None
+    if nb:
+        start, stop = np.empty(nb, np.int64), np.empty(nb, np.int64)
+        counts = np.zeros((m, nb), np.int64)
+        key_lo, key_hi = np.empty(nb, keys.dtype), np.empty(nb, keys.dtype)
+
+    def ptr(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    _lib.check(_lib.lib().knn_eval_windows(keys.ctypes.data, 1 if keys.dtype == np.float64 else 0, n, ptr(values), m, 1 if descending else 0, window,
+                                           ptr(key_means), ptr(value_means), ptr(order), ptr(starts), ptr(stops), ptr(edges), nb, ptr(start), ptr(stop),
+                                           ptr(counts), ptr(key_lo), ptr(key_hi)))
+    return key_means, value_means, order, start, stop, counts, key_lo, key_hi
+
+
+def last_windows_info():
+    """How this thread's last rolling_means / even_bins / edge_bins ran on the device: the staging run of the key's chains,
+    blocks per run, runs per block, and milliseconds: the device allocations (host clock), then uploads, sort, the gather
+    with the scans, the chains, the columns' means, the bins and the downloads (HIP events)."""
+    from ctypes import byref, c_float, c_int64
+    run, bpr, rpb, ms = c_int64(), c_int64(), c_int64(), (c_float * 8)()
+    _lib.check(_lib.lib().knn_last_windows_info(byref(run), byref(bpr), byref(rpb), ms))
+    names = ("alloc_ms", "upload_ms", "sort_ms", "gather_scan_ms", "chains_ms", "means_ms", "bins_ms", "download_ms")
+    return {"run": run.value, "blocks_per_run": bpr.value, "runs_per_block": rpb.value, **dict(zip(names, ms))}
+
+
+def rolling_means(keys: ndarray, values=None, window: int = 1000, descending: bool = False, want_order: bool = False) -> RollingMeans:
+    """rolling_mean(x[argsort(key)], window) of seqvec_search/utils.py:103 for the key itself and for up to 32 boolean
+    columns at once (pfam/pfam.py:247-253, cath/cath.py:799-813, 913-919) -> RollingMeans(keys, values, order).
+
+    keys float32 / float64 (integers such as lengths are taken as float64), 1-D or 2-D (flattened row by row); values a
+    bool / uint8 array [M, ...] or a sequence of M arrays shaped like keys, or None.  The order is ranked_cumulative's:
+    stable, -0.0 equals +0.0, NaN last, descending=True the order of numpy.argsort(-keys, kind="stable").
+    A column's mean over the window is the correctly rounded count / window.  The key's mean adds each window in a fixed
+    order (blocks of `window` ranks, a forward and a backward chain per block: include/knn355.h) without any subtraction:
+    an inf or a NaN shows in the windows that hold it and in no other."""
+    keys, values = _window_arrays(keys, values, "rolling_means")
+    window = int(window)
+    if window < 1 or window > keys.size:
+        raise ValueError(f"rolling_means: window must be in [1, N = {keys.size}], not {window}")
+    key_means, value_means, order, *_ = _windows(keys, values, descending, window=window, want_order=want_order)
+    return RollingMeans(key_means, value_means, order)
+
+
+def _ranked_bins(start, stop, counts, key_lo, key_hi):
+    n = (stop - start).astype(np.float64)
+    c = counts.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = c / n  # (numpy sums a boolean column exactly: these are the bits of its mean())
+        stderr = np.sqrt((c * (1 - mean) * (1 - mean) + (n - c) * mean * mean) / n) / np.sqrt(n)
+    return RankedBins(start, stop, counts, mean, stderr, key_lo, key_hi)
+
+
+def even_bins(keys: ndarray, values, bins: int, descending: bool = False) -> RankedBins:
+    """hist_evenly of cath/cath.py:863-875 and pfam/pfam.py:282-297: mean and standard error of boolean columns over
+    `bins` equal-count slices of the ranked order.  Slice i is the ranks [N * i // (bins + 1), N * (i + 1) // (bins + 1)),
+    the reference's own arithmetic: the last 1 / (bins + 1) of the order is never read.  key_lo and key_hi are the keys
+    at ranks start and stop, bits untouched, as the reference's tick labels read them.  An empty slice (bins + 1 > N)
+    has count 0 and mean = stderr = nan."""
+    keys, values = _window_arrays(keys, values, "even_bins")
+    bins = int(bins)
+    if bins < 1 or bins > 2 ** 20:
+        raise ValueError(f"even_bins: bins must be in [1, 2^20], not {bins}")
+    i = np.arange(bins + 1, dtype=np.int64)
+    cuts = keys.size * i // (bins + 1)
+    starts, stops = np.ascontiguousarray(cuts[:-1]), np.ascontiguousarray(cuts[1:])
+    _, _, _, start, stop, counts, key_lo, key_hi = _windows(keys, values, descending, starts=starts, stops=stops)
+    return _ranked_bins(start, stop, counts, key_lo, key_hi)
+
+
+def edge_bins(keys: ndarray, values, edges) -> RankedBins:
+    """The length bins of cath/cath.py:831-857: bin i holds the keys with edges[i] <= key < edges[i + 1], the last one
+    every key >= edges[-1]; NaN keys fall in no bin.  edges ascending and finite, taken in the keys' type; the order is
+    ascending.  key_lo, key_hi = edges[i], edges[i + 1] (+inf for the last)."""
+    keys, values = _window_arrays(keys, values, "edge_bins")
+    e = np.asarray(edges, np.float64).reshape(-1)
+    if e.size < 1 or e.size > 2 ** 20:
+        raise ValueError(f"edge_bins: need 1 to 2^20 edges, not {e.size}")
+    e = np.ascontiguousarray(e.astype(keys.dtype))
+    if not np.isfinite(e).all() or (np.diff(e) < 0).any():
+        raise ValueError("edge_bins: edges must be finite and ascending")
+    _, _, _, start, stop, counts, _, _ = _windows(keys, values, False, edges=e)
+    return _ranked_bins(start, stop, counts, e, np.append(e[1:], np.asarray(np.inf, keys.dtype)))
 
 
 def _quantile_positions(n: int, q: ndarray):
