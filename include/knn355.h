@@ -700,6 +700,35 @@ int knn_eval_fuse(const int64_t *hits_a, const double *scores_a, const uint8_t *
                   const int64_t *hits_b, const double *scores_b, int64_t kb, int64_t nq,
                   int32_t mode, int32_t ascending, int32_t k_out,
                   int64_t *hits_out, double *scores_out, int32_t *source_out, int32_t *filled_out);
+/* pfam/pfam.py:349-370 ("TP Set overlap") and 602-625 (auc1s_optimal): two hit lists compared query by query as sets of
+ * ids.  hits_a / correct_a are [nq][ka], hits_b / correct_b [nq][kb], tp_out / lead_out [nq][3]; all host arrays,
+ * row-major.  correct_x is uint8, a non-zero byte meaning "this hit is a true positive": the matrices of
+ * knn_eval_labels and knn_eval_sets_matrix, each list with its own.  Ids are compared as whole int64 values.
+ *   entries    an entry exists when its hit is >= 0 (knn_eval_fuse's rule; ragged MMseqs2 rows are padded that way).  An
+ *              entry that does not exist is in no set and does not end a leading run.
+ *   TP sets    TA = the distinct ids of A's existing entries whose flag is non-zero, TB the same for B from B's own
+ *              flags.  An id flagged in one list and not in the other is in one set only; an id that repeats inside a
+ *              list is in that list's set when any of its occurrences is flagged.
+ *   leading    A's existing entries are walked in column order up to, and without, the first one whose flag is zero; LA
+ *              = the distinct ids walked, LB the same for B (the reference's `for j in hits: if correct: add, else:
+ *              break`).
+ *   outputs    tp_out[q] = (|TA \ TB|, |TA & TB|, |TB \ TA|); lead_out[q] = the same split of LA and LB.  Either may be
+ *              NULL, not both.  The sum of lead_out[q] is |LA u LB|, the numerator of the best-case AUC1.
+ * The joined walk of pfam.py:629-667 is not here: it is knn_eval_fuse in KNN_FUSE_SORTED_UNION mode with k_out = ka + kb
+ * and source_out, followed by a leading-run count over the fused row.
+ * KNN_ERR_INVALID, with a message naming the argument, before anything is allocated or launched and with the outputs
+ * untouched: nq < 0; ka or kb outside [1, KNN_MAX_K]; a null input pointer; both output pointers null.  nq = 0 returns
+ * 0 before any pointer is looked at.  Rows go through the device in slabs of the row count above for k = ka + kb
+ * (KNN355_EVAL_SLAB_ROWS included).
+ * Hot path: overlap_kernel (overlap.inc), one workgroup per row: the two lead lengths by a workgroup minimum, (id, four
+ * membership bits) pairs sorted in LDS over next_pow2(ka + kb) slots, the bits of a run of equal ids OR-ed towards its
+ * head by doubling, the heads counted into the six classes.  Integers only, no atomics, plain vector stores. */
+int knn_eval_overlap(const int64_t *hits_a, const uint8_t *correct_a, int64_t ka,
+                     const int64_t *hits_b, const uint8_t *correct_b, int64_t kb, int64_t nq,
+                     int32_t *tp_out /* [nq][3] or NULL */, int32_t *lead_out /* [nq][3] or NULL */);
+/* measurement (tools/bench_overlap.py): milliseconds by HIP events of the calling thread's last successful
+ * knn_eval_overlap: uploads, kernels, downloads, each summed over the slabs. */
+int knn_eval_overlap_last_ms(float *ms /* [3] */);
 
 /* ---- principal components of embedding rows ---------------------------------------
  * pfam/reverse_evaluate.py:34-44, 100-108: sklearn.decomposition.PCA(n_components=2) over the concatenated forward and

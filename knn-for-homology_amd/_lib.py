@@ -156,6 +156,8 @@ def _declare(L):
         "knn_kde_last_ms": (c_int32, [f32p, f32p]),
         "knn_eval_fuse": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+        "knn_eval_overlap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+        "knn_eval_overlap_last_ms": (c_int32, [f32p]),
         "knn_write_prefilter_db": (c_int32, [c_char_p, c_char_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32]),
         "knn_scan_times": (c_int32, [H, c_void_p, c_int32]),
         "knn_last_seed_info": (c_int32, [H, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)]),

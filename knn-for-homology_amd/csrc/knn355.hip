@@ -30,6 +30,7 @@
 //   pr_curve.inc                    the precision-recall threshold sweep over (is_correct, scores) (knn_eval_pr_curve).
 //   buckets.inc                     accuracy per score bucket and the accuracy-over-hits curve (knn_eval_bucket_counts, knn_eval_hit_curve).
 //   fuse.inc                        the two hit-list fusions of the results scripts: prefix-then-fill, sorted union (knn_eval_fuse).
+//   overlap.inc                     two hit lists compared as sets of ids: true-positive overlap, leading-run union (knn_eval_overlap).
 //   pca.inc                         mean, covariance (fp32 MFMA) and projection behind decomposition.PCA (knn_pca_moments, knn_pca_project).
 //   kde.inc                         1-D Gaussian kernel density estimates behind density.gaussian_kde (knn_kde_stats, knn_kde_eval).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
@@ -5676,6 +5677,7 @@ extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *
 #include "bootstrap.inc"
 #include "pca.inc"
 #include "fuse.inc"
+#include "overlap.inc"
 #include "range.inc"
 #include "pool.inc"
 #include "kde.inc"

@@ -23,6 +23,7 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   score_quantiles            pfam/proteins.py:626-648 (numpy.quantile over every score: precision_recall_curve's thresholds)
   combine_hits               pfam/proteins.py:216-240 ("combined": MMseqs2 hits with E < 0.1, filled up with k-NN hits)
   merge_hits                 pfam/proteins.py:340-372 ("both aligned": two lists sorted together, repeated ids dropped)
+  compare_hits               pfam/pfam.py:349-370, 602-625 (two lists as sets of ids: "TP Set overlap" and auc1s_optimal)
 """
 from collections import Counter, namedtuple
 from itertools import groupby
@@ -1091,3 +1092,62 @@ def combine_hits(hits_a: ndarray, e_values_a: ndarray, hits_b: ndarray, scores_b
         row = int(np.argmax(filled < hits.shape[1]))
         raise ValueError(f"row {row} holds {int(filled[row])} hits, fewer than k_out = {hits.shape[1]}")
     return (hits, scores, source) if want_sources else (hits, scores)
+
+
+# ---- two hit lists compared as sets of ids: knn_eval_overlap (include/knn355.h) ----------------------------------------
+class HitOverlap(NamedTuple):
+    """compare_hits' result, int32 [nq, 3] each: per query the sizes of (only A, both, only B) for the true-positive sets
+    (tp) and for the ids each list returns before its first wrong hit (lead)."""
+    tp: ndarray
+    lead: ndarray
+
+
+def compare_hits(hits_a: ndarray, correct_a: ndarray, hits_b: ndarray, correct_b: ndarray) -> HitOverlap:
+    """The set comparisons of pfam/pfam.py between two methods' hit lists, query by query, one GPU pass -> HitOverlap.
+
+    hits_a [nq, ka] with correct_a bool / uint8 [nq, ka] (label_matches, compute_correctness_array: non-zero means "this hit
+    is a true positive") and hits_b [nq, kb] with its own correct_b; widths 1 .. 2048.  An entry with a negative id does
+    not exist (pad ragged MMseqs2 rows with -1): it is in no set and does not end a leading run.
+    tp[q] = (|TA - TB|, |TA & TB|, |TB - TA|) over the sets of distinct flagged ids (pfam.py:349-363, A being MMseqs2's list
+    there); an id flagged in one list only is in that set only.  lead[q] is the same split of the distinct ids each list
+    holds in front of its first existing entry with a zero flag (pfam.py:605-618): lead.sum(axis=1) is the reference's
+    len(knn_hits_set | mmseqs_hits_set).  See tp_overlap_fractions and auc1_optimal.
+    The joined walk of pfam.py:629-667 (auc1s_joined) is not part of this: merge_hits(..., k_out=ka + kb,
+    want_sources=True) gives the walk's order with repeats dropped, and the leading run of correct ids in it is the count."""
+    hits_a, hits_b = _hits(hits_a), _hits(hits_b)
+    correct_a, correct_b = _correct_bytes(correct_a, "compare_hits"), _correct_bytes(correct_b, "compare_hits")
+    if correct_a.shape != hits_a.shape or correct_b.shape != hits_b.shape:
+        raise ValueError(f"correct {correct_a.shape}, {correct_b.shape} and hits {hits_a.shape}, {hits_b.shape} must have the same shapes")
+    if hits_a.shape[0] != hits_b.shape[0]:
+        raise ValueError(f"both hit lists must have one row per query, not {hits_a.shape[0]} and {hits_b.shape[0]}")
+    (nq, ka), kb = hits_a.shape, hits_b.shape[1]
+    tp = np.empty((nq, 3), np.int32)
+    lead = np.empty((nq, 3), np.int32)
+    _lib.check(_lib.lib().knn_eval_overlap(hits_a.ctypes.data, correct_a.ctypes.data, ka, hits_b.ctypes.data, correct_b.ctypes.data, kb,
+                                           nq, tp.ctypes.data, lead.ctypes.data))
+    return HitOverlap(tp, lead)
+
+
+def tp_overlap_fractions(overlap: HitOverlap, per_query: int = 10) -> Tuple[float, float, float]:
+    """The three numbers of the reference's "TP Set overlap" line (pfam/pfam.py:365-370): the sums of only-A, both and only-B
+    true positives over the queries, each divided by per_query * nq (the reference's 10 * len(knn_hits))."""
+    tp = np.asarray(overlap.tp)
+    only_a, both, only_b = (int(c) for c in tp.sum(axis=0, dtype=np.int64))
+    denominator = per_query * len(tp)
+    return only_a / denominator, both / denominator, only_b / denominator
+
+
+def auc1_optimal(overlap: HitOverlap, family_sizes: ndarray) -> ndarray:
+    """auc1s_optimal of pfam/pfam.py:602-625 -> float64 [nq]: the AUC1 a perfect merger of the two lists could reach,
+    len(LA | LB) / family size.  The counts come from the device, the division is numpy's, one per query."""
+    lead = np.asarray(overlap.lead)
+    sizes = _per_query(family_sizes, np.int64, len(lead), "family_sizes")
+    return lead.sum(axis=1, dtype=np.int64) / sizes
+
+
+def last_overlap_ms():
+    """Milliseconds by HIP events of this thread's last compare_hits: {upload_ms, kernel_ms, download_ms}."""
+    from ctypes import c_float
+    ms = (c_float * 3)()
+    _lib.check(_lib.lib().knn_eval_overlap_last_ms(ms))
+    return dict(zip(("upload_ms", "kernel_ms", "download_ms"), ms))
