@@ -1,4 +1,4 @@
-// assemble.inc -- protein-level hits from slice searches (included by knn355.hip behind eval.inc).
+// assemble.inc -- protein-level hits from slice searches (included by knn355_lib.hip behind eval.inc).
 //
 // The reference searches fixed-length windows ("slices") of proteins (pfam/slices/slices_search.py) and then assembles
 // the slice hits per protein in a Python loop under tqdm (pfam/slices/slices.py:256-291 assemble): the k hits of every

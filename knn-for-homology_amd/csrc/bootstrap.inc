@@ -1,4 +1,4 @@
-// bootstrap.inc -- the bootstrap of the CATH accuracy table (included by knn355.hip behind pr_curve.inc).
+// bootstrap.inc -- the bootstrap of the CATH accuracy table (included by knn355_lib.hip behind pr_curve.inc).
 //
 // The reference resamples the evaluable queries 500 times per method and rebuilds, per resample, a Counter of
 // superfamilies and a Python list of 1 / count (cath/cath.py:404-438, once per method from :441-458).  Here a

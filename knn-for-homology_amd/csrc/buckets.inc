@@ -1,4 +1,4 @@
-// buckets.inc -- accuracy per score bucket and the accuracy-over-hits curve of (is_correct, scores) (included by knn355.hip
+// buckets.inc -- accuracy per score bucket and the accuracy-over-hits curve of (is_correct, scores) (included by knn355_lib.hip
 // behind pr_curve.inc).
 //
 // The reference bins its hits in a Python loop over 300 buckets, each iteration a handful of passes over the whole

@@ -1,4 +1,4 @@
-// eval.inc -- consumers of the (hits, scores) arrays, SURVEY.md section 8(f) N4 (included by knn355.hip).
+// eval.inc -- consumers of the (hits, scores) arrays, SURVEY.md section 8(f) N4 (included by knn355_lib.hip).
 //
 // The reference post-processes search results with per-row Python loops
 // (pfam/proteins.py:85-122 remove_self_hit; seqvec_search/main.py:64-82 evaluate;
@@ -184,7 +184,7 @@ __global__ void levels_eval_kernel(const int64_t *__restrict__ hits, int64_t nq,
 }
 
 // ---- host wrappers: host buffers in and out, rows processed in slabs -------------------------
-// (EvalBufs, EVAL_ALLOC, EVAL_TRY: knn355.hip, the head of the host side)
+// (EvalBufs, EVAL_ALLOC, EVAL_TRY: host_core.inc)
 // The slab walker: the columns that travel between the host and the device.  A column is declared once -- host pointer,
 // bytes per row, input or output -- which allocates `cap` rows of it through EvalBufs and registers its copy; upload and
 // download then move the rows [r0, r0 + m) of every input and of every output column (synchronous copies on the null

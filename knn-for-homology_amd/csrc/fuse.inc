@@ -1,4 +1,4 @@
-// fuse.inc -- the two hit-list fusions of the reference's results script (included by knn355.hip behind pr_curve.inc).
+// fuse.inc -- the two hit-list fusions of the reference's results script (included by knn355_lib.hip behind pr_curve.inc).
 //
 // Between a search and the evaluation passes, pfam/proteins.py builds two more hit arrays per query in Python loops under
 // tqdm: "combined" (lines 216-240: the MMseqs2 hits with E < 0.1, filled up with the k-NN hits that are not among them)

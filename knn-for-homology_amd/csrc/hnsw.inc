@@ -1,4 +1,4 @@
-// hnsw.inc -- faiss.IndexHNSWFlat on MI355X (included by knn355.hip).
+// hnsw.inc -- faiss.IndexHNSWFlat on MI355X (included by knn355_lib.hip).
 //
 // Reference call site: pfam/proteins_search.py:27-31,35-37,49
 //   index = faiss.IndexHNSWFlat(d, 42, faiss.METRIC_INNER_PRODUCT); index.hnsw.efSearch = 256

@@ -1,5 +1,5 @@
 // kde.inc -- one-dimensional Gaussian kernel density estimates: density.gaussian_kde, density.density_curves (included
-// by knn355.hip last).
+// by knn355_lib.hip last).
 //
 // The reference draws DataFrame({...}).plot.density() over the projected columns and over raw embedding dimensions
 // (pfam/reverse_evaluate.py:63-70, 113-118, 139-142); pandas turns every column into

@@ -34,6 +34,11 @@
 //   pca.inc                         mean, covariance (fp32 MFMA) and projection behind decomposition.PCA (knn_pca_moments, knn_pca_project).
 //   kde.inc                         1-D Gaussian kernel density estimates behind density.gaussian_kde (knn_kde_stats, knn_kde_eval).
 //   range.inc / refine.inc          IndexFlat.range_search, IndexRefineFlat (exact re-scoring of a shortlist).
+//
+// This file is the device code of the flat search and nothing else: bench.py and tools/summarize_profiles.py pin it by
+// SHA-256, and the measured HBM traffic of profiles/pmc_traffic.json is quoted only while the hash stands.  Host code
+// belongs in host_core.inc, flat_index.inc, flat_search.inc, flat_info.inc and comm.inc, a feature in an .inc file of its
+// own, and every #include of them in knn355_lib.hip (the translation unit the Makefile builds) -- not here.
 #include <hip/hip_runtime.h>
 #include <thread>
 #include <type_traits>
@@ -3164,2520 +3169,3 @@ __global__ __launch_bounds__(256) void rescore16_kernel(const uint64_t *__restri
         ok[(size_t)q * kp + j0 + tid] = out;
     }
 }
-
-// ===========================================================================
-// host side
-// ===========================================================================
-static thread_local std::string g_err;
-static thread_local int g_device = 0;
-
-static int set_err(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return set_err(KNN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
-// ---- what one call owns: every host entry releases its transient device memory, events and streams
-// through these and HostCall below, whichever way it returns
-// device buffers of one call, straight from hipMalloc and hipFree'd with it
-struct EvalBufs {
-    std::vector<std::pair<void *, size_t>> dev;
-    bool oom = false; // a get() has failed
-    ~EvalBufs() { for (auto &b : dev) if (b.first) (void)hipFree(b.first); }
-    void *get(size_t bytes)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-            oom = true;
-            return nullptr;
-        }
-        dev.push_back({p, bytes});
-        return p;
-    }
-};
-// a device-only buffer
-#define EVAL_ALLOC(var, type, bytes)                                                    \
-    type var = (type)bufs.get(bytes);                                                   \
-    if (!var) return set_err(KNN_ERR_HIP, "eval: out of device memory")
-#define EVAL_TRY(expr)                                                                  \
-    do {                                                                                \
-        const int rc_ = (expr);                                                         \
-        if (rc_) return rc_;                                                            \
-    } while (0)
-
-// HIP events of one call, in the order they were recorded
-struct EventList {
-    std::vector<hipEvent_t> ev;
-    ~EventList()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    int mark(hipStream_t s, unsigned flags = 0)
-    {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, flags));
-        ev.push_back(e);
-        HIP_TRY(hipEventRecord(e, s));
-        return 0;
-    }
-};
-// after the streams have drained: the times between the events of every pair (0, 1), (2, 3), ... summed into *ms
-static int sum_pairs(const EventList &ev, float *ms)
-{
-    *ms = 0.0f;
-    for (size_t i = 0; i + 1 < ev.ev.size(); i += 2) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, ev.ev[i], ev.ev[i + 1]));
-        *ms += t;
-    }
-    return 0;
-}
-
-// Device scratch buffers are recycled through a small per-device pool: the reference's scripts
-// build a fresh index per embedding file (cath/search.py:20-24), and hipMalloc/hipFree of the
-// gigabyte-sized candidate-list workspace would otherwise dominate their end-to-end time.
-struct DevPool {
-    struct Item { void *p; size_t bytes; int device; };
-    std::mutex mu;
-    std::vector<Item> items;
-    size_t total = 0;
-    static constexpr size_t kMaxBytes = 8ull << 30;
-    void *take(size_t need, int device, size_t *got)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        int best = -1;
-        for (int i = 0; i < (int)items.size(); i++)
-            if (items[i].device == device && items[i].bytes >= need && items[i].bytes <= need * 4 + (1u << 20) &&
-                (best < 0 || items[i].bytes < items[best].bytes))
-                best = i;
-        if (best < 0) return nullptr;
-        void *p = items[best].p;
-        *got = items[best].bytes;
-        total -= items[best].bytes;
-        items.erase(items.begin() + best);
-        return p;
-    }
-    void give(void *p, size_t bytes, int device)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (total + bytes <= kMaxBytes && items.size() < 64) {
-                items.push_back({p, bytes, device});
-                total += bytes;
-                return;
-            }
-        }
-        (void)hipFree(p);
-    }
-};
-static DevPool g_pool;
-
-// database storage goes through the same pool as the scratch buffers
-static void *pool_alloc(size_t bytes, int device, size_t *got)
-{
-    if (void *q = g_pool.take(bytes, device, got)) return q;
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    *got = bytes;
-    return p;
-}
-
-// A pool_alloc that goes back to the pool with its scope (null: the allocation failed, or 0 bytes were asked for), unless
-// release() has handed it to a new owner.  The destructor waits for nothing: whoever enqueued work on the buffer has
-// drained that stream first.
-struct PoolBuf {
-    void *p = nullptr;
-    size_t got = 0;
-    int device = 0;
-    PoolBuf(size_t bytes, int dev) : device(dev) { if (bytes) p = pool_alloc(bytes, dev, &got); }
-    PoolBuf(const PoolBuf &) = delete;
-    PoolBuf &operator=(const PoolBuf &) = delete;
-    ~PoolBuf() { if (p) g_pool.give(p, got, device); }
-    explicit operator bool() const { return p != nullptr; }
-    template <typename T> T *get() const { return (T *)p; }
-    void *release(size_t *bytes)
-    {
-        void *q = p;
-        *bytes = got;
-        p = nullptr;
-        return q;
-    }
-};
-
-extern "C" int64_t knn_trim(void)
-{
-    std::vector<DevPool::Item> items;
-    {
-        std::lock_guard<std::mutex> lk(g_pool.mu);
-        items.swap(g_pool.items);
-        g_pool.total = 0;
-    }
-    int64_t freed = 0;
-    int cur = 0;
-    (void)hipGetDevice(&cur);
-    for (auto &it : items) {
-        if (hipSetDevice(it.device) == hipSuccess && hipFree(it.p) == hipSuccess) freed += (int64_t)it.bytes;
-    }
-    (void)hipSetDevice(cur);
-    return freed;
-}
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    int device = 0;
-    // done / s: the owner's "everything my earlier calls enqueued" event and the stream of the call in progress.  A buffer
-    // that grows goes back to the pool, which may hand it to another handle right away: whatever still uses it must have
-    // finished.  With both given that is a host wait for the OWNER's work only (its previous calls through `done`, this
-    // call's launches through `s`); rounds 1-2 called hipDeviceSynchronize() here, which also stalled the other lane and
-    // every caller stream at the first searches of a handle.  Without them (users unknown): the whole device.
-    int ensure(size_t need, hipEvent_t done = nullptr, hipStream_t s = nullptr)
-    {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        if (need <= bytes && cur == device) return 0;
-        if (p) {
-            (void)hipSetDevice(device);
-            if (done && cur == device) {
-                (void)hipEventSynchronize(done);
-                (void)hipStreamSynchronize(s);
-            } else {
-                (void)hipDeviceSynchronize();
-            }
-            (void)hipSetDevice(cur);
-        }
-        release();
-        device = cur;
-        size_t got = 0;
-        if (void *q = g_pool.take(need, device, &got)) {
-            p = q;
-            bytes = got;
-            return 0;
-        }
-        size_t want = need + need / 4;
-        if (hipMalloc(&p, want) != hipSuccess) {
-            if (hipMalloc(&p, need) != hipSuccess) { p = nullptr; return -1; }
-            want = need;
-        }
-        bytes = want;
-        return 0;
-    }
-    void release()
-    {
-        if (p) g_pool.give(p, bytes, device);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-#ifdef KNN355_TRACE
-static DevBuf g_trace_buf;
-static int g_trace_grid = 0;
-// developer build only: the stamps of the last traced scan launch, [grid][128]; returns the grid
-extern "C" int knn_dev_trace_read(unsigned long long *out, int max_wgs)
-{
-    const int n = std::min(max_wgs, g_trace_grid);
-    if (n > 0 && hipMemcpy(out, g_trace_buf.p, (size_t)n * 128 * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return g_trace_grid;
-}
-#endif
-
-// per seed-recursion level: compact candidate arrays [nq][qcap] + their fill, the shared running
-// thresholds and the verification bounds of a statistically seeded pass
-struct LevelBufs {
-    DevBuf qlist, qcnt, gthr, qthr;
-    DevBuf pub, arrive; // tile-minimum seed: published keys [nslots][rounds * nchunks], arrival counters [nqtiles]
-    DevBuf pair_ctr;    // paired walk: ticket counter of every pair of workgroups
-    uint64_t clean_sig = 0; // != 0: the last search's selection reset this state for a search of exactly this shape
-};
-
-// HIP streams are recycled: creating one costs a third of a millisecond, and the reference's scripts build a fresh
-// index per embedding file (cath/search.py:20-24).  A stream goes back to the pool fully drained.
-struct StreamPool {
-    std::mutex mu;
-    std::vector<std::pair<int, hipStream_t>> free_list;
-    hipStream_t take(int device)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            for (size_t i = 0; i < free_list.size(); i++)
-                if (free_list[i].first == device) {
-                    hipStream_t s = free_list[i].second;
-                    free_list.erase(free_list.begin() + i);
-                    return s;
-                }
-        }
-        hipStream_t s = nullptr;
-        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        return s;
-    }
-    void give(int device, hipStream_t s)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (free_list.size() < 16) free_list.push_back({device, s});
-        else (void)hipStreamDestroy(s);
-    }
-};
-static StreamPool g_streams;
-
-// A stream of the pool for one scope (null: the take failed, or `want` was false); it goes back drained.
-struct StreamLease {
-    int device;
-    hipStream_t s;
-    explicit StreamLease(int dev, bool want = true) : device(dev), s(want ? g_streams.take(dev) : nullptr) {}
-    StreamLease(const StreamLease &) = delete;
-    StreamLease &operator=(const StreamLease &) = delete;
-    ~StreamLease()
-    {
-        if (!s) return;
-        (void)hipStreamSynchronize(s);
-        g_streams.give(device, s);
-    }
-    operator hipStream_t() const { return s; }
-};
-
-struct knn_index_s {
-    int d = 0, dp = 0, metric = 0, device = 0;
-    int num_cus = 256;
-    int64_t ntotal = 0, cap_rows = 0;
-    bool is_view = false; // shares another handle's database (knn_flat_view): read-only, frees nothing of it
-    // storage generation: bumped whenever xb/yn are reallocated, reset or freed.  A view remembers the
-    // value it was made at and refuses to search once its parent's storage has moved on.
-    std::shared_ptr<std::atomic<int64_t>> storage_gen = std::make_shared<std::atomic<int64_t>>(0);
-    int64_t view_gen = 0;
-    float *xb = nullptr; // [cap_rows][dp]
-    bool approx16 = false;  // the scan multiplies bf16 copies of rows and queries (HNSW's coarse entry index: approximate on purpose)
-    bool keep16 = false;    // bf16 copies of the rows are kept beside the fp32 ones (HNSW storage: the beam walks on them); scans stay fp32
-    DevBuf xb16, ws_q16;    // approx16: [cap_rows][dp] bf16 rows, [nq][dp] bf16 queries
-    // exact 16-bit prefilter (knn_flat_set_scan16): fp16 copies of the rows, [cap_rows][dp16] (dp16 = d rounded
-    // up to 64), one int8 exponent per row, the index-wide statistics (S16_*).  Views use their parent's.
-    int scan16 = 0;               // 0 off, 1 copies kept, 2 dropped (allocation failed) until the index is reset
-    int s16_fmt = 16;             // the copies' format: 16 = fp16 [cap_rows][dp16]; 12 = 12-bit fixed point in tiles (scan12_rows_kernel)
-    // the copies cover every row and every row is finite -- shared with the views, so a row added to the parent that is not
-    // finite turns the path off for them too
-    std::shared_ptr<std::atomic<bool>> s16_ok = std::make_shared<std::atomic<bool>>(false);
-    int dp16 = 0;
-    DevBuf s16_rows_buf, s16_exp_buf, s16_stat_buf;
-    const _Float16 *s16_rows = nullptr;
-    const int8_t *s16_exp = nullptr;
-    const uint32_t *s16_stat = nullptr;
-    std::string s16_note;
-    DevBuf ws_q16x, ws_s16q, ws_s16ak, ws_s16ok, ws_s16stat; // fp16 queries; exponents, bounds, flags; keys; [largest window, fallbacks]
-    bool last_s16_used = false;   // some piece of the last search (search_keys_impl) took the prefilter
-    int last_s16_fmt = 0;         // ... on copies of this format (recorded where the pass is enqueued)
-    int s16_pieces = 0;           // ... how many: the first one restarts the largest-window counter
-    float *yn = nullptr; // [cap_rows + pad]
-    size_t xb_bytes = 0, yn_bytes = 0; // allocation sizes (may exceed the row capacity: pooled)
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;               // recorded behind everything a search of this handle enqueued (DevBuf::ensure)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; // the pair of the most recent scan launch
-    static const int RING = 64;
-    hipEvent_t ring0[RING] = {nullptr}, ring1[RING] = {nullptr};
-    int64_t nlaunches = 0;
-    std::mutex mu;
-    DevBuf ws_q, ws_qn, ws_lists, ws_D, ws_I, ws_tmp, ws_tmp2;
-    DevBuf ws_D1, ws_I1, ws_tmp3; // second set for the pipelined host search
-    DevBuf ws_flag;               // [0]: a statistically seeded search failed its verification
-    DevBuf ws_sym;                // work table of a symmetric all-vs-all launch
-    int sym_tiles = -1, sym_run = 0; // ... which is the table for this many tiles (run length sym_run, sym_items entries)
-    int sym_ts = 0;               // ... of this many rows each
-    int64_t sym_items = 0;
-    int sym_groups = 1;           // ... in this many groups of query tiles, one launch each (results streamed to the host group by group)
-    std::vector<int64_t> sym_gstart; // [sym_groups + 1] first entry of each group
-    DevBuf ws_qdiff;              // difference builds: the queries interleaved by pairs
-    DevBuf ws_defer;              // tile-minimum seed: the parked first-tile scores of every workgroup
-    DevBuf ws_turn;               // batch launches: one word per CU (the resident workgroups take turns in their K loops)
-    void *turn_zeroed = nullptr;  // the ws_turn allocation that has been cleared (every holder gives its word back: a launch leaves them all zero)
-    int64_t sym_searches = 0;     // self-searches served by the symmetric path
-    static const int MAX_LEVELS = 8;
-    LevelBufs ws_level[MAX_LEVELS]; // per seed-recursion level
-    int last_seed_stride = 0, last_seed_stat = 0;
-    int64_t last_sample_rows = 0; // rows the seed sample took out of the main pass of the last search
-    int64_t stat_redo = 0;        // searches repeated because the statistical threshold was too tight
-    int *flag_host = nullptr;     // pinned: [slot] copy of ws_flag behind each batch of a host search
-    // tuning + introspection
-    int force_qt = 0, force_chunks = 0, flags = 0;
-    int64_t batch_nq = 0; // the caller's whole batch while a search works through it in pieces (BatchScope); 0: outside a search
-    int64_t batch_hint = 0; // knn_flat_set_batch: the calls that follow are pieces of a batch of this many queries (0: each its own)
-    int pub_rounds_force = 0; // tile-minimum seed: rounds of publications (0: the host's choice)
-    std::string last_kernel;
-    int last_qt = 0, last_dt = 0, last_chunks = 0, last_grid = 0;
-    // range search (range.inc): scratch, and the results of the last search until knn_flat_range_fetch takes them
-    DevBuf ws_rq, ws_rqn, ws_rcnt, ws_rsegD, ws_rsegI, ws_roff, ws_routD, ws_routI, ws_rsel, ws_rq2, ws_rexp;
-    std::vector<float> range_D;
-    std::vector<int64_t> range_I;
-    int64_t range_qblocks = 0, range_redos = 0, range_redo_queries = 0; // query blocks, overflow rescans, queries rescanned
-    // refine (refine.inc): queries as uploaded / padded, labels, rescored keys, results; HIP-event times of the last call
-    DevBuf ws_rfq, ws_rfqp, ws_rfI, ws_rfkeys, ws_rfD, ws_rfI2;
-    float refine_ms[2] = {0.f, 0.f}; // rescore launches, final selections
-    float last_ms = 0.f;
-};
-
-// A view whose parent's storage has moved on (grown, reset, freed): its xb / yn went back to the pool.  Every entry point
-// that reads a handle's rows asks this first, before anything is copied or launched.
-static bool view_is_stale(const knn_index_s *h) { return h->is_view && h->storage_gen->load() != h->view_gen; }
-#define KNN_STALE_VIEW_MSG ": this view is stale (its parent index was grown, reset or freed after the view was made)"
-
-static int ensure_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return set_err(KNN_ERR_NO_DEVICE, "no HIP device available (libknn355 has no CPU fallback)");
-    if (device < 0 || device >= n) return set_err(KNN_ERR_INVALID, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    return 0;
-}
-
-extern "C" const char *knn_last_error(void) { return g_err.c_str(); }
-extern "C" const char *knn_version(void) { return "knn355 0.1 (gfx950)"; }
-extern "C" int knn_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-extern "C" int knn_init(int device)
-{
-    int rc = ensure_device(device);
-    if (rc) return rc;
-    g_device = device;
-    return 0;
-}
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-// ---- normalize ------------------------------------------------------------
-static int normalize_dev_impl(float *x, int64_t n, int d, int64_t stride, hipStream_t s)
-{
-    if (n == 0) return 0;
-    unsigned grid = (unsigned)((n + 63) / 64);
-    if ((stride % 4) == 0 && (((uintptr_t)x) % 16) == 0)
-        hipLaunchKernelGGL(normalize_rows_kernel<true>, dim3(grid), dim3(64), 0, s, x, n, d, stride);
-    else
-        hipLaunchKernelGGL(normalize_rows_kernel<false>, dim3(grid), dim3(64), 0, s, x, n, d, stride);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-static int norms_dev_impl(const float *x, int64_t n, int d, int64_t stride, float *out, hipStream_t s)
-{
-    if (n == 0) return 0;
-    unsigned grid = (unsigned)((n + 63) / 64);
-    if ((stride % 4) == 0 && (((uintptr_t)x) % 16) == 0)
-        hipLaunchKernelGGL(norm_rows_kernel<true>, dim3(grid), dim3(64), 0, s, x, n, d, stride, out);
-    else
-        hipLaunchKernelGGL(norm_rows_kernel<false>, dim3(grid), dim3(64), 0, s, x, n, d, stride, out);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-// dst[n][dp] <- src[n][d], zero padded, on stream s (both on the device)
-static int pad_rows_dev(const float *src, int64_t n, int d, float *dst, int dp, hipStream_t s)
-{
-    const unsigned grid = (unsigned)std::min<int64_t>((n * dp + 255) / 256, 65535);
-    hipLaunchKernelGGL(pad_rows_kernel, dim3(grid), dim3(256), 0, s, src, n, d, dst, dp);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-extern "C" int knn_normalize_l2_dev(float *x_dev, int64_t n, int32_t d, void *stream)
-{
-    if (n < 0 || d <= 0) return set_err(KNN_ERR_INVALID, "normalize_l2: bad shape");
-    int rc = normalize_dev_impl(x_dev, n, d, d, (hipStream_t)stream);
-    if (rc) return rc;
-    if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));
-    return 0;
-}
-
-extern "C" int knn_normalize_l2(float *x_host, int64_t n, int32_t d)
-{
-    if (n < 0 || d <= 0) return set_err(KNN_ERR_INVALID, "normalize_l2: bad shape");
-    if (n == 0) return 0;
-    if (!x_host) return set_err(KNN_ERR_INVALID, "normalize_l2: null pointer");
-    int rc = ensure_device(g_device);
-    if (rc) return rc;
-    // Two pooled device buffers (no hipMalloc / hipFree per call: the reference's scripts normalise per embedding file)
-    // and two streams taking turns in chunks of <= 64 MB: the download of chunk i overlaps the upload of chunk i + 1 (PCIe
-    // is full duplex).  (A caller that adds the rows to an index anyway should add them raw and use knn_flat_normalize_rows
-    // + knn_flat_reconstruct: one crossing each way -- pfam/proteins_search.py's flat mode does.)
-    const int64_t rows_per = std::max<int64_t>(1, (int64_t)(64ull << 20) / ((int64_t)d * 4));
-    const int64_t nbuf = std::min(n, rows_per);
-    const int lanes = n > nbuf ? 2 : 1;
-    // (the streams are declared behind the buffers: they go first, drained, whichever way the call returns)
-    const size_t bytes = (size_t)nbuf * d * 4;
-    PoolBuf buf0(bytes, g_device), buf1(lanes > 1 ? bytes : 0, g_device);
-    StreamLease st0(g_device), st1(g_device, lanes > 1);
-    if (!buf0 || !st0 || (lanes > 1 && (!buf1 || !st1))) return set_err(KNN_ERR_HIP, "normalize_l2: out of device memory");
-    float *buf[2] = {buf0.get<float>(), buf1.get<float>()};
-    const hipStream_t st[2] = {st0, st1};
-    int turn = 0;
-    for (int64_t i0 = 0; i0 < n; i0 += nbuf, turn ^= (lanes - 1)) {
-        const int64_t m = std::min(nbuf, n - i0);
-        hipError_t e = hipStreamSynchronize(st[turn]); // (this buffer's previous chunk is home)
-        if (e == hipSuccess) e = hipMemcpyAsync(buf[turn], x_host + i0 * d, (size_t)m * d * 4, hipMemcpyHostToDevice, st[turn]);
-        if (e == hipSuccess) {
-            rc = normalize_dev_impl(buf[turn], m, d, d, st[turn]);
-            if (rc) return rc;
-            e = hipMemcpyAsync(x_host + i0 * d, buf[turn], (size_t)m * d * 4, hipMemcpyDeviceToHost, st[turn]);
-        }
-        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("normalize_l2 copy: ") + hipGetErrorString(e));
-    }
-    for (int i = 0; i < lanes; i++) {
-        hipError_t e = hipStreamSynchronize(st[i]);
-        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("normalize_l2: ") + hipGetErrorString(e));
-    }
-    return 0;
-}
-
-// ---- index lifecycle ------------------------------------------------------
-extern "C" int knn_flat_create(int32_t d, int32_t metric, knn_handle *out)
-{
-    if (!out) return set_err(KNN_ERR_INVALID, "flat_create: null out");
-    if (d <= 0) return set_err(KNN_ERR_INVALID, "flat_create: d must be positive");
-    if (metric != KNN_METRIC_INNER_PRODUCT && metric != KNN_METRIC_L2)
-        return set_err(KNN_ERR_UNSUPPORTED, "flat_create: metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1)");
-    int rc = ensure_device(g_device);
-    if (rc) return rc;
-    knn_index_s *h = new knn_index_s();
-    h->d = d;
-    h->dp = round_up(d, 32);
-    h->metric = metric;
-    h->device = g_device;
-#ifdef KNN355_DEV
-    if (const char *e = getenv("KNN355_FLAGS")) h->flags = atoi(e); // (developer build only, A/B runs: the tuning flags every index starts with)
-#endif
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g_device) == hipSuccess && cus > 0) h->num_cus = cus;
-    }
-    if (!(h->stream = g_streams.take(h->device))) {
-        delete h;
-        return set_err(KNN_ERR_HIP, "flat_create: stream creation failed");
-    }
-    (void)hipEventCreateWithFlags(&h->done, hipEventDisableTiming); // (without it a growing buffer waits for the whole device)
-    *out = h;
-    return 0;
-}
-
-extern "C" int knn_flat_view(knn_handle parent, knn_handle *out)
-{
-    if (!parent || !out) return set_err(KNN_ERR_INVALID, "flat_view: null argument");
-    std::lock_guard<std::mutex> lk(parent->mu);
-    if (parent->approx16) return set_err(KNN_ERR_UNSUPPORTED, "flat_view: not for an approximate (bf16) index");
-    if (view_is_stale(parent)) return set_err(KNN_ERR_INVALID, "flat_view" KNN_STALE_VIEW_MSG); // (its xb / yn dangle: a copy of them must not pass for fresh)
-    HIP_TRY(hipSetDevice(parent->device));
-    knn_index_s *h = new knn_index_s();
-    h->flags = parent->flags;
-    h->pub_rounds_force = parent->pub_rounds_force;
-    h->force_qt = parent->force_qt;
-    h->force_chunks = parent->force_chunks;
-    h->d = parent->d;
-    h->dp = parent->dp;
-    h->metric = parent->metric;
-    h->device = parent->device;
-    h->num_cus = parent->num_cus;
-    h->is_view = true;
-    h->storage_gen = parent->storage_gen;
-    // a view of a live view goes stale together with it: the generation its rows were read at, not today's (the owner may have
-    // moved on between the check above and here)
-    h->view_gen = parent->is_view ? parent->view_gen : parent->storage_gen->load();
-    h->xb = parent->xb;
-    h->yn = parent->yn;
-    h->ntotal = parent->ntotal;
-    h->cap_rows = parent->ntotal;
-    h->scan16 = parent->scan16;
-    h->dp16 = parent->dp16;
-    h->s16_fmt = parent->s16_fmt;
-    h->s16_rows = parent->s16_rows;
-    h->s16_exp = parent->s16_exp;
-    h->s16_stat = parent->s16_stat;
-    h->s16_ok = parent->s16_ok;
-    h->s16_note = parent->s16_note;
-    if (!(h->stream = g_streams.take(h->device))) {
-        delete h;
-        return set_err(KNN_ERR_HIP, "flat_view: stream creation failed");
-    }
-    (void)hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
-    *out = h;
-    return 0;
-}
-
-static void free_index_buffers(knn_index_s *h)
-{
-    if (!h->is_view) h->storage_gen->fetch_add(1);
-    if (h->xb && !h->is_view) g_pool.give(h->xb, h->xb_bytes, h->device);
-    if (h->yn && !h->is_view) g_pool.give(h->yn, h->yn_bytes, h->device);
-    if (!h->is_view) {
-        h->s16_rows_buf.release();
-        h->s16_exp_buf.release();
-        h->s16_stat_buf.release();
-        if (h->scan16 == 2) h->scan16 = 1; // (dropped copies are tried again from the next add on)
-    }
-    h->s16_rows = nullptr;
-    h->s16_exp = nullptr;
-    h->s16_stat = nullptr;
-    if (!h->is_view) h->s16_ok->store(false);
-    h->xb = nullptr;
-    h->yn = nullptr;
-    h->ntotal = 0;
-    h->cap_rows = 0;
-}
-
-extern "C" void knn_free(knn_handle h)
-{
-    if (!h) return;
-    if (hipSetDevice(h->device) == hipSuccess) {
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        if (!h->is_view && h->xb) (void)hipDeviceSynchronize(); // a view's stream may still be scanning these rows
-        free_index_buffers(h);
-        DevBuf *bufs[] = {&h->xb16, &h->ws_q16, &h->ws_sym, &h->ws_qdiff, &h->ws_defer, &h->ws_turn, &h->ws_flag, &h->ws_q, &h->ws_qn, &h->ws_lists, &h->ws_D, &h->ws_I, &h->ws_tmp, &h->ws_tmp2, &h->ws_D1, &h->ws_I1, &h->ws_tmp3,
-                          &h->ws_rq, &h->ws_rqn, &h->ws_rcnt, &h->ws_rsegD, &h->ws_rsegI, &h->ws_roff, &h->ws_routD, &h->ws_routI, &h->ws_rsel, &h->ws_rq2, &h->ws_rexp,
-                          &h->ws_q16x, &h->ws_s16q, &h->ws_s16ak, &h->ws_s16ok, &h->ws_s16stat,
-                          &h->ws_rfq, &h->ws_rfqp, &h->ws_rfI, &h->ws_rfkeys, &h->ws_rfD, &h->ws_rfI2};
-        for (DevBuf *b : bufs) b->release();
-        for (LevelBufs &b : h->ws_level) {
-            b.qlist.release();
-            b.qcnt.release();
-            b.gthr.release();
-            b.qthr.release();
-            b.pub.release();
-            b.arrive.release();
-            b.pair_ctr.release();
-        }
-        for (int i = 0; i < knn_index_s::RING; i++) {
-            if (h->ring0[i]) (void)hipEventDestroy(h->ring0[i]);
-            if (h->ring1[i]) (void)hipEventDestroy(h->ring1[i]);
-        }
-        if (h->stream) g_streams.give(h->device, h->stream); // (synchronised above)
-        if (h->flag_host) (void)hipHostFree(h->flag_host);
-        if (h->done) (void)hipEventDestroy(h->done);
-    }
-    delete h;
-}
-
-extern "C" int64_t knn_ntotal(knn_handle h) { return h ? h->ntotal : -1; }
-extern "C" int32_t knn_dim(knn_handle h) { return h ? h->d : -1; }
-extern "C" int32_t knn_metric(knn_handle h) { return h ? h->metric : -1; }
-extern "C" int32_t knn_device_of(knn_handle h) { return h ? h->device : -1; }
-
-extern "C" int knn_reset(knn_handle h)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "reset: null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "reset: a view is read-only");
-    HIP_TRY(hipSetDevice(h->device));
-    free_index_buffers(h);
-    return 0;
-}
-
-// The handle's rows move to fresh storage of new_cap rows (> cap_rows; the caller holds h->mu and has set the device): the
-// common tail of grow_index and knn_flat_reserve.  A failure leaves the handle as it was, and the new buffers go back.
-static int move_storage(knn_index_s *h, int64_t new_cap, const char *who)
-{
-    const size_t row_bytes = (size_t)h->dp * 4;
-    PoolBuf bxb((size_t)new_cap * row_bytes, h->device);
-    if (!bxb) return set_err(KNN_ERR_HIP, std::string(who) + ": out of device memory");
-    PoolBuf byn(((size_t)new_cap + 64) * 4, h->device);
-    if (!byn) return set_err(KNN_ERR_HIP, std::string(who) + ": out of device memory");
-    float *nxb = bxb.get<float>(), *nyn = byn.get<float>();
-    auto copy = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(nxb, h->xb, (size_t)h->ntotal * row_bytes, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(nyn, h->yn, (size_t)h->ntotal * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        return 0;
-    };
-    if (h->ntotal > 0)
-        if (int rc = copy()) {
-            (void)hipStreamSynchronize(h->stream); // (a copy already queued writes a buffer that goes back to the pool)
-            return rc;
-        }
-    if (h->xb) {
-        h->storage_gen->fetch_add(1); // views of the old storage are dead
-        (void)hipDeviceSynchronize(); // ... and nothing may still be scanning it
-        g_pool.give(h->xb, h->xb_bytes, h->device);
-    }
-    if (h->yn) g_pool.give(h->yn, h->yn_bytes, h->device);
-    h->xb = (float *)bxb.release(&h->xb_bytes);
-    h->yn = (float *)byn.release(&h->yn_bytes);
-    h->cap_rows = new_cap;
-    return 0;
-}
-
-static int grow_index(knn_index_s *h, int64_t need_rows)
-{
-    if (need_rows <= h->cap_rows) return 0;
-    int64_t new_cap = std::max<int64_t>(need_rows, h->cap_rows + h->cap_rows / 2);
-    if (h->cap_rows == 0) new_cap = need_rows; // first add: exact fit (the reference adds once)
-    int rc = move_storage(h, new_cap, "add");
-    if (rc && new_cap > need_rows) rc = move_storage(h, need_rows, "add"); // (the guess was too large: the exact fit)
-    return rc;
-}
-
-// bf16 copies of rows [r0, r0 + n) of an approximate index (kept beside the fp32 rows: reconstruct, norms and the
-// exact re-scoring use those)
-static int approx16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s)
-{
-    if (!(h->approx16 || h->keep16) || n <= 0) return 0;
-    const size_t need = (size_t)h->cap_rows * h->dp * 2;
-    if (h->xb16.bytes < need) {
-        // (regrown with the fp32 storage: convert everything that is there)
-        if (h->xb16.ensure(need)) return set_err(KNN_ERR_HIP, "add: out of device memory (bf16 rows)");
-        n += r0;
-        r0 = 0;
-    }
-    const int64_t total = n * h->dp;
-    const unsigned grid = (unsigned)std::min<int64_t>((total / 4 + 255) / 256, 65535);
-    hipLaunchKernelGGL(to_bf16_kernel, dim3(grid), dim3(256), 0, s, h->xb + (size_t)r0 * h->dp, total, (__bf16 *)h->xb16.p + (size_t)r0 * h->dp);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// fp16 copies of rows [r0, r0 + n) for the exact 16-bit prefilter.  Storage that has to grow is rebuilt from all
-// rows, and r0 = 0 restarts the index-wide statistics.  Copies that cannot be allocated are dropped: the index goes on with its
-// fp32 scans.  Waits for the stream (adds are synchronous): whether every row is finite decides whether searches may use them.
-// Called with n = 0 by knn_flat_reserve: the copies grow with the fp32 rows.  Copies that move (or are dropped) make every
-// view of the index stale, as moved fp32 rows do: a view holds their addresses.
-static int scan16_sync_rows(knn_index_s *h, int64_t r0, int64_t n, hipStream_t s)
-{
-    if (h->scan16 != 1 || h->is_view) return 0;
-    // (12-bit copies: whole tiles of 256 rows, 1.5 bytes per value)
-    const size_t need = h->s16_fmt == 12 ? (size_t)((h->cap_rows + 255) / 256) * (h->dp16 / 64) * 24576 : (size_t)h->cap_rows * h->dp16 * 2;
-    if (h->cap_rows > 0 && (h->s16_rows_buf.bytes < need || h->s16_exp_buf.bytes < (size_t)h->cap_rows || !h->s16_stat_buf.p)) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (h->s16_rows_buf.p || h->s16_exp_buf.p) {
-            h->storage_gen->fetch_add(1); // (views of the old copies are dead ...)
-            (void)hipDeviceSynchronize(); // (... and nothing may still be scanning them: ensure() below hands them back to the pool)
-        }
-        if (h->s16_rows_buf.ensure(need) || h->s16_exp_buf.ensure((size_t)h->cap_rows) || h->s16_stat_buf.ensure(S16_NSTAT * 4)) {
-            h->s16_rows_buf.release();
-            h->s16_exp_buf.release();
-            h->s16_stat_buf.release();
-            h->s16_rows = nullptr;
-            h->s16_exp = nullptr;
-            h->s16_stat = nullptr;
-            h->s16_ok->store(false);
-            h->scan16 = 2;
-            h->s16_note = "dropped: no device memory for the row copies";
-            return 0;
-        }
-        n += r0;
-        r0 = 0;
-    }
-    if (n <= 0) return 0;
-    h->s16_rows = (const _Float16 *)h->s16_rows_buf.p;
-    h->s16_exp = (const int8_t *)h->s16_exp_buf.p;
-    h->s16_stat = (const uint32_t *)h->s16_stat_buf.p;
-    uint32_t init[S16_NSTAT] = {0u, 0u, 0u, 0x80000000u, 0u, 0u, 0u, 0u}; // (largest exponent: INT_MIN)
-    if (r0 == 0) HIP_TRY(hipMemcpyAsync(h->s16_stat_buf.p, init, sizeof init, hipMemcpyHostToDevice, s));
-    if (h->s16_fmt == 12)
-        hipLaunchKernelGGL(scan12_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->xb, h->dp, r0, n, h->dp16,
-                           (uint8_t *)h->s16_rows_buf.p, (int8_t *)h->s16_exp_buf.p, (uint32_t *)h->s16_stat_buf.p);
-    else
-        hipLaunchKernelGGL(scan16_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, h->xb, h->dp, r0, n, h->dp16,
-                           (_Float16 *)h->s16_rows_buf.p, (int8_t *)h->s16_exp_buf.p, (uint32_t *)h->s16_stat_buf.p);
-    HIP_TRY(hipGetLastError());
-    uint32_t nonfinite = 0;
-    HIP_TRY(hipMemcpyAsync(&nonfinite, (const uint32_t *)h->s16_stat_buf.p + S16_NONFINITE, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    h->s16_ok->store(nonfinite == 0);
-    h->s16_note = nonfinite ? "off: a row holds a value that is not finite" : "on";
-    return 0;
-}
-
-// before the first add and before knn_flat_reserve: the index multiplies bf16 copies (rows padded to a multiple of 64 values).
-// The row stride changes, so storage that was sized with the old one (reserve on an empty index) must not exist.
-static int flat_set_approx16(knn_index_s *h)
-{
-    if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "approx16: the index already holds rows");
-    if (h->cap_rows != 0 || h->xb) return set_err(KNN_ERR_INVALID, "approx16: the index already has storage (knn_flat_reserve): set it first, or knn_reset");
-    if (h->scan16) return set_err(KNN_ERR_UNSUPPORTED, "approx16: the index keeps fp16 copies for the 16-bit prefilter");
-    if (h->keep16) return set_err(KNN_ERR_UNSUPPORTED, "approx16: not for an index that keeps bf16 copies (HNSW)");
-    h->approx16 = true;
-    h->dp = round_up(h->d, 64);
-    return 0;
-}
-
-// the same for a caller's index: the way in for the tests of the bf16 builds (include/knn355.h)
-extern "C" int knn_flat_set_approx16(knn_handle h)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "set_approx16: null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "set_approx16: a view uses its parent's rows");
-    return flat_set_approx16(h);
-}
-
-// before the first add: bf16 copies of the rows are kept (the scans do not use them)
-static int flat_keep16(knn_index_s *h)
-{
-    if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "keep16: the index already holds rows");
-    if (h->scan16) return set_err(KNN_ERR_UNSUPPORTED, "keep16: the index keeps fp16 copies for the 16-bit prefilter");
-    h->keep16 = true;
-    return 0;
-}
-
-// appends rows that already live on the device ([n][d], contiguous)
-static int add_dev_impl(knn_index_s *h, const float *x_dev, int64_t n, hipStream_t s)
-{
-    float *dst = h->xb + (size_t)h->ntotal * h->dp;
-    if (h->dp == h->d) {
-        HIP_TRY(hipMemcpyAsync(dst, x_dev, (size_t)n * h->d * 4, hipMemcpyDeviceToDevice, s));
-    } else {
-        int rc = pad_rows_dev(x_dev, n, h->d, dst, h->dp, s);
-        if (rc) return rc;
-    }
-    // norms are kept for both metrics: reconstruct/HNSW-L2 need them and they cost one pass
-    int rc = norms_dev_impl(dst, n, h->d, h->dp, h->yn + h->ntotal, s);
-    if (rc) return rc;
-    rc = approx16_sync_rows(h, h->ntotal, n, s);
-    if (rc) return rc;
-    rc = scan16_sync_rows(h, h->ntotal, n, s);
-    if (rc) return rc;
-    h->ntotal += n;
-    return 0;
-}
-
-extern "C" int knn_flat_add_dev(knn_handle h, const float *x_dev, int64_t n, void *stream)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "add: null handle");
-    if (n < 0) return set_err(KNN_ERR_INVALID, "add: negative n");
-    if (n == 0) return 0;
-    if (!x_dev) return set_err(KNN_ERR_INVALID, "add: null pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "add: a view is read-only");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->ntotal + n > 0xFFFFFFF0ll) return set_err(KNN_ERR_UNSUPPORTED, "add: more than 2^32 rows per index");
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    if (stream) HIP_TRY(hipStreamSynchronize(h->stream));
-    int rc = grow_index(h, h->ntotal + n);
-    if (rc) return rc;
-    rc = add_dev_impl(h, x_dev, n, s);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
-
-extern "C" int knn_flat_add(knn_handle h, const float *x_host, int64_t n)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "add: null handle");
-    if (n < 0) return set_err(KNN_ERR_INVALID, "add: negative n");
-    if (n == 0) return 0;
-    if (!x_host) return set_err(KNN_ERR_INVALID, "add: null pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "add: a view is read-only");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->ntotal + n > 0xFFFFFFF0ll) return set_err(KNN_ERR_UNSUPPORTED, "add: more than 2^32 rows per index");
-    int rc = grow_index(h, h->ntotal + n);
-    if (rc) return rc;
-    if (h->dp == h->d) {
-        float *dst = h->xb + (size_t)h->ntotal * h->dp;
-        HIP_TRY(hipMemcpy(dst, x_host, (size_t)n * h->d * 4, hipMemcpyHostToDevice));
-        rc = norms_dev_impl(dst, n, h->d, h->dp, h->yn + h->ntotal, h->stream);
-        if (rc) return rc;
-        rc = approx16_sync_rows(h, h->ntotal, n, h->stream);
-        if (rc) return rc;
-        rc = scan16_sync_rows(h, h->ntotal, n, h->stream);
-        if (rc) return rc;
-        h->ntotal += n;
-    } else {
-        const int64_t rows_per = std::max<int64_t>(1, (int64_t)(256ull << 20) / ((int64_t)h->d * 4));
-        if (h->ws_tmp.ensure((size_t)std::min(n, rows_per) * h->d * 4)) return set_err(KNN_ERR_HIP, "add: out of device memory");
-        for (int64_t i0 = 0; i0 < n; i0 += rows_per) {
-            int64_t m = std::min(rows_per, n - i0);
-            HIP_TRY(hipMemcpy(h->ws_tmp.p, x_host + i0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice));
-            rc = add_dev_impl(h, (const float *)h->ws_tmp.p, m, h->stream);
-            if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(h->stream));
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int knn_flat_reconstruct(knn_handle h, int64_t i0, int64_t n, float *out_host)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "reconstruct: null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "reconstruct" KNN_STALE_VIEW_MSG);
-    if (i0 < 0 || n < 0 || i0 + n > h->ntotal) return set_err(KNN_ERR_INVALID, "reconstruct: range out of bounds");
-    if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpy2D(out_host, (size_t)h->d * 4, h->xb + (size_t)i0 * h->dp, (size_t)h->dp * 4, (size_t)h->d * 4,
-                        (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// one workgroup per query: best k of its candidate keys (see select_topk_kernel).  tmp: scratch for the segment
-// pass of arrays longer than one workgroup's registers hold.
-static const int KNN_SELECT_SEG = 32768;
-static int launch_select(SelectParams sp, hipStream_t s, DevBuf *tmp = nullptr)
-{
-    if (sp.nq <= 0) return 0;
-    // (an array whose CAPACITY is larger but which is expected to hold far fewer keys -- the compact arrays of an
-    // exactly seeded scan are sized for the worst case of every chunk -- goes straight to the one-launch selection:
-    // 32768 keys fit its registers, a longer array is re-read from L2 on every probe)
-    const bool expect_short = sp.n_expect > 0 && sp.n_expect <= 24576;
-    if (tmp && sp.lm_lists == 0 && sp.cnt && sp.cap > KNN_SELECT_SEG && !expect_short) {
-        // Arrays of up to `cap` > 32768 keys (a seed sample of a 10 M-row database hands on 39 k scores per
-        // query): workgroup (q, s) reduces segment s of query q to its kk = kmax best keys in registers, then
-        // one more launch selects among the nseg * kk survivors -- two launches instead of re-reading the
-        // array from L2 on every probe.
-        const int kk = sp.k + std::max(sp.k >> 2, 32);
-        const int nseg = (sp.cap + KNN_SELECT_SEG - 1) / KNN_SELECT_SEG;
-        if (tmp->ensure((size_t)sp.nq * nseg * kk * 8)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        SelectParams a = {};
-        a.in = sp.in; a.in_stride = sp.in_stride; a.cnt = sp.cnt; a.cap = sp.cap;
-        a.seg_len = KNN_SELECT_SEG; a.nseg = nseg;
-        a.nq = sp.nq; a.k = kk; a.metric = sp.metric;
-        a.out_keys = (uint64_t *)tmp->p; a.out_stride = kk; a.out_fill = 0;
-        a.gate = sp.gate; a.gate_n = sp.gate_n;
-        const size_t lds = (size_t)next_pow2_host(kk + std::max(kk >> 2, 32)) * 8;
-        hipLaunchKernelGGL((select_topk_kernel<32, 1024, false>), dim3((unsigned)sp.nq, (unsigned)nseg), dim3(1024), lds, s, a);
-        HIP_TRY(hipGetLastError());
-        sp.in = (const uint64_t *)tmp->p;
-        sp.in_stride = (int64_t)nseg * kk;
-        sp.cnt = nullptr;
-        sp.n_fixed = nseg * kk;
-        sp.cap = nseg * kk;
-        sp.n_expect = 0;
-    }
-    const bool seed = sp.seed_cnt != nullptr;
-    const int kmax = sp.k + std::max(sp.k >> 2, 32);
-    const size_t lds = seed ? 0 : (size_t)next_pow2_host(kmax) * 8;
-    const int nmax = sp.lm_lists > 0 ? sp.lm_lists * sp.lm_k : (sp.cnt ? sp.cap : sp.n_fixed);
-    void (*kern)(SelectParams);
-    int nt = 256;
-    // Many queries with short candidate arrays (the batch regime): ONE WAVE per query -- four times the queries
-    // in flight per CU, and the kernel is bound by the latency of its dependent loads, not by arithmetic
-    // (14433 queries x ~1400 keys: 265 us with a workgroup per query).  Few queries with long arrays (the
-    // streaming regime): a workgroup per query, up to 32768 keys in registers.  Arrays longer than the
-    // registers of the chosen build hold are re-read from L2 on every probe.
-    const int nexp = sp.n_expect > 0 ? std::min(sp.n_expect, nmax) : nmax;
-    if (sp.nq >= 512 && nexp <= 64 * 32) {
-        nt = 64;
-        if (seed) kern = nexp <= 64 * 8 ? select_topk_kernel<8, 64, true> : select_topk_kernel<32, 64, true>;
-        else kern = nexp <= 64 * 8 ? select_topk_kernel<8, 64, false> : select_topk_kernel<32, 64, false>;
-    } else if (seed) {
-        if (nmax <= 256 * 4) kern = select_topk_kernel<4, 256, true>;
-        else if (nmax <= 256 * 16) kern = select_topk_kernel<16, 256, true>;
-        else if (nmax <= 256 * 32) kern = select_topk_kernel<32, 256, true>;
-        else { kern = select_topk_kernel<32, 1024, true>; nt = 1024; }
-    } else {
-        // (by the EXPECTED count when the arrays carry their own: the compact arrays of a seeded scan are sized for the worst
-        // case of every chunk -- 64 k slots per query on a 1.25 M-row shard -- and hold 1-2 k keys; the 1024-thread build
-        // took 32-36 us for them, its probes are workgroup-wide reductions over 16 waves)
-        const int nsel = sp.cnt ? nexp : nmax;
-        if (nsel <= 256 * 4) kern = select_topk_kernel<4, 256, false>;
-        else if (nsel <= 256 * 16) kern = select_topk_kernel<16, 256, false>;
-        else if (nsel <= 256 * 32) kern = select_topk_kernel<32, 256, false>;
-        else { kern = select_topk_kernel<32, 1024, false>; nt = 1024; }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)sp.nq), dim3(nt), lds, s, sp);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Which pass of a prefiltered search (search_view_s16) a search_view call enqueues, and what that pass reads.  The default is
-// a plain search.
-struct S16Pass {
-    int mode = 0;                    // 0 plain, 1 the 16-bit pass, 2 the gated fp32 fallback
-    const int *qexp = nullptr;       // 1: the fp16 queries' exponents
-    const uint32_t *gate = nullptr;  // 2: the per-query fallback flags [gate_n] (ScanParams::gate)
-    int gate_n = 0;
-    uint32_t *gate_count = nullptr;  // 2: counts the fallbacks taken (SelectParams::gate_count)
-};
-
-typedef void (*ScanKernel)(ScanParams);
-
-// a scan build's opt-in to lds bytes of dynamic LDS: once in front of the launch(es) of a search
-static int scan_lds_opt_in(ScanKernel kern, size_t lds)
-{
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return 0;
-}
-
-// one scan launch: grid workgroups of 256 threads with lds bytes of dynamic LDS
-static int launch_scan(ScanKernel kern, const ScanParams &p, int grid, size_t lds, hipStream_t s)
-{
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// the builds of one wave layout: fp32 or bf16 rows; one query tile (rows are read once, non-temporal staging loads) or several
-template <int WM, int WN, int TM, int TN>
-static ScanKernel scan_build(bool l2, bool approx16, bool one_qtile)
-{
-    if (approx16) {
-        if (one_qtile) return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, true, false, true>;
-        return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false, false, true> : flat_scan_kernel<WM, WN, TM, TN, false, false, false, true>;
-    }
-    if (one_qtile) return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, true> : flat_scan_kernel<WM, WN, TM, TN, false, true>;
-    return l2 ? flat_scan_kernel<WM, WN, TM, TN, true, false> : flat_scan_kernel<WM, WN, TM, TN, false, false>;
-}
-
-// The flat_scan_kernel build that serves a launch: query tile qt, squared L2 or inner product, bf16 rows, one query tile or
-// several, the width of the difference build (0: none), the pass of a prefiltered search (S16Pass::mode).  nullptr with the
-// error set when no build serves the combination (scan_kernel_illegal, plan.h).
-static ScanKernel pick_scan_kernel(int qt, bool l2, bool approx16, bool one_qtile, int diff_width, int pass_mode, int s16_fmt = 16)
-{
-    if (const char *why = scan_kernel_illegal(qt, l2, approx16, one_qtile, pass_mode)) {
-        set_err(KNN_ERR_INVALID, why);
-        return nullptr;
-    }
-    switch (qt) {
-    case 256: return l2 ? flat_scan_kernel<2, 2, 4, 4, true, false> : flat_scan_kernel<2, 2, 4, 4, false, false>;
-    case 128: return scan_build<2, 2, 2, 2>(l2, approx16, one_qtile);
-    // (16-query blocks, three per wave)
-    case 96: return l2 ? flat_scan_kernel<2, 2, 2, 1, true, true, false, false, 0, 3> : flat_scan_kernel<2, 2, 2, 1, false, true, false, false, 0, 3>;
-    case 48: return l2 ? flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 0, 3> : flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 3>;
-    case 64: return scan_build<2, 2, 2, 1>(l2, approx16, one_qtile);
-    }
-    if (pass_mode == 1 && s16_fmt == 12) return flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true, true>; // ... on the 12-bit row copies
-    if (pass_mode == 1) return flat_scan_kernel<4, 1, 2, 1, false, true, false, false, 0, 0, true>; // the 16-bit pass of a prefiltered search (search_view_s16)
-    // (difference builds for up to 8, 12, 16 and 19 queries: the vector work of a K step grows with the build's width -- up to 8
-    // queries scan at the speed of their HBM traffic)
-    switch (diff_width) {
-    case 0: break;
-    case 8: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 8>;
-    case 12: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 12>;
-    case 16: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 16>;
-    default: return flat_scan_kernel<4, 1, 2, 1, true, true, false, false, 20>;
-    }
-    return scan_build<4, 1, 2, 1>(l2, approx16, one_qtile);
-}
-
-// the build of a symmetric launch (SymPlan): square tiles of ts = 128 or 256 rows
-static ScanKernel pick_sym_kernel(int ts, bool l2)
-{
-    if (ts == 128) return l2 ? flat_scan_kernel<2, 2, 2, 2, true, false, true> : flat_scan_kernel<2, 2, 2, 2, false, false, true>;
-    return l2 ? flat_scan_kernel<2, 2, 4, 4, true, false, true> : flat_scan_kernel<2, 2, 4, 4, false, false, true>;
-}
-
-// opens a timed launch on s: the next pair of the ring of timing events becomes ev0 / ev1, ev0 is recorded; the caller records
-// ev1 behind its launch(es)
-static int open_timed_launch(knn_index_s *h, hipStream_t s)
-{
-    const int slot = (int)(h->nlaunches % knn_index_s::RING);
-    if (!h->ring0[slot]) {
-        HIP_TRY(hipEventCreate(&h->ring0[slot]));
-        HIP_TRY(hipEventCreate(&h->ring1[slot]));
-    }
-    h->ev0 = h->ring0[slot];
-    h->ev1 = h->ring1[slot];
-    h->nlaunches++;
-    HIP_TRY(hipEventRecord(h->ev0, s));
-    return 0;
-}
-
-// the words the two workgroups of a CU take turns with (ScanParams::cu_turn), all zero
-static int zeroed_turn_words(knn_index_s *h, hipStream_t s, uint32_t **words)
-{
-    if (h->ws_turn.ensure(2048 * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-    if (h->turn_zeroed != h->ws_turn.p) { // (once per allocation: a fill in front of every launch was 10 us of idle GPU per CATH-sized search)
-        HIP_TRY(hipMemsetAsync(h->ws_turn.p, 0, 2048 * 4, s));
-        h->turn_zeroed = h->ws_turn.p;
-    }
-    *words = (uint32_t *)h->ws_turn.p;
-    return 0;
-}
-
-// where the result of a (view) search goes
-struct SearchOut {
-    uint64_t *keys = nullptr; // sorted keys, k per query
-    int64_t keys_stride = 0;
-    int keys_fill = 0;
-    float *D = nullptr;
-    int64_t *I = nullptr;
-    // seeding the enclosing search (see SelectParams)
-    uint32_t *seed_cnt = nullptr, *seed_gthr = nullptr, *seed_qthr = nullptr;
-    int seed_j = 0, seed_stat = 0;
-    int64_t seed_nslots = 0;
-};
-
-// ---- the exact 16-bit prefilter ----------------------------------------------------------------------------
-static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int row_mul,
-                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag = nullptr,
-                       const S16Pass &pass = S16Pass());
-
-// what the planner (plan.h) reads from a handle
-static PlanCtx plan_ctx(const knn_index_s *h)
-{
-    PlanCtx c;
-    c.metric = h->metric; c.approx16 = h->approx16;
-    c.flags = h->flags; c.force_qt = h->force_qt; c.force_chunks = h->force_chunks;
-    c.num_cus = h->num_cus; c.batch_nq = h->batch_nq; c.pub_rounds_force = h->pub_rounds_force; c.ntotal = h->ntotal;
-    c.s16_fmt = h->s16_fmt;
-    return c;
-}
-
-// One prefiltered search, ten launches on the caller's stream, no host wait:
-//   scan16_queries_kernel   fp16 queries, exponents, bounds B_q, the per-query fallback flags
-//   16-bit pass             the streaming scan machinery on the fp16 (or 12-bit) copies with k' = s16_kprime(k, format): the exact
-//                           top-k' of the approximate scores (state reset, flat_scan_q32_d256_f16x / _x12, selection in two launches)
-//   rescore16_kernel        the window check and the exact scores of the rows inside the window: a grid of (query, 16 of its
-//                           k' keys), every row fetched by a whole workgroup with coalesced 16-byte loads
-//   selection               the exact top-k of those -> D / I or keys, exactly as the fp32 search writes them
-//   gated fp32 search       state reset, scan, selection of the plain search, each returning at once unless some query's
-//                           flag is set -- then it overwrites the output with the plain search's bits
-static int search_view_s16(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int vshift,
-                           const SearchOut &out, hipStream_t s, int *reset_flag)
-{
-    const int kp = s16_kprime(k, h->s16_fmt);
-    if (h->ws_q16x.ensure((size_t)nq * h->dp16 * 2, h->done, s) || h->ws_s16q.ensure((size_t)nq * 16, h->done, s) ||
-        h->ws_s16ak.ensure((size_t)nq * kp * 8, h->done, s) || h->ws_s16ok.ensure((size_t)nq * kp * 8, h->done, s))
-        return set_err(KNN_ERR_HIP, "search: out of device memory");
-    if (!h->ws_s16stat.p) {
-        if (h->ws_s16stat.ensure(16)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        HIP_TRY(hipMemsetAsync(h->ws_s16stat.p, 0, 16, s));
-    }
-    _Float16 *q16 = (_Float16 *)h->ws_q16x.p;
-    int *qexp = (int *)h->ws_s16q.p;
-    float *Bq = (float *)(qexp + nq);
-    uint32_t *pfail = (uint32_t *)(Bq + nq), *rfail = pfail + nq;
-    uint32_t *sstat = (uint32_t *)h->ws_s16stat.p;
-    hipLaunchKernelGGL(scan16_queries_kernel, dim3((unsigned)nq), dim3(64), 0, s, q_dev, h->dp, h->dp16, q16, qexp, Bq, pfail, h->s16_stat, sstat,
-                       h->s16_pieces == 0 ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    SearchOut ao;
-    ao.keys = (uint64_t *)h->ws_s16ak.p; ao.keys_stride = kp; ao.keys_fill = 0;
-    S16Pass f16;
-    f16.mode = 1;
-    f16.qexp = qexp;
-    int rc = search_view(h, (const float *)q16, nullptr, nq, kp, id_base, 1, vshift, 0, ao, false, s, reset_flag, f16);
-    if (rc) return rc;
-    const size_t rlds = rescore16_lds(h->dp);
-    HIP_TRY(hipFuncSetAttribute((const void *)rescore16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); // (above 64 KB from dp = 1024 on)
-    hipLaunchKernelGGL(rescore16_kernel, dim3((unsigned)nq, (unsigned)((kp + RS16_ROWS - 1) / RS16_ROWS)), dim3(256), rlds, s, (const uint64_t *)h->ws_s16ak.p,
-                       kp, k, Bq, pfail, rfail, h->xb, h->dp, q_dev, id_base, (uint64_t *)h->ws_s16ok.p, sstat);
-    HIP_TRY(hipGetLastError());
-    SelectParams sp = {};
-    sp.in = (const uint64_t *)h->ws_s16ok.p; sp.in_stride = kp; sp.n_fixed = kp; sp.cap = kp; sp.n_expect = kp;
-    sp.nq = nq; sp.k = k; sp.metric = h->metric;
-    sp.out_keys = out.keys; sp.out_stride = out.keys ? out.keys_stride : 0; sp.out_fill = out.keys_fill;
-    sp.D = out.D; sp.I = out.I;
-    rc = launch_select(sp, s);
-    if (rc) return rc;
-    S16Pass gated;
-    gated.mode = 2;
-    gated.gate = rfail;
-    gated.gate_n = (int)nq;
-    gated.gate_count = sstat + 1;
-    rc = search_view(h, q_dev, xn, nq, k, id_base, 1, vshift, 0, out, false, s, nullptr, gated);
-    h->last_s16_used = true;
-    h->last_s16_fmt = h->s16_fmt;
-    h->s16_pieces++;
-    return rc;
-}
-
-// Exact top-k of the block-strided view (view_row) with stride row_mul / block shift vshift for
-// queries [nq][dp] on the device.  allow_stat: the caller checks h->ws_flag afterwards.  pass: the pass of a prefiltered
-// search this is (search_view_s16), handed on unchanged to the seed sample's search.
-static int search_view(knn_index_s *h, const float *q_dev, const float *xn, int64_t nq, int k, uint32_t id_base, int row_mul,
-                       int vshift, int level, const SearchOut &out, bool allow_stat, hipStream_t s, int *reset_flag, const S16Pass &pass)
-{
-    const int64_t nb = view_rows(h->ntotal, row_mul, vshift);
-    const PlanCtx c = plan_ctx(h);
-    if (h->scan16 == 1 && h->s16_ok->load() && h->s16_rows && !out.seed_cnt && s16_eligible(c, pass.mode, nb, nq, k, row_mul, level, h->dp, h->s16_fmt))
-        return search_view_s16(h, q_dev, xn, nq, k, id_base, vshift, out, s, reset_flag);
-    if (level >= knn_index_s::MAX_LEVELS) return set_err(KNN_ERR_INVALID, "search: seed recursion too deep");
-    const SearchPlan plan = plan_search(c, nb, nq, k, level, row_mul, allow_stat, pass.mode);
-    const ScanPlan &pl = plan.pl;
-    const int sstride = plan.sstride, svshift = plan.svshift < 0 ? vshift : plan.svshift, seed_stat = plan.seed_stat;
-    const int pub_rounds = plan.pub_rounds, pub_m = plan.pub_m, qcap = plan.qcap;
-    LevelBufs &lb = h->ws_level[level];
-    uint64_t reset_sig = 0; // != 0: this search's final selection resets the level's state for a successor of the same shape
-    const size_t nslots = (size_t)pl.nqtiles * pl.qt;
-    if (lb.qlist.ensure((size_t)nq * qcap * 8, h->done, s) || lb.qcnt.ensure((size_t)nq * 4, h->done, s) || lb.gthr.ensure(nslots * 4, h->done, s) || lb.qthr.ensure((size_t)nq * 4, h->done, s))
-        return set_err(KNN_ERR_HIP, "search: out of device memory");
-    uint64_t *qlist = (uint64_t *)lb.qlist.p;
-    uint32_t *qcnt = (uint32_t *)lb.qcnt.p, *gthr = (uint32_t *)lb.gthr.p, *qthr = (uint32_t *)lb.qthr.p;
-    int rc;
-    if (sstride) {
-        lb.clean_sig = 0;
-        // the sample's sorted top-k opens every query's candidate array; its seed_j-th score is the
-        // running threshold the main pass starts from
-        SearchOut so;
-        so.keys = qlist; so.keys_stride = qcap; so.keys_fill = 0;
-        so.seed_cnt = qcnt; so.seed_gthr = gthr; so.seed_qthr = qthr; so.seed_j = plan.seed_j; so.seed_stat = seed_stat;
-        so.seed_nslots = (int64_t)nslots;
-        rc = search_view(h, q_dev, xn, nq, plan.k_sample, id_base, row_mul * sstride, svshift, level + 1, so, false, s, reset_flag, pass);
-        if (rc) return rc;
-    } else {
-        const int64_t nn = std::max<int64_t>((int64_t)nslots, nq);
-        uint64_t *pub = nullptr;
-        uint32_t *arrive = nullptr;
-        const int64_t npub = (int64_t)nslots * pub_rounds * pl.nchunks * pub_m;
-        if (pub_rounds) {
-            if (lb.pub.ensure((size_t)npub * 8, h->done, s) || lb.arrive.ensure((size_t)pl.nqtiles * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-            pub = (uint64_t *)lb.pub.p;
-            arrive = (uint32_t *)lb.arrive.p;
-        }
-        // (the first launch of a search: it also clears the verification flag)
-        if (pl.npairs && lb.pair_ctr.ensure(((size_t)pl.npairs + 1) * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        // A streaming search whose predecessor on this handle had exactly this shape finds the state already reset: that
-        // search's final selection did it (SelectParams::rs_*) -- one launch and a ~10 us launch gap less per step.
-        if (pub_rounds && pl.npairs && !(h->flags & KNN_TUNE_ALWAYS_RESET) && !pass.mode) { // (not inside a prefiltered search: its two passes differ in shape)
-            uint64_t sig = 0x9E3779B97F4A7C15ull;
-            const uint64_t parts[] = {(uint64_t)nslots, (uint64_t)nq, (uint64_t)npub, (uint64_t)pl.nqtiles, (uint64_t)pl.npairs, (uint64_t)(uintptr_t)gthr,
-                                      (uint64_t)(uintptr_t)qcnt, (uint64_t)(uintptr_t)qthr, (uint64_t)(uintptr_t)pub, (uint64_t)(uintptr_t)arrive,
-                                      (uint64_t)(uintptr_t)lb.pair_ctr.p, (uint64_t)(uintptr_t)h->ws_flag.p};
-            for (uint64_t v : parts) sig = (sig ^ v) * 0x100000001B3ull;
-            reset_sig = sig ? sig : 1;
-        }
-        if (!(reset_sig && lb.clean_sig == reset_sig)) {
-            hipLaunchKernelGGL(init_level_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, gthr, (int64_t)nslots, qcnt, qthr, nq,
-                               reset_flag, pub, npub, arrive, (int64_t)pl.nqtiles, pl.npairs ? (uint32_t *)lb.pair_ctr.p : nullptr, (int64_t)pl.npairs,
-                               pass.gate, pass.gate_n);
-            HIP_TRY(hipGetLastError());
-        }
-        lb.clean_sig = 0; // (until this search's own selection has been enqueued)
-    }
-    if (pl.npairs && sstride) { // (the sample's own search initialised this level: the pairs' ticket counters are left)
-        if (lb.pair_ctr.ensure(((size_t)pl.npairs + 1) * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)lb.pair_ctr.p, 2, (size_t)pl.npairs, s));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)lb.pair_ctr.p + pl.npairs), 0, 1, s));
-    }
-    if (h->ws_lists.ensure((size_t)pl.grid * pl.qt * pl.cap * 8, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory (candidate lists)");
-    ScanParams p = {};
-    p.xb = h->xb; p.yn = h->yn; p.xq = q_dev; p.xn = xn;
-    p.nb = nb; p.nq = nq; p.dp = h->dp; p.k = k; p.cap = pl.cap;
-    if (h->approx16) { // bf16 rows and queries: a row is dp / 2 four-byte units
-        p.xb = (const float *)h->xb16.p;
-        p.dp = h->dp / 2;
-    }
-    if (pass.mode == 1) { // the 16-bit pass: fp16 rows and queries (q_dev), a row is dp16 / 2 four-byte units
-        // (the 12-bit build addresses whole tiles of consecutive rows: plan_search gives its pass no sample, and nothing else strides it)
-        if (h->s16_fmt == 12 && (row_mul != 1 || sstride)) return set_err(KNN_ERR_INVALID, "search: the 12-bit row copies cannot serve a strided view");
-        p.xb = (const float *)h->s16_rows;
-        p.dp = h->dp16 / 2;
-        p.xexp = h->s16_exp;
-        p.qexp = pass.qexp;
-    }
-    p.gate = pass.gate; // (a gated fallback)
-    p.gate_n = pass.gate_n;
-    p.nqtiles = pl.nqtiles; p.nchunks = pl.nchunks; p.tiles_base = pl.tiles_base; p.tiles_rem = pl.tiles_rem;
-    p.lists = (uint64_t *)h->ws_lists.p; p.gthr = gthr;
-    p.qlist = qlist; p.qcnt = qcnt; p.qcap = qcap;
-    p.id_base = id_base;
-    p.row_mul = row_mul;
-    p.vshift = sstride ? svshift : vshift;
-    p.skip_mask = sstride ? sstride - 1 : -1;
-    p.kslot = plan.kslot;
-    p.sparse_epi = plan.sparse_epi;
-    p.pub = pub_rounds ? (uint64_t *)lb.pub.p : nullptr;
-    p.arrive = pub_rounds ? (uint32_t *)lb.arrive.p : nullptr;
-    p.pub_rounds = pub_rounds;
-    p.pub_n = pub_rounds * pl.nchunks * pub_m;
-    p.pub_m = pub_m;
-    p.pair_ctr = pl.npairs ? (uint32_t *)lb.pair_ctr.p : nullptr;
-    p.npairs = pl.npairs;
-    if (pl.diff) {
-        const int dnq = diff_build_width(nq); // (the build pick_scan_kernel picks)
-        if (h->ws_qdiff.ensure((size_t)dnq * h->dp * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        const int64_t tot = (int64_t)dnq * h->dp;
-        hipLaunchKernelGGL(diff_interleave_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, q_dev, nq, h->dp, dnq, (float *)h->ws_qdiff.p);
-        HIP_TRY(hipGetLastError());
-        p.xq_diff = (const float *)h->ws_qdiff.p;
-    }
-    if (plan.cu_turn && (rc = zeroed_turn_words(h, s, &p.cu_turn))) return rc;
-    p.pool_tiles = plan.pool_tiles;
-    if (pub_rounds) {
-        if (h->ws_defer.ensure((size_t)pl.grid * pl.qt * pl.dt * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        p.defer = (float *)h->ws_defer.p;
-    }
-    const bool top = level == 0 && pass.mode != 2; // (a gated fallback leaves the introspection to the 16-bit pass)
-#ifdef KNN355_TRACE
-    if (level == (getenv("KNN355_TRACE_LEVEL") ? atoi(getenv("KNN355_TRACE_LEVEL")) : 0)) { // (developer build: which seed level's launch is stamped)
-        if (g_trace_buf.ensure((size_t)pl.grid * 128 * 8)) return set_err(KNN_ERR_HIP, "trace: out of device memory");
-        HIP_TRY(hipMemsetAsync(g_trace_buf.p, 0, (size_t)pl.grid * 128 * 8, s));
-        p.trace = (unsigned long long *)g_trace_buf.p;
-        p.ablate = getenv("KNN355_ABLATE") ? atoi(getenv("KNN355_ABLATE")) : 0;
-        g_trace_grid = pl.grid;
-    }
-#endif
-    if (top && (rc = open_timed_launch(h, s))) return rc;
-    const ScanKernel kern = pick_scan_kernel(pl.qt, h->metric == KNN_METRIC_L2, h->approx16, pl.nqtiles == 1, pl.diff ? diff_build_width(nq) : 0, pass.mode, h->s16_fmt);
-    if (!kern) return KNN_ERR_INVALID;
-    rc = scan_lds_opt_in(kern, pl.lds);
-    if (!rc) rc = launch_scan(kern, p, pl.grid, pl.lds, s);
-    if (rc) return rc;
-    if (top) {
-        HIP_TRY(hipEventRecord(h->ev1, s));
-        h->last_kernel = pass.mode == 1 ? std::string(pl.name) + (h->s16_fmt == 12 ? "_x12" : "_f16x") : std::string(pl.name); h->last_qt = pl.qt; h->last_dt = pl.dt; h->last_chunks = pl.nchunks; h->last_grid = pl.grid;
-        h->last_seed_stride = pub_rounds ? -pub_rounds * pub_m : sstride; // (negative: tile-minimum seed, keys per workgroup and query)
-        h->last_seed_stat = seed_stat ? plan.seed_j : 0;
-        h->last_sample_rows = sstride ? view_rows(nb, sstride, p.vshift) : 0;
-    }
-    // final selection: every query's candidates (seed list + the chunks' survivors) -> sorted top-k
-    SelectParams sp = {};
-    sp.in = qlist; sp.in_stride = qcap; sp.cnt = qcnt; sp.cap = qcap;
-    sp.n_expect = select_expect_n(plan, nb, k, sstride ? view_rows(nb, sstride, p.vshift) : 0);
-    sp.nq = nq; sp.k = k; sp.metric = h->metric;
-    sp.out_keys = out.keys; sp.out_stride = out.keys ? out.keys_stride : 0; sp.out_fill = out.keys_fill;
-    sp.D = out.D; sp.I = out.I;
-    sp.seed_cnt = out.seed_cnt; sp.seed_gthr = out.seed_gthr; sp.seed_qthr = out.seed_qthr; sp.seed_j = out.seed_j; sp.seed_stat = out.seed_stat;
-    sp.seed_nslots = out.seed_nslots;
-    sp.qthr = qthr; sp.fail = (int *)h->ws_flag.p;
-    sp.gate = pass.gate; sp.gate_n = pass.gate_n; sp.gate_count = pass.gate_count;
-    if (reset_sig && out.seed_cnt == nullptr) {
-        sp.rs_gthr = gthr; sp.rs_qcnt = qcnt; sp.rs_qthr = qthr; sp.rs_nslots = (int)nslots;
-        sp.rs_pub = (uint64_t *)lb.pub.p; sp.rs_pub_n = pub_rounds * pl.nchunks * pub_m;
-        sp.rs_arrive = (uint32_t *)lb.arrive.p; sp.rs_narrive = pl.nqtiles;
-        sp.rs_pair = (uint32_t *)lb.pair_ctr.p; sp.rs_npairs = pl.npairs;
-    }
-    rc = launch_select(sp, s, &h->ws_tmp);
-    if (!rc && sp.rs_gthr) lb.clean_sig = reset_sig;
-    if (level == 0 && h->done) (void)hipEventRecord(h->done, s); // (everything this search enqueued: see DevBuf::ensure)
-    return rc;
-}
-
-// queries [nq][dp] already on device (padded); writes sorted keys [nq][k] and/or D/I.
-// allow_stat: the caller reads the fail flag once the stream has drained (wait_search) and repeats
-// the search with allow_stat = false if it is set.
-// The batch a caller handed over, for as long as the search works through it in pieces (the outermost scope wins).
-struct BatchScope {
-    knn_index_s *h;
-    int64_t prev;
-    BatchScope(knn_index_s *h_, int64_t nq) : h(h_), prev(h_->batch_nq)
-    {
-        if (!prev) h->batch_nq = h->batch_hint > 0 ? std::max(nq, h->batch_hint) : nq;
-    }
-    ~BatchScope() { h->batch_nq = prev; }
-};
-
-static int search_keys_impl(knn_index_s *h, const float *q_dev, int64_t nq, int k, uint32_t id_base,
-                            uint64_t *keys_out, float *D_out, int64_t *I_out, bool allow_stat, hipStream_t s)
-{
-    BatchScope scope(h, nq);
-    h->last_s16_used = false;
-    h->s16_pieces = 0;
-    const float *xn = nullptr;
-    if (h->metric == KNN_METRIC_L2) {
-        if (h->ws_qn.ensure((size_t)nq * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        int rc = norms_dev_impl(q_dev, nq, h->d, h->dp, (float *)h->ws_qn.p, s);
-        if (rc) return rc;
-        xn = (const float *)h->ws_qn.p;
-    }
-    if (h->ws_flag.ensure(64, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-    if (h->approx16) {
-        // the scan reads bf16 queries (the fp32 ones above gave the exact norms)
-        if (h->ws_q16.ensure((size_t)nq * h->dp * 2, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        const int64_t total = nq * h->dp;
-        hipLaunchKernelGGL(to_bf16_kernel, dim3((unsigned)std::min<int64_t>((total / 4 + 255) / 256, 65535)), dim3(256), 0, s, q_dev, total,
-                           (__bf16 *)h->ws_q16.p);
-        HIP_TRY(hipGetLastError());
-        q_dev = (const float *)h->ws_q16.p;
-    }
-    const std::vector<Piece> pieces = plan_pieces(plan_ctx(h), nq, k, allow_stat);
-    for (size_t b = 0; b < pieces.size(); b++) {
-        const int64_t q0 = pieces[b].q0, m = pieces[b].m;
-        SearchOut out;
-        out.keys = keys_out ? keys_out + q0 * k : nullptr; out.keys_stride = k; out.keys_fill = 0;
-        out.D = D_out ? D_out + q0 * k : nullptr; out.I = I_out ? I_out + q0 * k : nullptr;
-        int rc = search_view(h, q_dev + q0 * (h->approx16 ? h->dp / 2 : h->dp), xn ? xn + q0 : nullptr, m, k, id_base, 1, 3, 0, out, allow_stat, s,
-                             b == 0 ? (int *)h->ws_flag.p : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-static int check_search_args(knn_index_s *h, const void *q, int64_t nq, int64_t k, const void *D, const void *I)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "search: null handle");
-    if (nq < 0) return set_err(KNN_ERR_INVALID, "search: negative nq");
-    if (k < 1) return set_err(KNN_ERR_INVALID, "search: k must be >= 1");
-    if (k > KNN_MAX_K) return set_err(KNN_ERR_UNSUPPORTED, "search: k > 2048 is not supported by the fused top-k");
-    if (nq > 0 && (!q || !D || !I)) return set_err(KNN_ERR_INVALID, "search: null pointer");
-    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "search" KNN_STALE_VIEW_MSG);
-    return 0;
-}
-
-// index with no rows: every slot is unfilled
-__global__ void fill_empty_kernel(int64_t total, int metric, uint64_t *__restrict__ keys, float *__restrict__ D, int64_t *__restrict__ I)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    if (keys) keys[i] = KEY_PAD;
-    if (D) {
-        D[i] = metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX;
-        I[i] = -1;
-    }
-}
-// the same for results in host memory: D[n], I[n]
-static void fill_empty_host(float *D, int64_t *I, int64_t n, int metric)
-{
-    const float pad = metric == KNN_METRIC_INNER_PRODUCT ? -FLT_MAX : FLT_MAX;
-    for (int64_t i = 0; i < n; i++) {
-        D[i] = pad;
-        I[i] = -1;
-    }
-}
-
-// q_dev: [nq][d] contiguous on device. D_dev/I_dev on device.
-static int search_dev_impl(knn_index_s *h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
-                           uint64_t *keys_dev, uint32_t id_base, bool allow_stat, hipStream_t s)
-{
-    if (nq == 0) return 0;
-    // packed keys carry id_base + row in 32 bits: a shard whose ids would wrap is refused before anything is launched (a
-    // wrapped id collides with or sorts in front of another shard's, and the merge takes keys to be distinct)
-    if (keys_dev && (uint64_t)id_base + (uint64_t)h->ntotal > (1ull << 32))
-        return set_err(KNN_ERR_INVALID, "search_keys: id_base " + std::to_string(id_base) + " + ntotal " + std::to_string(h->ntotal) +
-                                            " exceeds 2^32: ids are 32 bits wide in the packed keys");
-    const int64_t total = nq * k;
-    if (h->ntotal == 0) {
-        hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, h->metric, keys_dev, D_dev, I_dev);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const float *qp = q_dev;
-    if (h->dp != h->d) {
-        if (h->ws_q.ensure((size_t)nq * h->dp * 4, h->done, s)) return set_err(KNN_ERR_HIP, "search: out of device memory");
-        int rc = pad_rows_dev(q_dev, nq, h->d, (float *)h->ws_q.p, h->dp, s);
-        if (rc) return rc;
-        qp = (const float *)h->ws_q.p;
-    }
-    return search_keys_impl(h, qp, nq, k, id_base, keys_dev, D_dev, I_dev, allow_stat, s);
-}
-
-// waits for the search on s; then: did a statistically seeded search fail its verification?
-static int wait_search(knn_index_s *h, hipStream_t s, bool *failed)
-{
-    *failed = false;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!h->ws_flag.p || h->ntotal == 0) return 0;
-    int flag = 0;
-    HIP_TRY(hipMemcpy(&flag, h->ws_flag.p, 4, hipMemcpyDeviceToHost));
-    *failed = flag != 0;
-    if (flag) {
-        h->stat_redo++;
-        // read = cleared: a search whose predecessor left the level's state reset (LevelBufs::clean_sig) skips the launch
-        // that clears the flag, and a repeat that returns early with an error never reaches its own
-        // (on the handle's stream, like every other access to the flag: a NULL-stream memset is not ordered against a
-        // non-blocking stream, and completing late it could erase the flag of the repeat search -- ADVICE r4)
-        HIP_TRY(hipMemsetAsync(h->ws_flag.p, 0, 4, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return 0;
-}
-
-extern "C" int knn_flat_search_dev(knn_handle h, const float *q_dev, int64_t nq, int64_t k, float *D_dev,
-                                   int64_t *I_dev, void *stream)
-{
-    int rc = check_search_args(h, q_dev, nq, k, D_dev, I_dev);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    h->last_ms = -1.f;
-    // a caller's stream means "enqueue and return": no way to look at the verification flag, so
-    // only the synchronous form may use the statistical seed
-    const bool sync = stream == nullptr;
-    rc = search_dev_impl(h, q_dev, nq, (int)k, D_dev, I_dev, nullptr, 0, sync, s);
-    if (rc) return rc;
-    if (sync) {
-        bool failed = false;
-        rc = wait_search(h, s, &failed);
-        if (rc) return rc;
-        if (failed) {
-            rc = search_dev_impl(h, q_dev, nq, (int)k, D_dev, I_dev, nullptr, 0, false, s);
-            if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-    }
-    return 0;
-}
-
-extern "C" int knn_flat_search_keys_dev(knn_handle h, const float *q_dev, int64_t nq, int64_t k, uint32_t id_base,
-                                        uint64_t *keys_dev, void *stream)
-{
-    int rc = check_search_args(h, q_dev, nq, k, keys_dev, keys_dev);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    h->last_ms = -1.f;
-    rc = search_dev_impl(h, q_dev, nq, (int)k, nullptr, nullptr, keys_dev, id_base, false, s);
-    if (rc) return rc;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
-
-extern "C" int knn_merge_keys_dev(knn_handle h, const uint64_t *keys_dev, int32_t nlists, int64_t nq, int64_t k,
-                                  float *D_dev, int64_t *I_dev, void *stream)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "merge_keys: null handle");
-    if (nlists < 1 || nq < 0 || k < 1 || k > KNN_MAX_K) return set_err(KNN_ERR_INVALID, "merge_keys: bad shape");
-    if (nq == 0) return 0;
-    if (!keys_dev || !D_dev || !I_dev) return set_err(KNN_ERR_INVALID, "merge_keys: null pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    // one launch whatever nlists * k is, no scratch memory: the selection reads the all-gather buffer in place
-    SelectParams sp = {};
-    sp.in = keys_dev; sp.lm_lists = nlists; sp.lm_k = (int)k;
-    sp.nq = nq; sp.k = (int)k; sp.metric = h->metric;
-    sp.D = D_dev; sp.I = I_dev;
-    int rc = launch_select(sp, s);
-    if (rc) return rc;
-    if (!stream) HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
-
-// Symmetric all-vs-all: index.search(x, k) for x = ALL rows of the index (cath/search.py:22-24,
-// pfam/proteins_search.py:37,49, pfam/slices/slices_search.py:22-28 -- every flat search of the reference is one).
-// Only the score tiles on and above the diagonal are multiplied (flat_scan_kernel<..., SYM>); needs the statistical
-// seed (the rows of a database tile have no candidate list of their own in that kernel, only their compact arrays)
-// and k <= 1536.  Returns 1 when it ran (D_dev / I_dev hold all n x k results, the verification flag is still to be
-// read by the caller), 0 when the plain path should be used, < 0 on error.
-//
-// D_host / I_host / d2h given and the result large: the query tiles are served in sp.groups launches of consecutive tiles, each
-// followed by the final selection of ITS rows -- a row's candidates are complete once every query tile up to its own has been
-// served (tile (I, J), J >= I, scores rows I against J and J against I) -- and by their download on the copy stream d2h, which
-// then overlaps the launches of the later groups (Pfam-sized k = 1000: 2.4 GB of results, 0.15 s behind a 0.38 s search;
-// CATH-sized k = 301: 52 MB, 1.3 ms on the wire behind a 2.5 ms search, in four groups).
-// Returns 2 then (the caller waits for d2h and checks the verification flag), 1 when the results are in D_dev / I_dev only.
-// Every decision is plan_self_symmetric's and sym_work_table's (plan.h).
-static int self_search_symmetric(knn_index_s *h, int k, float *D_dev, int64_t *I_dev, hipStream_t s, float *D_host = nullptr,
-                                 int64_t *I_host = nullptr, hipStream_t d2h = nullptr)
-{
-    const int64_t n = h->ntotal;
-    SymPlan sp;
-    if (!plan_self_symmetric(plan_ctx(h), k, D_host && I_host && d2h, sp)) return 0;
-    const int qcap = sp.qcap, groups = sp.groups;
-    const size_t nslots = (size_t)sp.tiles * sp.ts;
-    LevelBufs &lb = h->ws_level[0];
-    lb.clean_sig = 0; // (this search leaves the level's state in its own shape)
-    if (lb.qlist.ensure((size_t)n * qcap * 8) || lb.qcnt.ensure((size_t)n * 4) || lb.gthr.ensure(nslots * 4) || lb.qthr.ensure((size_t)n * 4) ||
-        h->ws_flag.ensure(64))
-        return set_err(KNN_ERR_HIP, "search_self: out of device memory");
-    uint64_t *qlist = (uint64_t *)lb.qlist.p;
-    uint32_t *qcnt = (uint32_t *)lb.qcnt.p, *gthr = (uint32_t *)lb.gthr.p, *qthr = (uint32_t *)lb.qthr.p;
-    const float *xn = h->metric == KNN_METRIC_L2 ? h->yn : nullptr; // the queries are the rows: their norms are the row norms
-    // 0. the work table.  It depends on (tiles, groups, CUs) only: it stays on the device between searches (uploading it between
-    //    the sample pass and the main launch cost a host round trip -- 35 us of idle GPU -- per search).
-    if (h->sym_tiles != sp.tiles || h->sym_ts != sp.ts || h->sym_groups != groups || !h->ws_sym.p) {
-        const SymTable t = sym_work_table(sp.tiles, groups, sp.slots);
-        h->sym_tiles = -1;
-        if (h->ws_sym.ensure(t.items.size() * sizeof(SymItem), h->done, s)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
-        HIP_TRY(hipMemcpyAsync(h->ws_sym.p, t.items.data(), t.items.size() * sizeof(SymItem), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s)); // (the table is a local vector)
-        h->sym_tiles = sp.tiles;
-        h->sym_ts = sp.ts;
-        h->sym_groups = groups;
-        h->sym_run = t.first_run;
-        h->sym_items = (int64_t)t.items.size();
-        h->sym_gstart = t.gstart;
-    }
-    const size_t nitems = (size_t)h->sym_items;
-    // 1. the sample pass (every row is a query, the strided sample is the database): thresholds + the sample's own candidates
-    SearchOut so;
-    so.keys = qlist; so.keys_stride = qcap; so.keys_fill = 0;
-    so.seed_cnt = qcnt; so.seed_gthr = gthr; so.seed_qthr = qthr; so.seed_j = sp.j; so.seed_stat = 1; so.seed_nslots = (int64_t)nslots;
-    int rc = search_view(h, h->xb, xn, n, sp.k_sample, 0, sp.st, 0, 1, so, false, s, (int *)h->ws_flag.p);
-    if (rc) return rc;
-    if (h->ws_lists.ensure((size_t)std::min<int64_t>((int64_t)nitems, sp.max_wgs) * sp.ts * sp.pl.cap * 8)) return set_err(KNN_ERR_HIP, "search_self: out of device memory (candidate lists)");
-    ScanParams p = {};
-    p.xb = h->xb; p.yn = h->yn; p.xq = h->xb; p.xn = xn;
-    p.nb = n; p.nq = n; p.dp = h->dp; p.k = k; p.cap = sp.pl.cap;
-    p.nqtiles = sp.tiles; p.nchunks = 1; p.tiles_base = 0; p.tiles_rem = 0;
-    p.lists = (uint64_t *)h->ws_lists.p; p.gthr = gthr;
-    p.qlist = qlist; p.qcnt = qcnt; p.qcap = qcap;
-    p.id_base = 0; p.row_mul = 1; p.vshift = 0; p.skip_mask = sp.st - 1;
-    p.kslot = knn_kslot(k);
-    p.fail = (int *)h->ws_flag.p;
-    if (sp.cu_turn && (rc = zeroed_turn_words(h, s, &p.cu_turn))) return rc;
-    const ScanKernel kern = pick_sym_kernel(sp.ts, h->metric == KNN_METRIC_L2);
-    rc = scan_lds_opt_in(kern, sp.lds);
-    if (!rc) rc = open_timed_launch(h, s);
-    if (rc) return rc;
-#ifdef KNN355_TRACE
-    if (g_trace_buf.ensure((size_t)nitems * 128 * 8)) return set_err(KNN_ERR_HIP, "trace: out of device memory");
-    HIP_TRY(hipMemsetAsync(g_trace_buf.p, 0, (size_t)nitems * 128 * 8, s));
-    p.trace = (unsigned long long *)g_trace_buf.p;
-    p.ablate = getenv("KNN355_ABLATE") ? atoi(getenv("KNN355_ABLATE")) : 0;
-    g_trace_grid = (int)std::min<size_t>(nitems, (size_t)sp.max_wgs);
-#endif
-    // 2 + 3. the launches, each followed by the final selection of the rows it completes (verified against the sample's bound)
-    EventList gev; // with several groups: one behind each group's selection
-    for (int g = 0; g < groups; g++) {
-        const size_t g0 = (size_t)h->sym_gstart[(size_t)g], g1 = (size_t)h->sym_gstart[(size_t)g + 1];
-        for (size_t i0 = g0; i0 < g1; i0 += (size_t)sp.max_wgs) {
-            const size_t cnt = std::min<size_t>((size_t)sp.max_wgs, g1 - i0);
-            p.sym_items = (const SymItem *)h->ws_sym.p + i0;
-            rc = launch_scan(kern, p, (int)cnt, sp.lds, s);
-            if (rc) return rc;
-        }
-        if (g == groups - 1) HIP_TRY(hipEventRecord(h->ev1, s));
-        const int64_t r0 = sym_group_row0(sp, n, g), r1 = sym_group_row0(sp, n, g + 1);
-        SelectParams sel = {};
-        sel.in = qlist + (size_t)r0 * qcap; sel.in_stride = qcap; sel.cnt = qcnt + r0; sel.cap = qcap;
-        sel.n_expect = sp.n_expect;
-        sel.nq = r1 - r0; sel.k = k; sel.metric = h->metric;
-        sel.D = D_dev + (size_t)r0 * k; sel.I = I_dev + (size_t)r0 * k;
-        sel.qthr = qthr + r0; sel.fail = (int *)h->ws_flag.p;
-        rc = launch_select(sel, s, &h->ws_tmp);
-        if (rc) return rc;
-        if (groups > 1 && (rc = gev.mark(s, hipEventDisableTiming))) return rc;
-    }
-    h->last_kernel = sp.name; h->last_qt = sp.ts; h->last_dt = sp.ts; h->last_chunks = h->sym_run; h->last_grid = (int)nitems;
-    h->last_seed_stride = sp.st; h->last_seed_stat = sp.j; h->last_sample_rows = sp.S;
-    if (h->done) (void)hipEventRecord(h->done, s); // (everything this search enqueued on the handle's buffers: see DevBuf::ensure)
-    h->sym_searches++;
-    if (groups == 1) return 1;
-    // the downloads, group by group behind their selections (everything above is enqueued: a copy into pageable memory may
-    // block this thread as long as it likes)
-    hipError_t e = hipSuccess;
-    for (int g = 0; g < groups; g++) {
-        const int64_t r0 = sym_group_row0(sp, n, g), r1 = sym_group_row0(sp, n, g + 1);
-        if (e == hipSuccess) e = hipStreamWaitEvent(d2h, gev.ev[(size_t)g], 0);
-        if (e == hipSuccess && r1 > r0) e = hipMemcpyAsync(D_host + (size_t)r0 * k, D_dev + (size_t)r0 * k, (size_t)(r1 - r0) * k * 4, hipMemcpyDeviceToHost, d2h);
-        if (e == hipSuccess && r1 > r0) e = hipMemcpyAsync(I_host + (size_t)r0 * k, I_dev + (size_t)r0 * k, (size_t)(r1 - r0) * k * 8, hipMemcpyDeviceToHost, d2h);
-    }
-    // (always: a copy already queued writes into the caller's arrays)
-    const hipError_t es = hipStreamSynchronize(d2h);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return set_err(KNN_ERR_HIP, hipGetErrorString(e));
-    return 2;
-}
-
-// Copy streams of the pipelined host search: one set per device for the whole process, created on
-// first use (a HIP stream costs milliseconds to create and callers such as cath/search.py build a
-// fresh index per file).  Whoever holds `mu` pipelines; a concurrent host search on the same
-// device simply runs its batches one after the other on its own stream.
-struct CopyPipes {
-    std::mutex mu;
-    hipStream_t h2d = nullptr, d2h = nullptr;
-    // per result slot, for the holder of `mu` alone: the slot's queries are up, its batch is done on the search stream,
-    // its results have left the buffers
-    hipEvent_t ev_query[2] = {nullptr, nullptr}, ev_batch[2] = {nullptr, nullptr}, ev_left[2] = {nullptr, nullptr};
-};
-static CopyPipes g_pipes[64];
-
-// A caller's hold on its device's copy pipes: cp is null when the caller did not want them (`want`: its own rule, one batch
-// has nothing to overlap with) or another host search holds them; otherwise they are this caller's until the lease goes.
-// The streams and events are made on first use (the caller has set the device).
-struct PipeLease {
-    std::unique_lock<std::mutex> lock;
-    CopyPipes *cp = nullptr;
-};
-static int lease_pipes(int device, bool want, PipeLease &lease)
-{
-    CopyPipes &cp = g_pipes[device & 63];
-    lease.lock = std::unique_lock<std::mutex>(cp.mu, std::defer_lock);
-    if (!want || !lease.lock.try_lock()) return 0;
-    if (!cp.h2d) HIP_TRY(hipStreamCreateWithFlags(&cp.h2d, hipStreamNonBlocking));
-    if (!cp.d2h) HIP_TRY(hipStreamCreateWithFlags(&cp.d2h, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-        if (!cp.ev_query[i]) HIP_TRY(hipEventCreateWithFlags(&cp.ev_query[i], hipEventDisableTiming));
-        if (!cp.ev_batch[i]) HIP_TRY(hipEventCreateWithFlags(&cp.ev_batch[i], hipEventDisableTiming));
-        if (!cp.ev_left[i]) HIP_TRY(hipEventCreateWithFlags(&cp.ev_left[i], hipEventDisableTiming));
-    }
-    lease.cp = &cp;
-    return 0;
-}
-
-// The scaffold of a host entry that keeps nothing behind: enqueue on `s` (uploads may ride pipes.cp->h2d), then finish().
-// ORDER: streams are drained before any buffer goes back to the pool or to hipFree -- the pool may hand a buffer to
-// another handle at once -- and a stream of g_streams goes back behind the buffers.  finish() drains; the members then go
-// in reverse: events, buffers, the stream, the pipes.  (An entry without a HostCall declares its StreamLease behind its
-// PoolBufs: the lease's destructor drains, and it runs first.)
-struct HostCall {
-    PipeLease pipes;
-    StreamLease own;
-    EvalBufs bufs;
-    EventList ev;
-    hipStream_t s; // where the call's kernels run: its own stream, else the leased h2d stream, else the caller's / the null stream
-    // on a stream the caller names (null: the null stream)
-    explicit HostCall(hipStream_t caller = nullptr) : own(0, false), s(caller) {}
-    // on a stream of g_streams (s is null when there is none)
-    explicit HostCall(int device) : own(device), s(own) {}
-    // the device's copy pipes, if wanted and free; a call without a stream of its own then runs on their h2d stream
-    int lease(int device, bool want)
-    {
-        EVAL_TRY(lease_pipes(device, want, pipes));
-        if (pipes.cp && !own) s = pipes.cp->h2d;
-        return 0;
-    }
-    // Behind the enqueueing, whatever it returned (rc): waits for the h2d stream and for s -- always, copies already queued
-    // read and write the caller's arrays -- then reports rc, else the first HIP error as "who: ...", else fills ms[i] with
-    // the time between ev[i] and ev[i + 1], i < n_ms.
-    int finish(const char *who, int rc, float *ms, int n_ms)
-    {
-        hipError_t e = pipes.cp && pipes.cp->h2d != s ? hipStreamSynchronize(pipes.cp->h2d) : hipSuccess;
-        const hipError_t es = hipStreamSynchronize(s);
-        if (rc) return rc;
-        if (e == hipSuccess) e = es;
-        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-        for (int i = 0; i < n_ms; i++) HIP_TRY(hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]));
-        return 0;
-    }
-};
-
-// The result download of a batched search whose batches follow one another on the search stream `s` (hnsw_search_device,
-// lsh_search_batches).  Piped (cp given): two sets of result buffers, and while batch b runs on `s` the results of batch
-// b - 1 go down on the copy stream, ordered by events alone -- this thread never waits inside the loop.  Not piped: one
-// set, every batch downloaded on `s` and waited for.  The caller's loop is
-//     for every batch b, while rc == 0: before(b); enqueue the batch into the buffers of slot(b); after(b, copy)
-//     return finish(rc, nbatches, copy)
-// with copy(b, slot, stream) -> hipError_t enqueueing the device-to-host copies of batch b.  Every HIP error is reported
-// under `who` ("lsh_search: ").
-struct ResultPipe {
-    CopyPipes *cp;
-    hipStream_t s;
-    const char *who;
-    int slot(int64_t b) const { return cp ? (int)(b & 1) : 0; }
-    int hip(hipError_t e) const { return e == hipSuccess ? 0 : set_err(KNN_ERR_HIP, std::string(who) + hipGetErrorString(e)); }
-    // the results of batch b - 2 have left the buffers batch b is about to write
-    int before(int64_t b) const { return cp && b >= 2 ? hip(hipStreamWaitEvent(s, cp->ev_left[b & 1], 0)) : 0; }
-    // batch b is enqueued: the copy of batch b - 1 may block this thread as long as it likes
-    template <typename Copy>
-    int after(int64_t b, Copy &&copy) const
-    {
-        if (!cp) {
-            int rc = hip(copy(b, 0, s));
-            return rc ? rc : hip(hipStreamSynchronize(s));
-        }
-        int rc = hip(hipEventRecord(cp->ev_batch[b & 1], s));
-        if (rc || b == 0) return rc;
-        rc = download(b - 1, copy);
-        return rc ? rc : hip(hipEventRecord(cp->ev_left[(b - 1) & 1], cp->d2h));
-    }
-    // rc: how the loop ended.  If well, the last batch goes down; then, whichever way it ended, BOTH streams are waited
-    // for: a download already queued writes into the caller's host arrays, and the lease is released on return.
-    template <typename Copy>
-    int finish(int rc, int64_t nbatches, Copy &&copy) const
-    {
-        if (!cp) return rc;
-        if (!rc) rc = download(nbatches - 1, copy);
-        const hipError_t e1 = hipStreamSynchronize(cp->d2h), e2 = hipStreamSynchronize(s);
-        return rc ? rc : hip(e1 != hipSuccess ? e1 : e2);
-    }
-    template <typename Copy>
-    int download(int64_t b, Copy &&copy) const
-    {
-        int rc = hip(hipStreamWaitEvent(cp->d2h, cp->ev_batch[b & 1], 0));
-        return rc ? rc : hip(copy(b, (int)(b & 1), cp->d2h));
-    }
-};
-
-// Search with results (and, unless q_host is null, queries) in host memory.  q_host == nullptr:
-// the queries are the index's own rows [self_row0, self_row0 + nq) -- already on the device and
-// padded, nothing to upload.  Caller holds h->mu.
-static int host_search(knn_index_s *h, const float *q_host, int64_t self_row0, int64_t nq, int64_t k, float *D_host,
-                       int64_t *I_host)
-{
-    int rc = 0;
-    BatchScope scope(h, nq);
-    HIP_TRY(hipSetDevice(h->device));
-    // Query batches bound the device workspace; 16384 queries keep >= 128 query tiles in flight.
-    // Batches are pipelined: while batch b is scanned, a helper thread downloads the results of
-    // batch b-1 (pageable host memory: the copy blocks its caller) and this thread uploads the
-    // queries of batch b+1, each on its own stream with its own staging buffers.
-    int64_t QB = 16384;
-    // A single batch with a large result (CATH20-sized all-vs-all with 300 hits: 52 MB, a millisecond on
-    // the wire) is split in two so that half of its download overlaps the scan; small results are not
-    // worth the extra launches and the extra streams of the pipelined path.
-    // (two halves: measured 5.1-5.2 ms for the CATH-sized k=301 search_self against 5.4 in one piece and 5.4 in four --
-    // every piece pays its own sample pass and selections)
-    if (nq <= QB && (size_t)nq * k * 12 >= ((size_t)24 << 20) && nq >= 4096)
-        QB = std::max<int64_t>(2048, ((nq + 1) / 2 + 127) / 128 * 128);
-    const int64_t bq = std::min(nq, QB);
-    const int64_t nbatches = (nq + QB - 1) / QB;
-    DevBuf *qbuf[2] = {&h->ws_tmp2, &h->ws_tmp3}, *dbuf[2] = {&h->ws_D, &h->ws_D1}, *ibuf[2] = {&h->ws_I, &h->ws_I1};
-    const int nslots = nbatches > 1 ? 2 : 1;
-    for (int i = 0; i < nslots; i++)
-        if ((q_host && qbuf[i]->ensure((size_t)bq * h->d * 4)) || dbuf[i]->ensure((size_t)bq * k * 4) || ibuf[i]->ensure((size_t)bq * k * 8))
-            return set_err(KNN_ERR_HIP, "search: out of device memory");
-    if (!h->flag_host) HIP_TRY(hipHostMalloc((void **)&h->flag_host, 64, hipHostMallocDefault));
-    // one batch of queries on the device: uploaded rows ([m][d]) or the index's own rows ([m][dp]).
-    // The verification flag of a statistically seeded batch travels to flag_host[slot] behind it.
-    auto scan = [&](int slot, int64_t b0, int64_t m, bool allow_stat) -> int {
-        int r;
-        if (q_host)
-            r = search_dev_impl(h, (const float *)qbuf[slot]->p, m, (int)k, (float *)dbuf[slot]->p, (int64_t *)ibuf[slot]->p, nullptr, 0, allow_stat, h->stream);
-        else
-            r = search_keys_impl(h, h->xb + (size_t)(self_row0 + b0) * h->dp, m, (int)k, 0, nullptr, (float *)dbuf[slot]->p,
-                                 (int64_t *)ibuf[slot]->p, allow_stat, h->stream);
-        if (r) return r;
-        h->flag_host[slot] = 0;
-        if (allow_stat && h->ntotal > 0) HIP_TRY(hipMemcpyAsync(&h->flag_host[slot], h->ws_flag.p, 4, hipMemcpyDeviceToHost, h->stream));
-        return 0;
-    };
-    // plain form: one batch at a time on the handle's stream (nothing to overlap with, or the
-    // device's copy streams are taken)
-    auto plain = [&](int64_t b0, int64_t m, bool allow_stat) -> int {
-        if (q_host) HIP_TRY(hipMemcpyAsync(qbuf[0]->p, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, h->stream));
-        int r = scan(0, b0, m, allow_stat);
-        if (r) return r;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->flag_host[0]) { // the statistical threshold was too tight for some query: once more without it
-            h->stat_redo++;
-            r = scan(0, b0, m, false);
-            if (r) return r;
-        }
-        HIP_TRY(hipMemcpyAsync(D_host + b0 * k, dbuf[0]->p, (size_t)m * k * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(I_host + b0 * k, ibuf[0]->p, (size_t)m * k * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        if (h->ntotal > 0 && h->ev0 && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_ms += ms;
-        return 0;
-    };
-    PipeLease lease;
-    rc = lease_pipes(h->device, nbatches > 1, lease);
-    if (rc) return rc;
-    if (!lease.cp) {
-        h->last_ms = 0.f;
-        for (int64_t b0 = 0; b0 < nq; b0 += QB) {
-            rc = plain(b0, std::min(QB, nq - b0), true);
-            if (rc) return rc;
-        }
-        return 0;
-    }
-    CopyPipes &cp = *lease.cp;
-    struct Download {
-        std::thread th;
-        hipError_t err = hipSuccess;
-        hipEvent_t t0 = nullptr, t1 = nullptr; // scan events of the batch
-        int64_t batch = -1;
-        bool failed = false;
-    } dl[2];
-    float ms_total = 0.f;
-    hipError_t dl_err = hipSuccess;
-    std::vector<int64_t> redo; // batches whose statistical threshold failed its verification
-    auto join = [&](int slot) {
-        if (!dl[slot].th.joinable()) return;
-        dl[slot].th.join();
-        if (dl[slot].err != hipSuccess) dl_err = dl[slot].err;
-        if (dl[slot].failed) redo.push_back(dl[slot].batch);
-        float ms = 0.f;
-        if (dl[slot].t0 && hipEventElapsedTime(&ms, dl[slot].t0, dl[slot].t1) == hipSuccess) ms_total += ms;
-    };
-    auto upload = [&](int64_t b) -> hipError_t {
-        if (!q_host) return hipSuccess;
-        const int slot = (int)(b & 1);
-        const int64_t b0 = b * QB, m = std::min(QB, nq - b0);
-        hipError_t e = hipMemcpyAsync(qbuf[slot]->p, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, cp.h2d);
-        if (e == hipSuccess) e = hipEventRecord(cp.ev_query[slot], cp.h2d);
-        return e;
-    };
-    hipError_t e = upload(0);
-    for (int64_t b = 0; b < nbatches && e == hipSuccess && rc == 0; b++) {
-        const int slot = (int)(b & 1);
-        const int64_t b0 = b * QB, m = std::min(QB, nq - b0);
-        if (q_host) e = hipStreamWaitEvent(h->stream, cp.ev_query[slot], 0);
-        if (e != hipSuccess) break;
-        rc = scan(slot, b0, m, true);
-        if (rc) break;
-        e = hipEventRecord(cp.ev_batch[slot], h->stream);
-        if (e != hipSuccess) break;
-        dl[slot].t0 = h->ntotal > 0 ? h->ev0 : nullptr;
-        dl[slot].t1 = h->ev1;
-        dl[slot].err = hipSuccess;
-        dl[slot].batch = b;
-        dl[slot].failed = false;
-        CopyPipes *cpp = &cp;
-        dl[slot].th = std::thread([=, &dl]() {
-            hipError_t r = hipSetDevice(h->device);
-            if (r == hipSuccess) r = hipEventSynchronize(cpp->ev_batch[slot]);
-            if (r == hipSuccess && h->flag_host[slot]) {
-                dl[slot].failed = true; // repeated below, after the pipeline has drained
-                dl[slot].err = hipSuccess;
-                return;
-            }
-            if (r == hipSuccess) r = hipMemcpyAsync(D_host + b0 * k, dbuf[slot]->p, (size_t)m * k * 4, hipMemcpyDeviceToHost, cpp->d2h);
-            if (r == hipSuccess) r = hipMemcpyAsync(I_host + b0 * k, ibuf[slot]->p, (size_t)m * k * 8, hipMemcpyDeviceToHost, cpp->d2h);
-            if (r == hipSuccess) r = hipStreamSynchronize(cpp->d2h);
-            dl[slot].err = r;
-        });
-        if (b + 1 < nbatches) {
-            // the other slot's buffers: its scan (batch b-1) must be over and downloaded
-            join(slot ^ 1);
-            e = upload(b + 1);
-        }
-    }
-    join(0);
-    join(1);
-    if (rc) return rc;
-    if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("search: ") + hipGetErrorString(e));
-    if (dl_err != hipSuccess) return set_err(KNN_ERR_HIP, std::string("search: result download failed: ") + hipGetErrorString(dl_err));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->last_ms = ms_total;
-    for (int64_t b : redo) {
-        h->stat_redo++;
-        const int64_t b0 = b * QB;
-        rc = plain(b0, std::min(QB, nq - b0), false);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-extern "C" int knn_flat_search(knn_handle h, const float *q_host, int64_t nq, int64_t k, float *D_host,
-                               int64_t *I_host)
-{
-    int rc = check_search_args(h, q_host, nq, k, D_host, I_host);
-    if (rc) return rc;
-    if (nq == 0) return 0;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return host_search(h, q_host, 0, nq, k, D_host, I_host);
-}
-
-extern "C" int knn_flat_search_self(knn_handle h, int64_t row0, int64_t nrows, int64_t k, float *D_host, int64_t *I_host)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "search_self: null handle");
-    if (nrows == 0) return 0;
-    int rc = check_search_args(h, D_host, nrows, k, D_host, I_host);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (row0 < 0 || nrows < 0 || row0 + nrows > h->ntotal) return set_err(KNN_ERR_INVALID, "search_self: row range out of bounds");
-    if (row0 == 0 && nrows == h->ntotal && (size_t)nrows * k * 12 <= ((size_t)16 << 30) && self_search_symmetric_eligible(plan_ctx(h), (int)k)) {
-        // every row against every row: half the score tiles suffice (self_search_symmetric)
-        HIP_TRY(hipSetDevice(h->device));
-        if (h->ws_D.ensure((size_t)nrows * k * 4) || h->ws_I.ensure((size_t)nrows * k * 8)) return set_err(KNN_ERR_HIP, "search_self: out of device memory");
-        h->last_ms = -1.f;
-        // (a large result leaves in pieces while the later query tiles are still being served: the copy stream of the device,
-        // if no other host search of this process is using it)
-        static const bool stream_off = getenv("KNN355_SELF_STREAM") && atoi(getenv("KNN355_SELF_STREAM")) == 0; // (A/B: the result in one piece behind the search)
-        {
-            PipeLease lease;
-            rc = lease_pipes(h->device, !stream_off && (size_t)nrows * k * 12 >= ((size_t)dev_knob("KNN355_SELF_STREAM_MIN_MB", 32) << 20), lease);
-            if (rc) return rc;
-            rc = self_search_symmetric(h, (int)k, (float *)h->ws_D.p, (int64_t *)h->ws_I.p, h->stream, D_host, I_host, lease.cp ? lease.cp->d2h : nullptr);
-        }
-        if (rc < 0) return rc;
-        // (0: the plan left the search to the plain path after all, which also repeats a search whose verification failed: a
-        // threshold estimate was too tight or a candidate array overflowed)
-        bool failed = true;
-        if (rc > 0) {
-            const bool downloaded = rc == 2; // (the rows went out behind their groups' selections)
-            rc = wait_search(h, h->stream, &failed);
-            if (rc) return rc;
-            if (!failed && !downloaded) {
-                HIP_TRY(hipMemcpyAsync(D_host, h->ws_D.p, (size_t)nrows * k * 4, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipMemcpyAsync(I_host, h->ws_I.p, (size_t)nrows * k * 8, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-            }
-        }
-        // the results' staging stays with the handle for the next search unless it is gigabytes, or host_search follows: that
-        // works in batches and takes what it needs
-        if (failed || (size_t)nrows * k * 12 > ((size_t)1 << 30)) {
-            h->ws_D.release();
-            h->ws_I.release();
-        }
-        if (!failed) return 0;
-    }
-    return host_search(h, nullptr, row0, nrows, k, D_host, I_host);
-}
-
-// the same with the results left on the device (D_dev [ntotal][k], I_dev [ntotal][k]); synchronous
-extern "C" int knn_flat_search_self_dev(knn_handle h, int64_t k, float *D_dev, int64_t *I_dev)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "search_self: null handle");
-    if (h->ntotal == 0) return 0;
-    int rc = check_search_args(h, D_dev, h->ntotal, k, D_dev, I_dev);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    h->last_ms = -1.f;
-    rc = self_search_symmetric(h, (int)k, D_dev, I_dev, s);
-    if (rc < 0) return rc;
-    if (rc == 1) {
-        bool failed = false;
-        rc = wait_search(h, s, &failed);
-        if (rc) return rc;
-        if (!failed) return 0;
-    }
-    const int64_t QB = 16384;
-    BatchScope scope(h, h->ntotal);
-    for (int64_t b0 = 0; b0 < h->ntotal; b0 += QB) {
-        const int64_t m = std::min(QB, h->ntotal - b0);
-        for (int attempt = 0; attempt < 2; attempt++) { // (statistical seed first, plain if its verification fails)
-            rc = search_keys_impl(h, h->xb + (size_t)b0 * h->dp, m, (int)k, 0, nullptr, D_dev + b0 * k, I_dev + b0 * k, attempt == 0, s);
-            if (rc) return rc;
-            bool failed = false;
-            rc = wait_search(h, s, &failed);
-            if (rc) return rc;
-            if (!failed) break;
-        }
-    }
-    return 0;
-}
-
-extern "C" int knn_flat_normalize_rows(knn_handle h)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "normalize_rows: null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "normalize_rows: a view is read-only");
-    if (h->ntotal == 0) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    int rc = normalize_dev_impl(h->xb, h->ntotal, h->d, h->dp, h->stream);
-    if (rc) return rc;
-    rc = norms_dev_impl(h->xb, h->ntotal, h->d, h->dp, h->yn, h->stream);
-    if (rc) return rc;
-    rc = approx16_sync_rows(h, 0, h->ntotal, h->stream);
-    if (rc) return rc;
-    rc = scan16_sync_rows(h, 0, h->ntotal, h->stream); // (the rows changed: copies and statistics from scratch)
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int knn_last_scan_info(knn_handle h, char *name, int32_t name_len, int32_t *query_tile, int32_t *db_tile,
-                                  int32_t *nchunks, int32_t *grid)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "null handle");
-    if (name && name_len > 0) {
-        strncpy(name, h->last_kernel.c_str(), (size_t)name_len - 1);
-        name[name_len - 1] = 0;
-    }
-    if (query_tile) *query_tile = h->last_qt;
-    if (db_tile) *db_tile = h->last_dt;
-    if (nchunks) *nchunks = h->last_chunks;
-    if (grid) *grid = h->last_grid;
-    return 0;
-}
-
-extern "C" float knn_last_scan_ms(knn_handle h)
-{
-    if (!h) return -1.f;
-    std::lock_guard<std::mutex> lk(h->mu);
-    float ms = 0.f;
-    if (h->last_ms >= 0.f) return h->last_ms;
-    if (!h->ev0 || hipEventElapsedTime(&ms, h->ev0, h->ev1) != hipSuccess) return -1.f;
-    return ms;
-}
-
-extern "C" int32_t knn_scan_times(knn_handle h, float *out_ms, int32_t max_n)
-{
-    if (!h || !out_ms || max_n < 0) return set_err(KNN_ERR_INVALID, "scan_times: bad arguments");
-    std::lock_guard<std::mutex> lk(h->mu);
-    int64_t n = std::min<int64_t>(std::min<int64_t>(h->nlaunches, knn_index_s::RING), max_n);
-    // oldest first among the n most recent launches; launches whose events have not completed read -1
-    for (int64_t i = 0; i < n; i++) {
-        int64_t idx = h->nlaunches - n + i;
-        int slot = (int)(idx % knn_index_s::RING);
-        float ms = -1.f;
-        if (hipEventElapsedTime(&ms, h->ring0[slot], h->ring1[slot]) != hipSuccess) ms = -1.f;
-        out_ms[i] = ms;
-    }
-    return (int32_t)n;
-}
-
-// Page-locked host memory for result arrays: the download of a search result into it is one DMA at PCIe
-// line rate (into pageable memory the runtime stages through its own pinned buffer at a third of that).
-extern "C" void *knn_host_alloc(int64_t bytes)
-{
-    if (bytes <= 0) return nullptr;
-    if (ensure_device(g_device)) return nullptr;
-    void *p = nullptr;
-    if (hipHostMalloc(&p, (size_t)bytes, hipHostMallocPortable) != hipSuccess) {
-        set_err(KNN_ERR_HIP, "host_alloc: hipHostMalloc failed");
-        return nullptr;
-    }
-    return p;
-}
-extern "C" void knn_host_free(void *p)
-{
-    if (p) (void)hipHostFree(p);
-}
-
-extern "C" int knn_last_seed_info(knn_handle h, int32_t *seed_stride, int32_t *stat_rank, int64_t *stat_redo, int64_t *sample_rows)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "null handle");
-    if (sample_rows) *sample_rows = h->last_sample_rows;
-    if (seed_stride) *seed_stride = h->last_seed_stride;
-    if (stat_rank) *stat_rank = h->last_seed_stat;
-    if (stat_redo) *stat_redo = h->stat_redo;
-    return 0;
-}
-
-extern "C" int knn_flat_reserve(knn_handle h, int64_t nrows)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "reserve: null handle");
-    if (nrows < 0 || nrows > 0xFFFFFFF0ll) return set_err(KNN_ERR_INVALID, "reserve: bad row count");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "reserve: a view is read-only");
-    HIP_TRY(hipSetDevice(h->device));
-    if (nrows <= h->cap_rows) return 0;
-    // exact-size allocation (grow_index over-allocates only when it has to guess)
-    if (int rc = move_storage(h, nrows, "reserve")) return rc;
-    return scan16_sync_rows(h, h->ntotal, 0, h->stream); // (the fp16 copies grow with the rows)
-}
-
-extern "C" int knn_flat_set_scan16(knn_handle h, int32_t mode)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "set_scan16: null handle");
-    if (mode != 0 && mode != 1 && mode != 2) return set_err(KNN_ERR_INVALID, "set_scan16: mode must be 0, 1 or 2");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->is_view) return set_err(KNN_ERR_INVALID, "set_scan16: a view uses its parent's setting");
-    if (mode && (h->approx16 || h->keep16)) return set_err(KNN_ERR_UNSUPPORTED, "set_scan16: not for an index that keeps bf16 copies (HNSW)");
-    if (h->ntotal != 0) return set_err(KNN_ERR_INVALID, "set_scan16: the index already holds rows");
-    const char *env = getenv("KNN355_SCAN16");
-    if (mode && env && strcmp(env, "0") == 0) mode = 0; // (same-tree A/B runs)
-    const char *fenv = getenv("KNN355_SCAN_FORMAT");
-    if (mode == 2 && fenv && strcmp(fenv, "16") == 0) mode = 1; // (... of the two formats)
-    h->scan16 = mode ? 1 : 0;
-    h->s16_fmt = mode == 2 ? 12 : 16;
-    h->dp16 = round_up(h->d, 64);
-    h->s16_note = mode ? "on" : "off";
-    return 0;
-}
-
-extern "C" int knn_last_scan16_info(knn_handle h, int32_t *used, int32_t *candidates_max, int64_t *fallbacks)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "null handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    uint32_t st[2] = {0u, 0u};
-    if (h->ws_s16stat.p) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipDeviceSynchronize()); // (the searches ran on their callers' streams)
-        HIP_TRY(hipMemcpy(st, h->ws_s16stat.p, sizeof st, hipMemcpyDeviceToHost));
-    }
-    if (used) *used = h->last_s16_used ? 1 : 0;
-    if (candidates_max) *candidates_max = h->last_s16_used ? (int32_t)st[0] : 0;
-    if (fallbacks) *fallbacks = (int64_t)st[1];
-    return 0;
-}
-
-extern "C" int knn_last_scan16_format(knn_handle h, int32_t *format)
-{
-    if (!h || !format) return set_err(KNN_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(h->mu);
-    *format = h->last_s16_used ? h->last_s16_fmt : 0;
-    return 0;
-}
-
-extern "C" int knn_set_tuning(knn_handle h, int32_t query_tile, int32_t nchunks, int32_t flags)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "null handle");
-    if (query_tile != 0 && query_tile != 32 && query_tile != 48 && query_tile != 64 && query_tile != 96 && query_tile != 128 && query_tile != 256)
-        return set_err(KNN_ERR_INVALID, "set_tuning: query_tile must be 0, 32, 48, 64, 96, 128 or 256");
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->force_qt = query_tile;
-    h->force_chunks = nchunks;
-    h->flags = flags & ~KNN_TUNE_PUB_ROUNDS_MASK;
-    h->pub_rounds_force = (flags & KNN_TUNE_PUB_ROUNDS_MASK) >> KNN_TUNE_PUB_ROUNDS_SHIFT; // (0: the host's choice)
-    return 0;
-}
-
-// ---- measurement aid: the box's read rate over the index's own rows -----------------------------------------------
-__global__ __launch_bounds__(256) void read_rate_kernel(const f32x4 *__restrict__ p, size_t n4, float *__restrict__ sink)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (; i + 3 * stride < n4; i += 4 * stride) { // four independent 16-byte loads in flight per lane
-        const f32x4 a = p[i], b = p[i + stride], c = p[i + 2 * stride], d = p[i + 3 * stride];
-        acc += a + b + c + d;
-    }
-    for (; i < n4; i += stride) acc += p[i];
-    if (acc[0] + acc[1] + acc[2] + acc[3] == 12345.678f) *sink = acc[0]; // (keeps the loads alive)
-}
-
-extern "C" int knn_flat_read_rate(knn_handle h, int32_t reps, float *best_ms, int64_t *bytes_read)
-{
-    if (!h || !best_ms || !bytes_read) return set_err(KNN_ERR_INVALID, "read_rate: null pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "read_rate" KNN_STALE_VIEW_MSG);
-    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "read_rate: not for an approximate (bf16) index"); // (its scans read the bf16 copies: the fp32 rows' rate bounds nothing)
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t bytes = (size_t)h->ntotal * h->dp * 4;
-    *bytes_read = (int64_t)bytes;
-    *best_ms = 0.0f;
-    if (!bytes) return 0;
-    if (h->ws_flag.ensure(64, h->done, h->stream)) return set_err(KNN_ERR_HIP, "read_rate: out of device memory");
-    EventList ev; // one pair, recorded again around every launch
-    int rc = ev.mark(h->stream);
-    if (!rc) rc = ev.mark(h->stream);
-    if (rc) return rc;
-    const hipEvent_t e0 = ev.ev[0], e1 = ev.ev[1];
-    float best = FLT_MAX;
-    for (int grid : {2048, 4096, 8192})
-        for (int r = 0; r < std::max(1, reps); r++) {
-            HIP_TRY(hipEventRecord(e0, h->stream));
-            hipLaunchKernelGGL(read_rate_kernel, dim3(grid), dim3(256), 0, h->stream, (const f32x4 *)h->xb, bytes / 16, (float *)h->ws_flag.p + 8);
-            HIP_TRY(hipEventRecord(e1, h->stream));
-            HIP_TRY(hipEventSynchronize(e1));
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-            best = std::min(best, ms);
-        }
-    *best_ms = best;
-    return 0;
-}
-
-// ---- measurement aid: the box's fp32 MFMA rate -----------------------------------------------------------------
-// every wave issues back-to-back v_mfma_f32_32x32x2_f32 on four independent accumulators, operands in registers, no
-// memory traffic: what the matrix pipes of THIS box sustain under load (the chip lowers its clock: the in-kernel clock is
-// d(s_memtime) / d(s_memrealtime) x 100 MHz), to set beside the data sheet's 157.3 TFLOP/s
-__global__ __launch_bounds__(256) void mfma_rate_kernel(float *out, int iters, unsigned long long *clk)
-{
-    float x[8], y[8];
-    unsigned s0 = (blockIdx.x * 256u + threadIdx.x) * 16u;
-    for (int i = 0; i < 16; i++) { // (random operands: constant ones toggle fewer wires and run at a higher clock than real data)
-        unsigned s = (s0 + i) * 747796405u + 2891336453u;
-        s = ((s >> ((s >> 28) + 4)) ^ s) * 277803737u;
-        s = (s >> 22) ^ s;
-        const float v = (float)(s & 0xFFFFFF) / 8388608.0f - 1.0f;
-        if (i < 8) x[i] = v;
-        else y[i - 8] = v;
-    }
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    f32x16 a0 = {}, a1 = {}, a2 = {}, a3 = {};
-    for (int i = 0; i < iters; i++) {
-#pragma unroll
-        for (int u = 0; u < 8; u += 2) {
-            a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x[u], y[u], a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x[u + 1], y[u], a1, 0, 0, 0);
-            a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(x[u], y[u + 1], a2, 0, 0, 0);
-            a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(x[u + 1], y[u + 1], a3, 0, 0, 0);
-        }
-    }
-    float s = 0.0f;
-    for (int r = 0; r < 16; r++) s += a0[r] + a1[r] + a2[r] + a3[r];
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (s == 12345.678f) out[0] = s; // (keeps the accumulators alive)
-    if (threadIdx.x == 0) {
-        clk[2 * blockIdx.x] = t1 - t0;
-        clk[2 * blockIdx.x + 1] = r1 - r0;
-    }
-}
-
-extern "C" int knn_mfma_rate(int32_t warm_ms, float *tflops, float *clock_mhz)
-{
-    if (!tflops) return set_err(KNN_ERR_INVALID, "mfma_rate: null pointer");
-    int rc = ensure_device(g_device);
-    if (rc) return rc;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g_device);
-    const int grid = 2 * std::max(1, cus), iters = 8000; // (two workgroups per CU: two waves per SIMD, as in the scan)
-    // (the stream is declared behind the buffers: it goes first, drained, whichever way the call returns)
-    PoolBuf bo(64, g_device), bc((size_t)grid * 16, g_device);
-    StreamLease s(g_device);
-    EventList ev; // one pair, recorded again around every launch
-    if (!bo || !bc || !s || ev.mark(s) || ev.mark(s)) return set_err(KNN_ERR_HIP, "mfma_rate: out of resources");
-    float *o = bo.get<float>();
-    unsigned long long *c = bc.get<unsigned long long>();
-    const hipEvent_t e0 = ev.ev[0], e1 = ev.ev[1];
-    // back-to-back launches until warm_ms of them have run (the clock settles under load), then the best of eight
-    const double flop = (double)grid * 4 /* waves */ * iters * 16.0 * (32.0 * 32 * 2 * 2);
-    float best = FLT_MAX, total = 0.0f;
-    double mhz = 0.0;
-    std::vector<unsigned long long> hc((size_t)grid * 2);
-    int timed = 0;
-    for (int r = 0; r < 4000 && timed < 8; r++) {
-        hipError_t e = hipEventRecord(e0, s);
-        hipLaunchKernelGGL(mfma_rate_kernel, dim3(grid), dim3(256), 0, s, o, iters, c);
-        if (e == hipSuccess) e = hipEventRecord(e1, s);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.0f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("mfma_rate: ") + hipGetErrorString(e));
-        total += ms;
-        if (total < (float)warm_ms) continue;
-        timed++;
-        if (ms < best) {
-            best = ms;
-            if (hipMemcpy(hc.data(), c, hc.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                double acc = 0.0;
-                for (int b = 0; b < grid; b++) acc += (double)hc[2 * b] / (double)std::max<unsigned long long>(1, hc[2 * b + 1]) * 100.0;
-                mhz = acc / grid;
-            }
-        }
-    }
-    *tflops = (float)(flop / (best * 1e-3) / 1e12);
-    if (clock_mhz) *clock_mhz = (float)mhz;
-    return 0;
-}
-
-extern "C" int knn_flat_set_batch(knn_handle h, int64_t nq_whole)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "null handle");
-    if (nq_whole < 0) return set_err(KNN_ERR_INVALID, "set_batch: negative batch size");
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->batch_hint = nq_whole;
-    return 0;
-}
-
-// ---- gather distances -------------------------------------------------------
-extern "C" int knn_gather_distances(knn_handle h, const float *q_host, int64_t nq, const int64_t *cand_ids,
-                                    const int64_t *cand_offsets, float *out_host)
-{
-    if (!h) return set_err(KNN_ERR_INVALID, "gather_distances: null handle");
-    if (nq < 0) return set_err(KNN_ERR_INVALID, "gather_distances: negative nq");
-    if (view_is_stale(h)) return set_err(KNN_ERR_INVALID, "gather_distances" KNN_STALE_VIEW_MSG); // (an empty list too: nothing of a stale view is served)
-    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "gather_distances: not for an approximate (bf16) index"); // (fp32 scores: not the ones its searches return)
-    if (nq == 0) return 0;
-    if (!q_host || !cand_offsets) return set_err(KNN_ERR_INVALID, "gather_distances: null pointer");
-    const int64_t np = cand_offsets[nq];
-    if (np == 0) return 0;
-    if (!cand_ids || !out_host) return set_err(KNN_ERR_INVALID, "gather_distances: null pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    std::vector<int32_t> pq((size_t)np);
-    for (int64_t i = 0; i < nq; i++) {
-        if (cand_offsets[i + 1] < cand_offsets[i]) return set_err(KNN_ERR_INVALID, "gather_distances: offsets not monotone");
-        for (int64_t p = cand_offsets[i]; p < cand_offsets[i + 1]; p++) {
-            if (cand_ids[p] < 0 || cand_ids[p] >= h->ntotal) return set_err(KNN_ERR_INVALID, "gather_distances: candidate id out of range");
-            pq[(size_t)p] = (int32_t)i;
-        }
-    }
-    hipStream_t s = h->stream;
-    if (h->ws_tmp2.ensure((size_t)nq * h->d * 4) || h->ws_q.ensure((size_t)nq * h->dp * 4) || h->ws_qn.ensure((size_t)nq * 4) ||
-        h->ws_I.ensure((size_t)np * 8) || h->ws_tmp.ensure((size_t)np * 4) || h->ws_D.ensure((size_t)np * 4))
-        return set_err(KNN_ERR_HIP, "gather_distances: out of device memory");
-    HIP_TRY(hipMemcpyAsync(h->ws_tmp2.p, q_host, (size_t)nq * h->d * 4, hipMemcpyHostToDevice, s));
-    int rc = pad_rows_dev((const float *)h->ws_tmp2.p, nq, h->d, (float *)h->ws_q.p, h->dp, s);
-    if (rc) return rc;
-    rc = norms_dev_impl((const float *)h->ws_q.p, nq, h->d, h->dp, (float *)h->ws_qn.p, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(h->ws_I.p, cand_ids, (size_t)np * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->ws_tmp.p, pq.data(), (size_t)np * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pair_distance_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, s, h->xb, h->yn,
-                       (const float *)h->ws_q.p, (const float *)h->ws_qn.p, h->dp, h->metric, np,
-                       (const int32_t *)h->ws_tmp.p, (const int64_t *)h->ws_I.p, (float *)h->ws_D.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_host, h->ws_D.p, (size_t)np * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Several GPUs without torch: RCCL inside the library.  One process per GPU; rank 0 makes a
-// unique id (knn_comm_unique_id), the caller hands it to the other ranks by whatever means it
-// has (a file, MPI, a socket), every rank creates its communicator, and a sharded search is
-// local scan -> ncclAllGather of the [nq][k] packed keys -> selection, all on one stream.
-// librccl is opened on first use (dlopen): a process that shards through torch.distributed
-// instead (bench.py, sharded.py) never loads a second copy.
-// ---------------------------------------------------------------------------
-#include <dlfcn.h>
-struct Id128 { char b[128]; };
-struct RcclApi {
-    void *lib = nullptr;
-    int (*GetUniqueId)(void *) = nullptr;
-    int (*CommInitRank)(void **, int, /* ncclUniqueId by value: 128 bytes */ Id128, int) = nullptr;
-    int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    const char *(*GetErrorString)(int) = nullptr;
-};
-static RcclApi g_rccl;
-static std::mutex g_rccl_mu;
-static int rccl_load()
-{
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (g_rccl.lib) return 0;
-    const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    void *L = nullptr;
-    for (const char *nm : names)
-        if ((L = dlopen(nm, RTLD_NOW | RTLD_GLOBAL))) break;
-    if (!L) return set_err(KNN_ERR_UNSUPPORTED, std::string("comm: librccl not found (") + dlerror() + ")");
-    RcclApi a;
-    a.GetUniqueId = (int (*)(void *))dlsym(L, "ncclGetUniqueId");
-    a.CommInitRank = (int (*)(void **, int, Id128, int))dlsym(L, "ncclCommInitRank");
-    a.AllGather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t))dlsym(L, "ncclAllGather");
-    a.CommDestroy = (int (*)(void *))dlsym(L, "ncclCommDestroy");
-    a.GetErrorString = (const char *(*)(int))dlsym(L, "ncclGetErrorString");
-    if (!a.GetUniqueId || !a.CommInitRank || !a.AllGather || !a.CommDestroy || !a.GetErrorString)
-        return set_err(KNN_ERR_UNSUPPORTED, "comm: librccl lacks a required symbol");
-    a.lib = L;
-    g_rccl = a;
-    return 0;
-}
-#define RCCL_TRY(expr)                                                                                        \
-    do {                                                                                                      \
-        int r_ = (expr);                                                                                      \
-        if (r_ != 0) return set_err(KNN_ERR_HIP, std::string(#expr) + ": " + g_rccl.GetErrorString(r_));      \
-    } while (0)
-
-// how long a rank waits for its peers (communicator creation, a synchronous sharded search): KNN355_COMM_TIMEOUT_S, default 120 s
-static double comm_timeout_s()
-{
-    const char *e = getenv("KNN355_COMM_TIMEOUT_S");
-    const double v = e ? atof(e) : 120.0;
-    return v > 0 ? v : 120.0;
-}
-
-struct knn_comm_s {
-    void *comm = nullptr;
-    int world = 1, rank = 0, device = 0;
-    DevBuf keys, gathered;    // this rank's keys / everybody's: one search at a time uses them (see `done`)
-    hipEvent_t done = nullptr; // recorded behind the last search's selection: a call on ANOTHER stream waits for it
-    std::mutex mu;
-};
-
-extern "C" int knn_comm_unique_id(uint8_t *id128)
-{
-    if (!id128) return set_err(KNN_ERR_INVALID, "comm_unique_id: null pointer");
-    int rc = rccl_load();
-    if (rc) return rc;
-    RCCL_TRY(g_rccl.GetUniqueId(id128));
-    return 0;
-}
-
-extern "C" int knn_comm_create(const uint8_t *id128, int32_t world, int32_t rank, int32_t device, knn_comm_s **out)
-{
-    if (!id128 || !out) return set_err(KNN_ERR_INVALID, "comm_create: null pointer");
-    if (world < 1 || rank < 0 || rank >= world) return set_err(KNN_ERR_INVALID, "comm_create: bad world / rank");
-    int rc = rccl_load();
-    if (rc) return rc;
-    rc = ensure_device(device);
-    if (rc) return rc;
-    knn_comm_s *c = new knn_comm_s();
-    c->world = world;
-    c->rank = rank;
-    c->device = device;
-    Id128 id;
-    memcpy(id.b, id128, 128);
-    // ncclCommInitRank returns when EVERY rank has called it -- with a peer that never arrives, never.  It runs on a helper
-    // thread and this call waits for it at most KNN355_COMM_TIMEOUT_S seconds (120): the first contact with a multi-GPU node
-    // fails with the rank named, not as a hang.  (A helper that is still inside RCCL when the wait runs out is left to itself:
-    // it owns its state and destroys the communicator should the call ever return.)
-    struct InitState {
-        std::mutex mu;
-        std::condition_variable cv;
-        bool finished = false, abandoned = false;
-        int r = 0;
-        void *comm = nullptr;
-    };
-    auto st = std::make_shared<InitState>();
-    std::thread([st, id, world, rank, device]() {
-        int r = hipSetDevice(device) == hipSuccess ? 0 : -1; // (the communicator belongs to the calling thread's current device)
-        void *comm = nullptr;
-        if (r == 0) r = g_rccl.CommInitRank(&comm, world, id, rank);
-        std::unique_lock<std::mutex> lk(st->mu);
-        st->r = r;
-        st->comm = comm;
-        st->finished = true;
-        if (st->abandoned && r == 0 && comm) (void)g_rccl.CommDestroy(comm);
-        st->cv.notify_all();
-    }).detach();
-    const double wait_s = comm_timeout_s();
-    {
-        std::unique_lock<std::mutex> lk(st->mu);
-        if (!st->cv.wait_for(lk, std::chrono::duration<double>(wait_s), [&] { return st->finished; })) {
-            st->abandoned = true;
-            delete c;
-            char msg[256];
-            snprintf(msg, sizeof msg, "comm_create: rank %d of %d: ncclCommInitRank did not return within %.0f s (KNN355_COMM_TIMEOUT_S) -- "
-                                      "a peer never arrived, or the ranks do not share the unique id", rank, world, wait_s);
-            return set_err(KNN_ERR_TIMEOUT, msg);
-        }
-    }
-    if (st->r != 0) {
-        delete c;
-        return set_err(KNN_ERR_HIP, st->r == -1 ? std::string("comm_create: hipSetDevice failed on the helper thread")
-                                               : std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(st->r));
-    }
-    c->comm = st->comm;
-    *out = c;
-    return 0;
-}
-
-extern "C" void knn_comm_free(knn_comm_s *c)
-{
-    if (!c) return;
-    if (hipSetDevice(c->device) == hipSuccess) {
-        if (c->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c->comm);
-        (void)hipDeviceSynchronize();
-        c->keys.release();
-        c->gathered.release();
-        if (c->done) (void)hipEventDestroy(c->done);
-    }
-    delete c;
-}
-
-// h holds THIS rank's rows (global id of local row r = id_base + r); q_dev [nq][d] is the same on every rank;
-// D_dev / I_dev receive the global result on every rank.  Every rank must call with the same nq and k.
-extern "C" int knn_sharded_search_dev(knn_handle h, knn_comm_s *c, const float *q_dev, int64_t nq, int64_t k, uint32_t id_base,
-                                      float *D_dev, int64_t *I_dev, void *stream)
-{
-    if (!c) return set_err(KNN_ERR_INVALID, "sharded_search: null communicator");
-    int rc = check_search_args(h, q_dev, nq, k, D_dev, I_dev);
-    if (rc) return rc;
-    if (h->approx16) return set_err(KNN_ERR_UNSUPPORTED, "sharded_search: not for an approximate (bf16) index"); // (before the collective, like every argument error)
-    if (nq == 0) return 0;
-    if (h->device != c->device) return set_err(KNN_ERR_INVALID, "sharded_search: index and communicator live on different devices");
-    std::lock_guard<std::mutex> lc(c->mu);
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    const size_t nkeys = (size_t)nq * k;
-    // The key and gather buffers belong to the communicator: a search on another stream than the previous one must not
-    // overwrite them while that one's all-gather or selection is still running -- it waits for the previous
-    // search's `done` event (on the GPU; the host does not block).  RCCL wants the collectives of one communicator
-    // issued in one order anyway.
-    if (!c->done) HIP_TRY(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
-    HIP_TRY(hipStreamWaitEvent(s, c->done, 0));
-    if (c->keys.ensure(nkeys * 8) || c->gathered.ensure(nkeys * 8 * c->world))
-        return set_err(KNN_ERR_HIP, "sharded_search: out of device memory (before the collective: the other ranks will wait for this one -- "
-                                    "treat a failure on any rank as fatal for the communicator)");
-    h->last_ms = -1.f;
-    rc = search_dev_impl(h, q_dev, nq, (int)k, nullptr, nullptr, (uint64_t *)c->keys.p, id_base, false, s);
-    std::string local_err;
-    if (rc) {
-        // A rank that fails locally still enters the collective -- with "no rows" for keys -- so that its peers do not
-        // hang in ncclAllGather; it returns its error afterwards.  The peers' result then lacks this shard and they
-        // cannot know: callers must treat a failure on ANY rank as a failure of the search (exchange the return codes).
-        local_err = g_err;
-        hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s, (int64_t)nkeys, h->metric,
-                           (uint64_t *)c->keys.p, (float *)nullptr, (int64_t *)nullptr);
-    }
-    RCCL_TRY(g_rccl.AllGather(c->keys.p, c->gathered.p, nkeys, /* ncclUint64 */ 5, c->comm, s));
-    if (rc) {
-        (void)hipEventRecord(c->done, s);
-        return set_err(rc, local_err);
-    }
-    SelectParams sp = {};
-    sp.in = (const uint64_t *)c->gathered.p; sp.lm_lists = c->world; sp.lm_k = (int)k;
-    sp.nq = nq; sp.k = (int)k; sp.metric = h->metric;
-    sp.D = D_dev; sp.I = I_dev;
-    rc = launch_select(sp, s);
-    (void)hipEventRecord(c->done, s);
-    if (rc) return rc;
-    if (!stream) {
-        if (c->world == 1) {
-            HIP_TRY(hipStreamSynchronize(s));
-        } else {
-            // bounded: a peer that never enters the all-gather would hold hipStreamSynchronize for ever
-            const double wait_s = comm_timeout_s();
-            const auto t0 = std::chrono::steady_clock::now();
-            int spins = 0;
-            for (;;) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) return set_err(KNN_ERR_HIP, std::string("sharded_search: ") + hipGetErrorString(q));
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > wait_s) {
-                    char msg[256];
-                    snprintf(msg, sizeof msg, "sharded_search: rank %d of %d: the search (local scan, ncclAllGather, selection) did not complete within "
-                                              "%.0f s (KNN355_COMM_TIMEOUT_S) -- a peer never entered the all-gather; the communicator is unusable", c->rank, c->world, wait_s);
-                    return set_err(KNN_ERR_TIMEOUT, msg);
-                }
-                if (++spins < 2000) std::this_thread::yield(); // (a healthy step takes a millisecond: stay close for the first ones)
-                else std::this_thread::sleep_for(std::chrono::microseconds(200));
-            }
-        }
-    }
-    return 0;
-}
-
-#include "hnsw.inc"
-#include "refine.inc"
-#include "lsh.inc"
-#include "eval.inc"
-#include "assemble.inc"
-#include "slices_eval.inc"
-#include "pr_curve.inc"
-#include "buckets.inc"
-#include "rank.inc"
-#include "windows.inc"
-#include "bootstrap.inc"
-#include "pca.inc"
-#include "fuse.inc"
-#include "overlap.inc"
-#include "range.inc"
-#include "pool.inc"
-#include "kde.inc"

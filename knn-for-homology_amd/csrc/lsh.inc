@@ -1,4 +1,4 @@
-// lsh.inc -- faiss.IndexLSH on MI355X (included by knn355.hip).
+// lsh.inc -- faiss.IndexLSH on MI355X (included by knn355_lib.hip).
 //
 // Reference call sites: seqvec_search/create_index.py:41-45 (IndexLSH(d, param), train, add),
 // pfam/search.py:27-37 (1024 bits, search k = 1000), pfam/proteins_search.py:25-26 (2048 bits).

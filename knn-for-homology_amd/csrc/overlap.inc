@@ -1,4 +1,4 @@
-// overlap.inc -- two hit lists compared as sets of ids, query by query (included by knn355.hip behind fuse.inc).
+// overlap.inc -- two hit lists compared as sets of ids, query by query (included by knn355_lib.hip behind fuse.inc).
 //
 // pfam/pfam.py counts, per query, how the true-positive ids of two searches overlap ("TP Set overlap", lines 349-370) and
 // how many distinct ids the two lists return together before their first wrong hit (auc1s_optimal, lines 602-625), in

@@ -1,4 +1,4 @@
-// pca.inc -- the moments and the projection behind decomposition.PCA (included by knn355.hip behind eval.inc).
+// pca.inc -- the moments and the projection behind decomposition.PCA (included by knn355_lib.hip behind eval.inc).
 //
 // The reference runs sklearn.decomposition.PCA(n_components=2) over the concatenated forward and scrambled embedding
 // matrices (pfam/reverse_evaluate.py:34-44, 100-108).  Its array-sized work is a d x d covariance over n rows and the

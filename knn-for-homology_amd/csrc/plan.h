@@ -1,6 +1,6 @@
 // The planners of the flat search, the symmetric self-search and the range scan: which kernel build runs, over how many chunks
 // or runs of tiles, with which seed, with how much LDS, and how a batch is cut into pieces.  Plain host arithmetic on (nb, nq,
-// k, metric, flags, num_cus): no HIP header, no handle -- knn355.hip copies what the rules read into a PlanCtx (plan_ctx) and
+// k, metric, flags, num_cus): no HIP header, no handle -- flat_search.inc copies what the rules read into a PlanCtx (plan_ctx) and
 // launches what plan_pieces / plan_search / plan_self_symmetric / plan_range return; plan_check.cpp runs the same rules on a
 // machine without a GPU.
 #pragma once
@@ -953,7 +953,7 @@ static bool plan_kde(int64_t n, int64_t ncols, int64_t m, KdePlan *out)
     return true;
 }
 
-// Which flat_scan_kernel build serves a launch is pick_scan_kernel's choice (knn355.hip) from (query tile, metric, bf16 rows,
+// Which flat_scan_kernel build serves a launch is pick_scan_kernel's choice (flat_search.inc) from (query tile, metric, bf16 rows,
 // one query tile, width of the difference build or 0, pass of a prefiltered search); this is its legality rule: nullptr, or
 // why no build serves the combination (the width of a difference build does not enter: every width has its build).
 static const char *scan_kernel_illegal(int qt, bool l2, bool approx16, bool one_qtile, int pass_mode)

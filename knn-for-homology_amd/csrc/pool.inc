@@ -1,4 +1,4 @@
-// pool.inc -- mean pooling of row ranges: the per-protein and per-domain embeddings (included by knn355.hip last).
+// pool.inc -- mean pooling of row ranges: the per-protein and per-domain embeddings (included by knn355_lib.hip last).
 //
 // The reference produces the matrix an index stores with a Python loop over ragged [L, d] per-residue arrays:
 // embedding[start - 1 : stop].mean(axis=0) per Pfam domain (pfam/embed_pfam_seqvec.py:29-40), reduce_per_protein

@@ -1,4 +1,4 @@
-// pr_curve.inc -- the precision-recall threshold sweep over (is_correct, scores) (included by knn355.hip behind
+// pr_curve.inc -- the precision-recall threshold sweep over (is_correct, scores) (included by knn355_lib.hip behind
 // assemble.inc).
 //
 // The reference computes its precision-recall curves in a Python loop over every query, once per threshold

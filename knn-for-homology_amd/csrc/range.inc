@@ -1,4 +1,4 @@
-// range.inc -- IndexFlat.range_search on MI355X (included by knn355.hip).
+// range.inc -- IndexFlat.range_search on MI355X (included by knn355_lib.hip).
 //
 // FAISS's other flat-index query (IndexFlat::range_search; published behaviour of FAISS 1.7.2's utils/distances.cpp
 // range_search_inner_product / range_search_L2sqr and python/class_wrappers.py, restated -- FAISS is not part of the
@@ -336,6 +336,7 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
     std::vector<uint64_t> offs;
     std::vector<int64_t> over;
     uint64_t done = 0; // results of the blocks before this one
+    const char *oom = "range_search: out of device memory";
     for (int64_t b0 = 0; b0 < nq; b0 += KNN_RANGE_QB) {
         const int64_t m = std::min(KNN_RANGE_QB, nq - b0);
         h->range_qblocks++;
@@ -343,30 +344,34 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
         // the block's queries on the device, zero padded to dp, and their squared norms
         const float *xq, *xn = nullptr;
         if (q_host) {
-            if (h->ws_rq.ensure((size_t)m * h->d * 4, h->done, s) || h->ws_rqn.ensure((size_t)m * 4, h->done, s))
-                return set_err(KNN_ERR_HIP, "range_search: out of device memory");
-            HIP_TRY(hipMemcpyAsync(h->ws_rq.p, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
-            xq = (const float *)h->ws_rq.p;
+            float *rq, *rqn;
+            if (!(rq = scratch<float>(h, h->ws_rq, (size_t)m * h->d, s, oom)) || !(rqn = scratch<float>(h, h->ws_rqn, (size_t)m, s, oom))) return KNN_ERR_HIP;
+            HIP_TRY(hipMemcpyAsync(rq, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
+            xq = rq;
             if (dp != h->d) {
-                if (h->ws_q.ensure((size_t)m * dp * 4, h->done, s)) return set_err(KNN_ERR_HIP, "range_search: out of device memory");
-                int rc = pad_rows_dev(xq, m, h->d, (float *)h->ws_q.p, dp, s);
+                float *padded = scratch<float>(h, h->ws_q, (size_t)m * dp, s, oom);
+                if (!padded) return KNN_ERR_HIP;
+                int rc = pad_rows_dev(xq, m, h->d, padded, dp, s);
                 if (rc) return rc;
-                xq = (const float *)h->ws_q.p;
+                xq = padded;
             }
             if (l2 && !pl.diff) {
-                int rc = norms_dev_impl(xq, m, h->d, dp, (float *)h->ws_rqn.p, s);
+                int rc = norms_dev_impl(xq, m, h->d, dp, rqn, s);
                 if (rc) return rc;
-                xn = (const float *)h->ws_rqn.p;
+                xn = rqn;
             }
         } else {
             xq = h->xb + (size_t)(self_row0 + b0) * dp;
             if (l2 && !pl.diff) xn = h->yn + self_row0 + b0; // (the stored norms: the same chain as norm_rows_kernel over these rows)
         }
         const int64_t pairs = m * pl.nchunks, segcap = range_segcap(pl, m);
-        if (h->ws_rsegD.ensure((size_t)pairs * segcap * 4, h->done, s) || h->ws_rsegI.ensure((size_t)pairs * segcap * 8, h->done, s) ||
-            h->ws_rcnt.ensure((size_t)pairs * 4 * 2, h->done, s))
-            return set_err(KNN_ERR_HIP, "range_search: out of device memory");
-        uint32_t *cnt_dev = (uint32_t *)h->ws_rcnt.p, *cnt2_dev = cnt_dev + pairs;
+        float *segD;
+        int64_t *segI;
+        uint32_t *cnt_dev;
+        if (!(segD = scratch<float>(h, h->ws_rsegD, (size_t)pairs * segcap, s, oom)) || !(segI = scratch<int64_t>(h, h->ws_rsegI, (size_t)pairs * segcap, s, oom)) ||
+            !(cnt_dev = scratch<uint32_t>(h, h->ws_rcnt, (size_t)pairs * 2, s, oom)))
+            return KNN_ERR_HIP;
+        uint32_t *cnt2_dev = cnt_dev + pairs;
         p.xq = xq;
         p.xn = xn;
         p.nq = m;
@@ -379,8 +384,8 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
         p.offs = nullptr;
         p.expect = nullptr;
         p.cnt = cnt_dev;
-        p.outD = (float *)h->ws_rsegD.p;
-        p.outI = (int64_t *)h->ws_rsegI.p;
+        p.outD = segD;
+        p.outI = segI;
         int rc = range_launch(h, p, pl, s);
         if (rc) return rc;
         cnt.resize((size_t)pairs);
@@ -398,9 +403,12 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
         h->range_I.resize((size_t)(done + block_total));
         // copy-out in runs of whole queries that fit the output buffer (one query at least: ntotal entries at most)
         const size_t out_cap = std::max<size_t>(KNN_RANGE_OUT_BYTES / 12, (size_t)h->ntotal);
-        if (h->ws_routD.ensure(out_cap * 4, h->done, s) || h->ws_routI.ensure(out_cap * 8, h->done, s) ||
-            h->ws_roff.ensure((size_t)pairs * 8 * 2, h->done, s) || h->ws_rsel.ensure((size_t)m * 8, h->done, s))
-            return set_err(KNN_ERR_HIP, "range_search: out of device memory");
+        float *outD;
+        int64_t *outI, *sel;
+        uint64_t *offs_dev;
+        if (!(outD = scratch<float>(h, h->ws_routD, out_cap, s, oom)) || !(outI = scratch<int64_t>(h, h->ws_routI, out_cap, s, oom)) ||
+            !(offs_dev = scratch<uint64_t>(h, h->ws_roff, (size_t)pairs * 2, s, oom)) || !(sel = scratch<int64_t>(h, h->ws_rsel, (size_t)m, s, oom)))
+            return KNN_ERR_HIP;
         for (int64_t qa = 0; qa < m;) {
             int64_t qb = qa + 1;
             while (qb < m && lims[b0 + qb + 1] - lims[b0 + qa] <= out_cap) qb++;
@@ -422,11 +430,9 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
                 }
                 if (ov) over.push_back(q);
             }
-            uint64_t *offs_dev = (uint64_t *)h->ws_roff.p;
             HIP_TRY(hipMemcpyAsync(offs_dev, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(range_gather_kernel, dim3((unsigned)((qb - qa) * pl.nchunks)), dim3(64), 0, s, (const float *)h->ws_rsegD.p,
-                               (const int64_t *)h->ws_rsegI.p, (const uint32_t *)cnt_dev, segcap, qa * pl.nchunks, (const uint64_t *)offs_dev,
-                               (float *)h->ws_routD.p, (int64_t *)h->ws_routI.p);
+            hipLaunchKernelGGL(range_gather_kernel, dim3((unsigned)((qb - qa) * pl.nchunks)), dim3(64), 0, s, (const float *)segD,
+                               (const int64_t *)segI, (const uint32_t *)cnt_dev, segcap, qa * pl.nchunks, (const uint64_t *)offs_dev, outD, outI);
             HIP_TRY(hipGetLastError());
             if (!over.empty()) {
                 // ONE rescan of the queries whose runs overflowed, same tile and chunks, straight to their final offsets with
@@ -441,15 +447,16 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
                         offs2[(size_t)j * pl.nchunks + c] = offs[(size_t)(over[j] - qa) * pl.nchunks + c];
                         exp2[(size_t)j * pl.nchunks + c] = cnt[(size_t)over[j] * pl.nchunks + c];
                     }
-                if (h->ws_rq2.ensure((size_t)no * dp * 4 + (size_t)no * 4, h->done, s) ||
-                    h->ws_rexp.ensure((size_t)no * pl.nchunks * 4, h->done, s))
-                    return set_err(KNN_ERR_HIP, "range_search: out of device memory");
+                float *q2;
+                uint32_t *expect;
+                if (!(q2 = scratch<float>(h, h->ws_rq2, (size_t)no * dp + (size_t)no, s, oom)) || !(expect = scratch<uint32_t>(h, h->ws_rexp, (size_t)no * pl.nchunks, s, oom)))
+                    return KNN_ERR_HIP;
                 uint64_t *offs2_dev = offs_dev + offs.size();
                 HIP_TRY(hipMemcpyAsync(offs2_dev, offs2.data(), offs2.size() * 8, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(h->ws_rexp.p, exp2.data(), exp2.size() * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(h->ws_rsel.p, over.data(), (size_t)no * 8, hipMemcpyHostToDevice, s));
-                float *q2 = (float *)h->ws_rq2.p, *qn2 = q2 + (size_t)no * dp;
-                hipLaunchKernelGGL(range_pick_kernel, dim3((unsigned)no), dim3(256), 0, s, xq, xn, dp, (const int64_t *)h->ws_rsel.p, q2,
+                HIP_TRY(hipMemcpyAsync(expect, exp2.data(), exp2.size() * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(sel, over.data(), (size_t)no * 8, hipMemcpyHostToDevice, s));
+                float *qn2 = q2 + (size_t)no * dp;
+                hipLaunchKernelGGL(range_pick_kernel, dim3((unsigned)no), dim3(256), 0, s, xq, xn, dp, (const int64_t *)sel, q2,
                                    xn ? qn2 : nullptr);
                 HIP_TRY(hipGetLastError());
                 RangeParams p2 = p;
@@ -463,10 +470,10 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
                 p2.nt_rows = pl2.nqtiles == 1;
                 p2.segcap = 0;
                 p2.offs = offs2_dev;
-                p2.expect = (const uint32_t *)h->ws_rexp.p;
+                p2.expect = expect;
                 p2.cnt = cnt2_dev;
-                p2.outD = (float *)h->ws_routD.p;
-                p2.outI = (int64_t *)h->ws_routI.p;
+                p2.outD = outD;
+                p2.outI = outI;
                 rc = range_launch(h, p2, pl2, s);
                 if (rc) return rc;
                 std::vector<uint32_t> cnt2((size_t)no * pl.nchunks);
@@ -475,8 +482,8 @@ static int range_search_impl(knn_index_s *h, const float *q_host, int64_t self_r
                 h->last_ms += range_launch_ms(h);
                 if (cnt2 != exp2) return set_err(KNN_ERR_HIP, "range_search: the overflow rescan counted differently from the first pass");
             }
-            HIP_TRY(hipMemcpyAsync(h->range_D.data() + run0, h->ws_routD.p, run_n * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(h->range_I.data() + run0, h->ws_routI.p, run_n * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(h->range_D.data() + run0, outD, run_n * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(h->range_I.data() + run0, outI, run_n * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             qa = qb;
         }

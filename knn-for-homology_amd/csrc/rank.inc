@@ -1,4 +1,4 @@
-// rank.inc -- one stable order over every hit of a result set (included by knn355.hip behind pr_curve.inc).
+// rank.inc -- one stable order over every hit of a result set (included by knn355_lib.hip behind pr_curve.inc).
 //
 // The reference's dataset-wide curves order the whole result set at once on the host: pfam/pfam.py:561-598 (argsort of the
 // flattened scores, the running sum of `correct` in that order, searchsorted at 10 000 recall levels), the cumulative

@@ -1,4 +1,4 @@
-// refine.inc -- faiss.IndexRefineFlat on MI355X: exact re-scoring of a base index's candidates (included by knn355.hip).
+// refine.inc -- faiss.IndexRefineFlat on MI355X: exact re-scoring of a base index's candidates (included by knn355_lib.hip).
 //
 // FAISS 1.7.2's IndexRefineFlat (not in the reference tree; published behaviour restated): search the base index for
 // k * k_factor labels per query, IndexFlat::compute_distance_subset scores exactly those rows against the stored fp32
@@ -128,11 +128,10 @@ static int refine_sum_ms(const EventList &ev, float *ms)
 static int refine_batch(knn_index_s *flat, const float *xq_dev, const int64_t *labels_dev, int64_t m, int kb, int k, float *D_dev,
                         int64_t *I_dev, hipStream_t s, EventList &ev)
 {
-    if (flat->ws_rfkeys.ensure((size_t)m * kb * 8, flat->done, s)) return set_err(KNN_ERR_HIP, "refine: out of device memory");
     RefineParams p;
+    if (!(p.keys = scratch<uint64_t>(flat, flat->ws_rfkeys, (size_t)m * kb, s, "refine: out of device memory"))) return KNN_ERR_HIP;
     p.xb = flat->xb; p.nb = flat->ntotal; p.dp = flat->dp;
     p.xq = xq_dev; p.labels = labels_dev; p.kb = kb;
-    p.keys = (uint64_t *)flat->ws_rfkeys.p;
     const unsigned grid = (unsigned)(m * ((kb + RF_ROWS - 1) / RF_ROWS));
     void (*kern)(RefineParams) = flat->metric == KNN_METRIC_L2 ? refine_rescore_kernel<true> : refine_rescore_kernel<false>;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RF_LDS));
@@ -186,27 +185,26 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
     hipStream_t s = h->stream;
     const int64_t QB = 16384;
     const int64_t mb = std::min(QB, nq);
-    if (h->ws_rfq.ensure((size_t)mb * h->d * 4, h->done, s) || (h->dp != h->d && h->ws_rfqp.ensure((size_t)mb * h->dp * 4, h->done, s)) ||
-        h->ws_rfI.ensure((size_t)mb * kb * 8, h->done, s) || h->ws_rfD.ensure((size_t)mb * k * 4, h->done, s) ||
-        h->ws_rfI2.ensure((size_t)mb * k * 8, h->done, s))
-        return set_err(KNN_ERR_HIP, "flat_refine: out of device memory");
+    const char *oom = "flat_refine: out of device memory";
+    float *q_dev, *qp_dev = nullptr, *D_dev; // (qp_dev: the padded copy, where one is needed)
+    int64_t *lab_dev, *I_dev;
+    if (!(q_dev = scratch<float>(h, h->ws_rfq, (size_t)mb * h->d, s, oom)) || (h->dp != h->d && !(qp_dev = scratch<float>(h, h->ws_rfqp, (size_t)mb * h->dp, s, oom))) ||
+        !(lab_dev = scratch<int64_t>(h, h->ws_rfI, (size_t)mb * kb, s, oom)) || !(D_dev = scratch<float>(h, h->ws_rfD, (size_t)mb * k, s, oom)) ||
+        !(I_dev = scratch<int64_t>(h, h->ws_rfI2, (size_t)mb * k, s, oom)))
+        return KNN_ERR_HIP;
     EventList ev;
     for (int64_t b0 = 0; b0 < nq; b0 += QB) {
         const int64_t m = std::min(QB, nq - b0);
-        HIP_TRY(hipMemcpyAsync(h->ws_rfq.p, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
-        const float *xq = (const float *)h->ws_rfq.p;
-        if (h->dp != h->d) {
-            if ((rc = pad_rows_dev((const float *)h->ws_rfq.p, m, h->d, (float *)h->ws_rfqp.p, h->dp, s))) return rc;
-            xq = (const float *)h->ws_rfqp.p;
-        }
-        HIP_TRY(hipMemcpyAsync(h->ws_rfI.p, labels_host + b0 * kb, (size_t)m * kb * 8, hipMemcpyHostToDevice, s));
-        rc = refine_batch(h, xq, (const int64_t *)h->ws_rfI.p, m, (int)kb, (int)k, (float *)h->ws_rfD.p, (int64_t *)h->ws_rfI2.p, s, ev);
+        HIP_TRY(hipMemcpyAsync(q_dev, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
+        if (h->dp != h->d && (rc = pad_rows_dev(q_dev, m, h->d, qp_dev, h->dp, s))) return rc;
+        HIP_TRY(hipMemcpyAsync(lab_dev, labels_host + b0 * kb, (size_t)m * kb * 8, hipMemcpyHostToDevice, s));
+        rc = refine_batch(h, qp_dev ? qp_dev : q_dev, lab_dev, m, (int)kb, (int)k, D_dev, I_dev, s, ev);
         if (rc) {
             (void)hipStreamSynchronize(s); // (nothing of this batch is left running behind the error)
             return rc;
         }
-        HIP_TRY(hipMemcpyAsync(D_host + b0 * k, h->ws_rfD.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(I_host + b0 * k, h->ws_rfI2.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(D_host + b0 * k, D_dev, (size_t)m * k * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(I_host + b0 * k, I_dev, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     return refine_sum_ms(ev, h->refine_ms);

@@ -1,4 +1,4 @@
-// slices_eval.inc -- slice-level correctness and AUC1 of slice searches (included by knn355.hip behind assemble.inc).
+// slices_eval.inc -- slice-level correctness and AUC1 of slice searches (included by knn355_lib.hip behind assemble.inc).
 //
 // The reference judges the hits of pfam/slices/slices_search.py in Python loops under tqdm: per slice the Pfam domains
 // of its protein that lie inside the slice or merely intersect it (pfam/slices/slices.py:49-68), the family sizes

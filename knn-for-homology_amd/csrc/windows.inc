@@ -1,5 +1,5 @@
 // windows.inc -- statistics of boolean columns, and of the key itself, over contiguous ranges of the ranked order
-// (included by knn355.hip behind rank.inc).
+// (included by knn355_lib.hip behind rank.inc).
 //
 // The reference draws three families of curves from arrays "put into the order of a key": rolling means over a window
 // of W ranks (seqvec_search/utils.py:103 rolling_mean = numpy.convolve(data, ones(W) / W, "valid"), called at

@@ -2,18 +2,19 @@
 tests/test_flat_lifecycle_reference.py: plain numpy plus the CPU oracle, nothing of the library under test.
 
 The model's state is the parent's rows (float32 [n][d]) and row capacity, and per view the row count at its creation and
-whether it is alive or stale.  Its rules restate the storage rules of csrc/knn355.hip:
+whether it is alive or stale.  Its rules restate the storage rules of csrc/flat_index.inc
+(knn_flat_reserve: flat_info.inc, knn_flat_normalize_rows: flat_search.inc):
 
-  add(x)            grow_index (knn355.hip:3552-3587): the first add (capacity 0) fits exactly; a later add beyond the
+  add(x)            grow_index -> move_storage: the first add (capacity 0) fits exactly; a later add beyond the
                     capacity grows to max(need, cap + cap // 2); storage that moves (there was some: capacity > 0) makes
-                    every view stale (:3575-3576); an add that fits leaves the views alive with their old row count.
-  reserve(n)        knn_flat_reserve (:4915-4950): beyond the capacity the capacity becomes exactly n and the views go
+                    every view stale (move_storage bumps storage_gen); an add that fits leaves the views alive with their old row count.
+  reserve(n)        knn_flat_reserve -> move_storage: beyond the capacity the capacity becomes exactly n and the views go
                     stale (again only if there was storage to move); otherwise nothing happens.
-  reset()           knn_reset -> free_index_buffers (:3484-3503): no rows, capacity 0, every view stale.
+  reset()           knn_reset -> free_index_buffers: no rows, capacity 0, every view stale.
   free()            knn_free -> free_index_buffers: the same, and the parent is gone.
-  normalize_rows()  knn_flat_normalize_rows (:4827-4844): the rows become oracle.normalize_l2 of themselves, in place: live
+  normalize_rows()  knn_flat_normalize_rows: the rows become oracle.normalize_l2 of themselves, in place: live
                     views see the new values of their first n rows (storage is shared and does not move).
-  view(of)          knn_flat_view (:3432-3474): of the parent, or of a live view (the same rows, stale together with it,
+  view(of)          knn_flat_view: of the parent, or of a live view (the same rows, stale together with it,
                     which here is: with every other view); of a stale view it is refused (Refused).
 
 Expected answers are the oracle's on the model's rows: flat_search with FAISS's batch rule for `search` and for a window

@@ -10,7 +10,7 @@ or reaches its introspection, so these rows are checked against the stand-alone 
 
 EXPECT maps a case's name to (kernel, query_tile, db_tile, nchunks, grid, seed_stride, stat_rank, sample_rows), as last_scan() /
 last_seed() report them.  The literals were NOT produced by csrc/plan.h: they come from the planner as it stood in knn355.hip
-before it moved (make_plan, the head of search_view, the piece cutting of search_keys_impl, taken verbatim from that commit and
+(today its host side is flat_search.inc) before it moved (make_plan, the head of search_view, the piece cutting of search_keys_impl, taken verbatim from that commit and
 compiled for the host with 256 CUs, the MI355X's count), so both tests compare the planner with its predecessor and not with
 itself.
 
@@ -25,7 +25,7 @@ was asked to hold is eligible where it should be: none had to move.
 RANGE_CASES / RANGE_EXPECT: one block of a range search (plan_range, range_segcap): (kernel, query_tile, db_tile, nqtiles,
 nchunks, tiles_base, tiles_rem, grid, diff, LDS bytes, segcap), as `plan_check range` prints them.
 
-The literals of both tables come from self_search_symmetric (knn355.hip) and range_make_plan / range_search_impl (range.inc)
+The literals of both tables come from self_search_symmetric (flat_search.inc) and range_make_plan / range_search_impl (range.inc)
 as they stood before their decisions moved to csrc/plan.h, taken verbatim from that commit and compiled for the host with
 256 CUs."""
 from collections import namedtuple

@@ -1,5 +1,5 @@
 """GPU: the batched host searches of different index types share one set of copy pipes per device and one double-buffered
-result download (ResultPipe in knn355.hip).  Whoever holds the pipes downloads batch b - 1 while batch b runs; the others
+result download (ResultPipe in host_core.inc).  Whoever holds the pipes downloads batch b - 1 while batch b runs; the others
 run their batches one after the other on their own streams.  Three index types searched at once on one device -- a holder
 of one type beside non-holders of the others -- must each return what they return alone, bit for bit.
 

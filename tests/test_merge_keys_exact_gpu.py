@@ -21,7 +21,7 @@ KNN_ERR_INVALID = -1
 
 
 def select_build(nq, n):
-    """(R, NT) of the select_topk_kernel<R, NT, false> that launch_select (csrc/knn355.hip) launches for a list-major merge of
+    """(R, NT) of the select_topk_kernel<R, NT, false> that launch_select (csrc/flat_search.inc) launches for a list-major merge of
     n = nlists * k keys per query -- a mirror of its choice, kept beside the table that must reach every branch of it"""
     if nq >= 512 and n <= 64 * 32:  # one wave per query
         return (8, 64) if n <= 64 * 8 else (32, 64)
