@@ -491,7 +491,7 @@ extern "C" int knn_normalize_l2(float *x_host, int64_t n, int32_t d)
 }
 
 // ---- the owners of the batched host searches (DESIGN 4.10, 4.5): the device's copy pipes, the scaffold of a host entry, the
-// piped result download.  hnsw.inc, lsh.inc, pca.inc, kde.inc, pool.inc and overlap.inc use them as host_search does
+// piped result download.  hnsw_search.inc, lsh.inc, pca.inc, kde.inc, pool.inc and overlap.inc use them as host_search does
 // Copy streams of the pipelined host search: one set per device for the whole process, created on
 // first use (a HIP stream costs milliseconds to create and callers such as cath/search.py build a
 // fresh index per file).  Whoever holds `mu` pipelines; a concurrent host search on the same

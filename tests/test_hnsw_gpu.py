@@ -216,7 +216,7 @@ def test_graph_invariants_and_determinism(gpu_faiss):
                                                      (1, 24, 64, 30_000, 1, 150), (0, 63, 32, 24_000, 1, 40), (1, 2, 16, 12_000, 2, 40)])
 def test_device_links_build_the_host_links_graph(gpu_faiss, monkeypatch, metric, M, d, n, pieces, efc):
     """Construction keeps level 0 on the device since round 4 (candidates, forward selection, forward links, reverse requests
-    sorted by (node, v, from), appended or pruned: hnsw.inc::hnsw_level0_links_device); KNN355_HNSW_HOST_LINKS=1 is the
+    sorted by (node, v, from), appended or pruned: hnsw_build.inc::hnsw_level0_links_device); KNN355_HNSW_HOST_LINKS=1 is the
     host bookkeeping of rounds 1-3.  Same arithmetic, same request order, same members per pruning group: the two graphs
     are IDENTICAL -- every list of every level -- and so are the search results.  (M = 8: small lists, almost every reverse
     request prunes; several add calls: the device's lists outlive a call and the host copy is brought up to date in between
