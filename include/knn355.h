@@ -1005,6 +1005,50 @@ int knn_flat_read_rate(knn_handle h, int32_t reps, float *best_ms, int64_t *byte
  * in-kernel shader clock of that launch.  The data sheet's dense fp32 MFMA peak is 157.3 TFLOP/s at 2.4 GHz. */
 int knn_mfma_rate(int32_t warm_ms, float *tflops, float *clock_mhz);
 
+/* ---- weighted mixes of embedding layers, searched and scored where they lie ---------------
+ * cath/compare_seqvec_layer.py:44-56, 87-91: ratio[0] * cnn + ratio[1] * lstm1 + ratio[2] * lstm2 for every point of a
+ * simplex grid, each mix through cath.search.search, of which only is_correct[:, 3, 0].mean() is kept;
+ * seqvec_search/figures/layers.py:37-47 and lstm1_vs_sum.py: sums, differences and column blocks of one [N, 3072] matrix.
+ * A knn_mix handle holds L = 1 .. KNN_MIX_MAX_LAYERS layers of n rows and d columns on the device; they go up once.
+ * The contract of a mix with the float32 weights w, per row r and column c:
+ *     out[r][c] = ((w[0] * x0[r][c] + w[1] * x1[r][c]) + w[2] * x2[r][c]) + w[3] * x3[r][c]
+ * left to right over the L layers, every product and every sum rounded to float32 on its own (no fma, no wider
+ * accumulator): numpy's statement on float32 arrays with float32 weights, bit for bit (numpy 1.x casts the float64 scalars
+ * of the reference's grid to float32 by value; tests/layer_mix_reference.py does it by hand).  A zero weight's term is
+ * computed like any other: 0 * inf is NaN, 0 * x + y follows IEEE.
+ * knn_mix_set_layer copies layer i from host rows x_host + r * row_stride (row_stride >= d in floats, so that a column
+ * block of a [n, L * d] matrix is a layer); knn_mix_set_layer_dev borrows rows that already lie on the device: nothing is
+ * copied, the caller keeps them alive and unchanged while the handle uses them, `stream` (the one that produced them) is
+ * waited for.  All layers have the same n: a layer with another n is refused while another layer is set.
+ * knn_mix_into makes `flat` hold the mix: it is reset, n rows are reserved, the rows are written by mix_rows_kernel at the
+ * index's padded stride and then go through what knn_flat_add_dev does behind its copy (norms, the row copies of
+ * knn_flat_set_scan16 / an approximate index, views of the old rows stale); with normalize != 0 the rows are normalised as
+ * by knn_flat_normalize_rows first.  Afterwards `flat` cannot be told from an index that had knn_flat_add(mix) and
+ * knn_flat_normalize_rows called on it.
+ * knn_mix_sweep does, for each of the G weight rows, knn_mix_into (normalised when flat's metric is the inner product, as
+ * cath.search.search does), knn_flat_search_self_dev with k neighbours and mix_top1_kernel: counts_out[g][l] = the number of
+ * rows q with mapping[q][l] == mapping[I[q][column]][l] (mapping: int32 [n][nlevels] on the host; a hit < 0 or >= n is
+ * wrong, knn_eval_levels' rule; column 1 is the first hit behind the self hit).  Integer counting: exact, whatever the
+ * order.  D_host / I_host: both NULL, and only the counts leave the device, or both given, [G][n][k] scores and ids.
+ * KNN_ERR_INVALID before anything is allocated, copied or launched, outputs untouched: a null handle or pointer, a layer
+ * without rows, flat's dimension other than d, flat a view or on another device, nlayers outside 1 .. KNN_MIX_MAX_LAYERS
+ * (knn_mix_create), k outside 1 .. KNN_MAX_K, column outside 0 .. k - 1, nlevels outside 1 .. KNN_MIX_MAX_LEVELS, only one
+ * of D_host / I_host.
+ * knn_mix_last_ms: HIP-event milliseconds of the calling thread's last successful knn_mix_sweep, summed over its mixes --
+ * knn_mix_into's launches, the self-search (host gaps included), the scoring kernel; after knn_mix_into the first alone. */
+#define KNN_MIX_MAX_LAYERS 4
+#define KNN_MIX_MAX_LEVELS 8
+typedef struct knn_mix_s *knn_mix_handle;
+int knn_mix_create(int32_t d, int32_t nlayers, knn_mix_handle *out);
+void knn_mix_free(knn_mix_handle h);
+int knn_mix_set_layer(knn_mix_handle h, int32_t i, const float *x_host, int64_t n, int64_t row_stride);
+int knn_mix_set_layer_dev(knn_mix_handle h, int32_t i, const float *x_dev, int64_t n, int64_t row_stride, void *stream);
+int knn_mix_into(knn_mix_handle h, const float *weights /* [nlayers] */, knn_handle flat, int32_t normalize);
+int knn_mix_sweep(knn_mix_handle h, const float *weights /* [G][nlayers] */, int64_t G, knn_handle flat, int64_t k,
+                  const int32_t *mapping /* [n][nlevels] */, int32_t nlevels, int64_t column,
+                  int64_t *counts_out /* [G][nlevels] */, float *D_host, int64_t *I_host);
+int knn_mix_last_ms(float *mix_ms, float *search_ms, float *score_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,13 @@ def _declare(L):
         "knn_flat_range_search_self": (c_int32, [H, c_int64, c_int64, c_float, c_void_p]),
         "knn_flat_range_fetch": (c_int32, [H, c_void_p, c_void_p]),
         "knn_last_range_info": (c_int32, [H, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+        "knn_mix_create": (c_int32, [c_int32, c_int32, POINTER(H)]),
+        "knn_mix_free": (None, [H]),
+        "knn_mix_set_layer": (c_int32, [H, c_int32, c_void_p, c_int64, c_int64]),
+        "knn_mix_set_layer_dev": (c_int32, [H, c_int32, c_void_p, c_int64, c_int64, c_void_p]),
+        "knn_mix_into": (c_int32, [H, c_void_p, H, c_int32]),
+        "knn_mix_sweep": (c_int32, [H, c_void_p, c_int64, H, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
+        "knn_mix_last_ms": (c_int32, [f32p, f32p, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the library does not export the ABI

@@ -31,3 +31,4 @@
 #include "range.inc"
 #include "pool.inc"
 #include "kde.inc"
+#include "mix.inc"

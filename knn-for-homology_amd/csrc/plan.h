@@ -920,6 +920,56 @@ static void pool_assign_chunks(const int64_t *starts, const int64_t *stops, int6
     }
 }
 
+// ---- weighted layer mixes (mix.inc) --------------------------------------------------
+static const int MIX_BLOCK = 256;     // threads of a workgroup of mix_rows_kernel and mix_top1_kernel
+static const int MIX_MAX_GRID = 2048; // workgroups of mix_rows_kernel, at most (256 CUs x 8): the rest is a grid-stride loop
+
+struct MixPlan {
+    bool vec;             // an item is four columns moved by 16-byte loads and one 16-byte store; false: one column
+    int per_row;          // items of one output row: dp / 4, or dp
+    int64_t items;        // n * per_row (the padding columns d .. dp - 1 are items too: they are written as zeros)
+    int grid;             // workgroups of MIX_BLOCK threads: ceil(items / MIX_BLOCK), MIX_MAX_GRID at most
+};
+
+// false: not a legal launch (n outside [1, 0xFFFFFFF0], d < 1, dp < d or dp >= 2^30, nlayers outside [1, KNN_MIX_MAX_LAYERS], a
+// null base, a row stride below d).  The 16-byte build needs every layer's base and the output's to be multiples of 16 bytes
+// and every row stride, the output's (dp) included, to be a multiple of four floats; anything else is moved float by float.
+// A quad that straddles d (d no multiple of four) is handled float by float inside the 16-byte build.
+static bool plan_mix(int64_t n, int64_t d, int64_t dp, int nlayers, const uintptr_t *bases, const int64_t *strides, uintptr_t out_base, MixPlan *out)
+{
+    if (n < 1 || n > 0xFFFFFFF0ll || d < 1 || dp < d || dp >= ((int64_t)1 << 30) || nlayers < 1 || nlayers > KNN_MIX_MAX_LAYERS || !out_base) return false;
+    MixPlan pl;
+    pl.vec = out_base % 16 == 0 && dp % 4 == 0;
+    for (int i = 0; i < nlayers; i++) {
+        if (!bases[i] || strides[i] < d) return false;
+        pl.vec = pl.vec && bases[i] % 16 == 0 && strides[i] % 4 == 0;
+    }
+    pl.per_row = (int)(pl.vec ? dp / 4 : dp);
+    pl.items = n * pl.per_row;
+    pl.grid = (int)std::min<int64_t>((pl.items + MIX_BLOCK - 1) / MIX_BLOCK, MIX_MAX_GRID);
+    *out = pl;
+    return true;
+}
+
+// What knn_mix_into and knn_mix_sweep refuse before anything is allocated, copied or launched: nullptr, or the message.
+// layers_set: bit i = layer i has rows; sweep: the arguments of knn_mix_sweep are checked too (k, column, nlevels).
+static const char *mix_args_illegal(int d, int nlayers, unsigned layers_set, int flat_d, bool flat_is_view, bool sweep, int64_t g, int64_t k, int64_t column,
+                                    int64_t nlevels)
+{
+    if (nlayers < 1 || nlayers > KNN_MIX_MAX_LAYERS) return "nlayers must be 1 .. KNN_MIX_MAX_LAYERS";
+    if (d < 1) return "d must be positive";
+    for (int i = 0; i < nlayers; i++)
+        if (!((layers_set >> i) & 1u)) return "a layer has no rows (knn_mix_set_layer)";
+    if (flat_d != d) return "the index's dimension is not the layers'";
+    if (flat_is_view) return "a view is read-only";
+    if (!sweep) return nullptr;
+    if (g < 0) return "negative number of mixes";
+    if (k < 1 || k > KNN_MAX_K) return "k must be 1 .. KNN_MAX_K";
+    if (column < 0 || column >= k) return "column must be 0 .. k - 1";
+    if (nlevels < 1 || nlevels > KNN_MIX_MAX_LEVELS) return "nlevels must be 1 .. KNN_MIX_MAX_LEVELS";
+    return nullptr;
+}
+
 // ---- one-dimensional kernel density estimates (kde.inc) -----------------------------
 // Constants of the arithmetic contract above knn_kde_stats (include/knn355.h), not functions of the device.
 static const int KDE_CHUNK = 16384; // consecutive rows whose terms are summed by one workgroup

@@ -509,6 +509,76 @@ static void sweep_pool()
     }
 }
 
+// ---- weighted layer mixes (mix.inc) ----
+// `plan_check mix`: lines "n d dp nlayers out_base base0 stride0 ... base3 stride3" (four pairs, those past nlayers ignored)
+// -> vec per_row items grid, or "refused"; every plan that is not refused is walked as mix_rows_kernel walks it, a wrong
+// walk prints "broken"
+static int run_mix()
+{
+    long long n, d, dp, stride[KNN_MIX_MAX_LAYERS];
+    unsigned long long out_base, base[KNN_MIX_MAX_LAYERS];
+    int nlayers;
+    while (scanf("%lld %lld %lld %d %llu %llu %lld %llu %lld %llu %lld %llu %lld", &n, &d, &dp, &nlayers, &out_base, &base[0], &stride[0], &base[1], &stride[1],
+                 &base[2], &stride[2], &base[3], &stride[3]) == 13) {
+        uintptr_t bases[KNN_MIX_MAX_LAYERS];
+        int64_t strides[KNN_MIX_MAX_LAYERS];
+        for (int i = 0; i < KNN_MIX_MAX_LAYERS; i++) {
+            bases[i] = (uintptr_t)base[i];
+            strides[i] = stride[i];
+        }
+        MixPlan p;
+        if (!plan_mix(n, d, dp, nlayers, bases, strides, (uintptr_t)out_base, &p)) {
+            printf("refused\n");
+            continue;
+        }
+        bool ok = p.grid >= 1 && p.grid <= MIX_MAX_GRID && p.items == n * p.per_row && p.per_row == (p.vec ? dp / 4 : dp);
+        ok = ok && (int64_t)p.grid * MIX_BLOCK >= std::min<int64_t>(p.items, (int64_t)MIX_MAX_GRID * MIX_BLOCK);
+        // the kernel's own walk, for outputs small enough to count: every float of [n][dp] is written exactly once, nothing
+        // is read at or past column d, and the running (row, item) pair is the item's quotient and remainder
+        if (ok && n * dp <= (1 << 22)) {
+            std::vector<uint8_t> written((size_t)(n * dp), 0);
+            const int64_t step = (int64_t)p.grid * MIX_BLOCK;
+            for (int64_t first = 0; first < step && ok; first++) {
+                int64_t r = first / p.per_row;
+                int q = (int)(first - r * p.per_row);
+                const int64_t step_r = step / p.per_row;
+                const int step_q = (int)(step - step_r * p.per_row);
+                for (int64_t it = first; it < p.items; it += step) {
+                    ok = ok && r == it / p.per_row && q == it % p.per_row && r < n;
+                    const int c0 = p.vec ? 4 * q : q;
+                    for (int e = 0; e < (p.vec ? 4 : 1); e++) {
+                        ok = ok && c0 + e < dp;
+                        if (ok) written[(size_t)(r * dp + c0 + e)]++;
+                    }
+                    r += step_r;
+                    q += step_q;
+                    if (q >= p.per_row) {
+                        q -= p.per_row;
+                        r++;
+                    }
+                }
+            }
+            for (uint8_t v : written) ok = ok && v == 1;
+        }
+        if (!ok) printf("broken\n");
+        else printf("%d %d %lld %d\n", (int)p.vec, p.per_row, (long long)p.items, p.grid);
+    }
+    return 0;
+}
+
+// `plan_check mixargs`: lines "d nlayers layers_set flat_d flat_is_view sweep g k column nlevels" -> "ok", or the refusal's message
+static int run_mixargs()
+{
+    int d, nlayers, flat_d, is_view, sweep;
+    unsigned set;
+    long long g, k, column, nlevels;
+    while (scanf("%d %d %u %d %d %d %lld %lld %lld %lld", &d, &nlayers, &set, &flat_d, &is_view, &sweep, &g, &k, &column, &nlevels) == 10) {
+        const char *why = mix_args_illegal(d, nlayers, set, flat_d, is_view != 0, sweep != 0, g, k, column, nlevels);
+        printf("%s\n", why ? why : "ok");
+    }
+    return 0;
+}
+
 // `plan_check s16`: lines "nb nq k flags" -> the prefilter's eligibility and k' for the fp16 and the 12-bit row copies
 static int run_s16()
 {
@@ -587,7 +657,9 @@ int main(int argc, char **argv)
     if (argc == 2 && !strcmp(argv[1], "pool")) return run_pool();
     if (argc == 2 && !strcmp(argv[1], "poolchunks")) return run_poolchunks();
     if (argc == 2 && !strcmp(argv[1], "kde")) return run_kde();
+    if (argc == 2 && !strcmp(argv[1], "mix")) return run_mix();
+    if (argc == 2 && !strcmp(argv[1], "mixargs")) return run_mixargs();
     if (argc == 2 && !strcmp(argv[1], "sweep")) return run_sweep();
-    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank|pool|poolchunks|kde < lines | plan_check sweep\n");
+    fprintf(stderr, "usage: plan_check cases|sym|range|s16|rank|pool|poolchunks|kde|mix|mixargs < lines | plan_check sweep\n");
     return 2;
 }
