@@ -120,8 +120,9 @@ static int bucket_agg_mode()
     return e && e[0] == '1' && e[1] == '\0' ? 1 : 0;
 }
 
-// upload, kernels, download of this thread's last successful knn_eval_bucket_counts [0] and knn_eval_hit_curve [1]
-static thread_local float g_buckets_ms[2][3] = {{0, 0, 0}, {0, 0, 0}};
+// the phases of this thread's last successful knn_eval_bucket_counts [0] and knn_eval_hit_curve [1]
+enum { BUCKETS_UP, BUCKETS_KERNELS, BUCKETS_DOWN, BUCKETS_PHASES };
+static thread_local float g_buckets_ms[2][BUCKETS_PHASES] = {{0, 0, 0}, {0, 0, 0}};
 
 extern "C" int knn_eval_bucket_counts(const void *scores, int32_t key_type, const uint8_t *is_correct, int64_t nq, int64_t k, int64_t limit,
                                       const double *lo, const double *hi, int32_t nb, int64_t *count_out, int64_t *correct_out)
@@ -146,7 +147,7 @@ extern "C" int knn_eval_bucket_counts(const void *scores, int32_t key_type, cons
     const int agg = bucket_agg_mode();
     HostCall call;
     EvalBufs &bufs = call.bufs;
-    EventList ev_k, ev_down; // (call.ev: the uploads')
+    PhaseClock &clock = call.clock;
     std::vector<int64_t> cnt(4 * n1);
     EvalCols tab(bufs, 1), w(bufs, slab);
     const double *d_lo = tab.in(lo, (size_t)nb * 8);
@@ -155,25 +156,24 @@ extern "C" int knn_eval_bucket_counts(const void *scores, int32_t key_type, cons
     const uint8_t *d_ic = w.in(is_correct, (size_t)k);
     const char *d_sc = w.in((const char *)scores, (size_t)k * esz);
     EVAL_TRY(w.ready());
-    EVAL_TRY(call.ev.mark(call.s));
+    EVAL_TRY(clock.open(BUCKETS_UP, call.s));
     EVAL_TRY(tab.upload(0, 1));
     HIP_TRY(hipMemset(d_cnt, 0, cnt.size() * 8));
-    EVAL_TRY(call.ev.mark(call.s));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        EVAL_TRY(call.ev.mark(call.s));
+        EVAL_TRY(clock.next(BUCKETS_UP, call.s));
         EVAL_TRY(w.upload(r0, m));
-        EVAL_TRY(call.ev.mark(call.s));
         const BucketParams p = {d_sc, d_ic, d_lo, d_hi, m, (int)k, (int)limit, nb, agg, d_cnt};
         const unsigned blocks = (unsigned)std::min<int64_t>((m + 3) / 4, 1024);
-        EVAL_TRY(ev_k.mark(call.s));
+        EVAL_TRY(clock.next(BUCKETS_KERNELS, call.s));
         EVAL_TRY(esz == 8 ? bucket_hist_launch<double>(p, blocks, lds) : bucket_hist_launch<float>(p, blocks, lds));
-        EVAL_TRY(ev_k.mark(call.s));
     }
-    EVAL_TRY(ev_down.mark(call.s));
+    EVAL_TRY(clock.next(BUCKETS_DOWN, call.s));
     EVAL_TRY(tab.download(0, 1));
-    EVAL_TRY(ev_down.mark(call.s));
-    EVAL_TRY(call.finish("bucket_counts", 0, nullptr, 0));
+    EVAL_TRY(clock.close(call.s));
+    EVAL_TRY(call.finish("bucket_counts", 0));
+    float ms[BUCKETS_PHASES];
+    EVAL_TRY(clock.read(ms, BUCKETS_PHASES));
     // count[b] = #{cells with h <= b} - #{cells with a <= b}, over the cells with a > h
     int64_t sel = 0, cor = 0;
     for (size_t b = 0; b < (size_t)nb; b++) {
@@ -182,9 +182,7 @@ extern "C" int knn_eval_bucket_counts(const void *scores, int32_t key_type, cons
         count_out[b] = sel;
         correct_out[b] = cor;
     }
-    EVAL_TRY(sum_pairs(call.ev, &g_buckets_ms[0][0]));
-    EVAL_TRY(sum_pairs(ev_k, &g_buckets_ms[0][1]));
-    EVAL_TRY(sum_pairs(ev_down, &g_buckets_ms[0][2]));
+    memcpy(g_buckets_ms[0], ms, sizeof ms);
     return 0;
 }
 
@@ -299,7 +297,7 @@ extern "C" int knn_eval_hit_curve(const uint8_t *is_correct, int64_t nq, int64_t
     const int lds_cols = (int)std::min<int64_t>(limit, HIT_LDS_COLS);
     HostCall call;
     EvalBufs &bufs = call.bufs;
-    EventList ev_k, ev_down; // (call.ev: the uploads')
+    PhaseClock &clock = call.clock;
     std::vector<double> sums((size_t)limit);
     std::vector<int64_t> cols(column_correct_out ? (size_t)limit : 0);
     EvalCols tab(bufs, 1), w(bufs, slab);
@@ -316,40 +314,37 @@ extern "C" int knn_eval_hit_curve(const uint8_t *is_correct, int64_t nq, int64_t
     if (d_cols) HIP_TRY(hipMemset(d_cols, 0, (size_t)limit * 8));
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        EVAL_TRY(call.ev.mark(call.s));
+        EVAL_TRY(clock.next(BUCKETS_UP, call.s));
         EVAL_TRY(w.upload(r0, m));
-        EVAL_TRY(call.ev.mark(call.s));
         const HitParams p = {d_ic, d_tot, m, (int)k, (int)limit, lds_cols, d_terms, d_rows, d_cols};
-        EVAL_TRY(ev_k.mark(call.s));
+        EVAL_TRY(clock.next(BUCKETS_KERNELS, call.s));
         hipLaunchKernelGGL(hit_terms_kernel, dim3((unsigned)std::min<int64_t>((m + 3) / 4, 1024)), dim3(256), d_cols ? (size_t)lds_cols * 4 : 0, 0, p);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(hit_fold_kernel, dim3((unsigned)((limit + HIT_FOLD_COLS - 1) / HIT_FOLD_COLS)), dim3(256),
                            2 * HIT_FOLD_ROWS * HIT_FOLD_COLS * 8, 0, d_terms, m, limit, d_sums);
         HIP_TRY(hipGetLastError());
-        EVAL_TRY(ev_k.mark(call.s));
-        EVAL_TRY(ev_down.mark(call.s));
+        EVAL_TRY(clock.next(BUCKETS_DOWN, call.s));
         EVAL_TRY(w.download(r0, m));
-        EVAL_TRY(ev_down.mark(call.s));
     }
-    EVAL_TRY(ev_down.mark(call.s));
+    EVAL_TRY(clock.next(BUCKETS_DOWN, call.s));
     EVAL_TRY(tab.download(0, 1));
-    EVAL_TRY(ev_down.mark(call.s));
-    EVAL_TRY(call.finish("hit_curve", 0, nullptr, 0));
+    EVAL_TRY(clock.close(call.s));
+    EVAL_TRY(call.finish("hit_curve", 0));
+    float ms[BUCKETS_PHASES];
+    EVAL_TRY(clock.read(ms, BUCKETS_PHASES));
     int64_t run = 0;
     for (int64_t j = 0; j < limit; j++) {
         mean_out[j] = sums[(size_t)j] / (double)nq;
         if (column_correct_out) column_correct_out[j] = run += cols[(size_t)j]; // the column sums of C: the prefix sum of the counts
     }
-    EVAL_TRY(sum_pairs(call.ev, &g_buckets_ms[1][0]));
-    EVAL_TRY(sum_pairs(ev_k, &g_buckets_ms[1][1]));
-    EVAL_TRY(sum_pairs(ev_down, &g_buckets_ms[1][2]));
+    memcpy(g_buckets_ms[1], ms, sizeof ms);
     return 0;
 }
 
 extern "C" int knn_eval_buckets_last_ms(float *counts_ms, float *curve_ms)
 {
     if (!counts_ms || !curve_ms) return set_err(KNN_ERR_INVALID, "buckets_last_ms: null pointer");
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < BUCKETS_PHASES; i++) {
         counts_ms[i] = g_buckets_ms[0][i];
         curve_ms[i] = g_buckets_ms[1][i];
     }

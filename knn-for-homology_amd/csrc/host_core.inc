@@ -1,5 +1,5 @@
 // host_core.inc -- what the whole host side stands on (included by knn355_lib.hip right behind knn355.hip): the error
-// channel, the owners of what one call holds (DESIGN 4.10), the device and stream pools, DevBuf, knn_index_s with its
+// channel, the owners of what one call holds and its phase clock (DESIGN 4.10), the device and stream pools, DevBuf, knn_index_s with its
 // scratch helpers, knn_init, the normalize / norm / pad helpers with knn_normalize_l2*, the copy pipes and HostCall.
 // ===========================================================================
 // host side
@@ -47,7 +47,8 @@ struct EvalBufs {
         if (rc_) return rc_;                                                            \
     } while (0)
 
-// HIP events of one call, in the order they were recorded
+// HIP events of one call that are not phase timing (ordering events, pairs recorded again and again), in the order they
+// were recorded
 struct EventList {
     std::vector<hipEvent_t> ev;
     ~EventList()
@@ -63,17 +64,69 @@ struct EventList {
         return 0;
     }
 };
-// after the streams have drained: the times between the events of every pair (0, 1), (2, 3), ... summed into *ms
-static int sum_pairs(const EventList &ev, float *ms)
-{
-    *ms = 0.0f;
-    for (size_t i = 0; i + 1 < ev.ev.size(); i += 2) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, ev.ev[i], ev.ev[i + 1]));
-        *ms += t;
+
+// The HIP-event times of one call, by phase: every interval of enqueued work belongs to one phase (an enum next to the
+// entry's thread_local result), and the time of a phase is the sum over its intervals.  One interval is open at a time.  The
+// caller reads into a local array once its streams have drained and copies that to where the getters look only when the
+// whole call has succeeded: a failed call leaves the previous figures as they were.
+struct PhaseClock {
+    static constexpr int NONE = -1;
+    struct Mark {
+        hipEvent_t e;
+        int phase; // of the interval this event starts (it ends at the next event), or NONE
+    };
+    std::vector<Mark> marks; // in the order they were recorded
+    PhaseClock() = default;
+    PhaseClock(const PhaseClock &) = delete;
+    PhaseClock &operator=(const PhaseClock &) = delete;
+    ~PhaseClock()
+    {
+        for (const Mark &m : marks) (void)hipEventDestroy(m.e);
     }
-    return 0;
-}
+    hipStream_t stream = nullptr; // of the open interval
+    bool is_open() const { return !marks.empty() && marks.back().phase != NONE; }
+    // starts an interval of phase p; none may be open
+    int open(int p, hipStream_t s)
+    {
+        if (is_open()) return set_err(KNN_ERR_INVALID, "PhaseClock: open() while an interval is open");
+        return next(p, s);
+    }
+    // ends the open interval
+    int close(hipStream_t s)
+    {
+        if (!is_open()) return set_err(KNN_ERR_INVALID, "PhaseClock: close() without an open interval");
+        return next(NONE, s);
+    }
+    // one event that ends the open interval, if there is one, and starts one of phase p (consecutive phases on one stream:
+    // an interval ends on the stream it began on)
+    int next(int p, hipStream_t s)
+    {
+        if (is_open() && s != stream) return set_err(KNN_ERR_INVALID, "PhaseClock: an interval ends on another stream than it began on");
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, 0));
+        marks.push_back({e, NONE}); // (an event that failed to record starts nothing)
+        HIP_TRY(hipEventRecord(e, s));
+        marks.back().phase = p;
+        stream = s;
+        return 0;
+    }
+    // after the streams have drained: ms[p] = the summed time of phase p's intervals, exactly 0.0f where it has none, p < n.
+    // ms is written only when every query has succeeded.
+    int read(float *ms, int n) const
+    {
+        if (is_open()) return set_err(KNN_ERR_INVALID, "PhaseClock: read() while an interval is open");
+        std::vector<float> sum((size_t)n, 0.0f);
+        for (size_t i = 0; i + 1 < marks.size(); i++) {
+            if (marks[i].phase == NONE) continue;
+            if (marks[i].phase < 0 || marks[i].phase >= n) return set_err(KNN_ERR_INVALID, "PhaseClock: a phase outside the array read()");
+            float t = 0;
+            HIP_TRY(hipEventElapsedTime(&t, marks[i].e, marks[i + 1].e));
+            sum[(size_t)marks[i].phase] += t;
+        }
+        std::copy(sum.begin(), sum.end(), ms);
+        return 0;
+    }
+};
 
 // Device scratch buffers are recycled through a small per-device pool: the reference's scripts
 // build a fresh index per embedding file (cath/search.py:20-24), and hipMalloc/hipFree of the
@@ -537,7 +590,7 @@ struct HostCall {
     PipeLease pipes;
     StreamLease own;
     EvalBufs bufs;
-    EventList ev;
+    PhaseClock clock;
     hipStream_t s; // where the call's kernels run: its own stream, else the leased h2d stream, else the caller's / the null stream
     // on a stream the caller names (null: the null stream)
     explicit HostCall(hipStream_t caller = nullptr) : own(0, false), s(caller) {}
@@ -551,16 +604,15 @@ struct HostCall {
         return 0;
     }
     // Behind the enqueueing, whatever it returned (rc): waits for the h2d stream and for s -- always, copies already queued
-    // read and write the caller's arrays -- then reports rc, else the first HIP error as "who: ...", else fills ms[i] with
-    // the time between ev[i] and ev[i + 1], i < n_ms.
-    int finish(const char *who, int rc, float *ms, int n_ms)
+    // read and write the caller's arrays -- then reports rc, else the first HIP error as "who: ...".  The clock is ready to
+    // be read behind a 0.
+    int finish(const char *who, int rc)
     {
         hipError_t e = pipes.cp && pipes.cp->h2d != s ? hipStreamSynchronize(pipes.cp->h2d) : hipSuccess;
         const hipError_t es = hipStreamSynchronize(s);
         if (rc) return rc;
         if (e == hipSuccess) e = es;
         if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-        for (int i = 0; i < n_ms; i++) HIP_TRY(hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]));
         return 0;
     }
 };

@@ -200,8 +200,10 @@ __global__ __launch_bounds__(256) void kde_reduce_kernel(const double *__restric
 
 // ---- host -------------------------------------------------------------------------------
 // measurement (tools/bench_kde.py): HIP-event milliseconds of this thread's last successful calls
-static thread_local float g_kde_stats_ms[2] = {0, 0};   // upload, kernels
-static thread_local float g_kde_eval_ms[3] = {0, 0, 0}; // uploads, evaluation kernel, reduce
+enum { KDE_STATS_UP, KDE_STATS_KERNELS, KDE_STATS_PHASES };
+static thread_local float g_kde_stats_ms[KDE_STATS_PHASES] = {0, 0};
+enum { KDE_EVAL_UP, KDE_EVAL_KERNEL, KDE_EVAL_REDUCE, KDE_EVAL_PHASES };
+static thread_local float g_kde_eval_ms[KDE_EVAL_PHASES] = {0, 0, 0};
 
 template <typename T>
 static bool kde_all_finite(const T *x, int64_t n, int64_t ncols, int64_t stride)
@@ -235,15 +237,15 @@ static size_t kde_span_bytes(int dtype, int64_t n, int ncols, int64_t row_stride
 }
 
 static int kde_stats_enqueue(const void *x, int dtype, int64_t n, int ncols, int64_t stride, const KdePlan &pl, double *stats_host, EvalBufs &bufs,
-                             hipStream_t s, EventList &ev)
+                             hipStream_t s, PhaseClock &clock)
 {
     const size_t gc = (size_t)pl.groups * ncols;
     EVAL_ALLOC(d_x, void *, kde_span_bytes(dtype, n, ncols, stride));
     EVAL_ALLOC(d_g, double *, 3 * gc * 8); // group sums, minima, maxima
     EVAL_ALLOC(d_stats, double *, (size_t)4 * ncols * 8);
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.open(KDE_STATS_UP, s));
     HIP_TRY(hipMemcpyAsync(d_x, x, kde_span_bytes(dtype, n, ncols, stride), hipMemcpyHostToDevice, s));
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.next(KDE_STATS_KERNELS, s));
     const dim3 gg((unsigned)((gc + 255) / 256)), gr((unsigned)((ncols + 255) / 256)), b(256);
     const double *d_mean = d_stats + (size_t)2 * ncols;
 #define KDE_STATS_PASS(PASS)                                                                                                                             \
@@ -259,7 +261,7 @@ static int kde_stats_enqueue(const void *x, int dtype, int64_t n, int ncols, int
     KDE_STATS_PASS(0);
     KDE_STATS_PASS(1);
 #undef KDE_STATS_PASS
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.close(s));
     HIP_TRY(hipMemcpyAsync(stats_host, d_stats, (size_t)4 * ncols * 8, hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -277,19 +279,22 @@ extern "C" int knn_kde_stats(const void *x, int32_t dtype, int64_t n, int32_t nc
     // the same stream (the null stream otherwise)
     HostCall call;
     if ((rc = call.lease(g_device, true))) return rc;
-    rc = kde_stats_enqueue(x, dtype, n, ncols, row_stride, pl, stats.data(), call.bufs, call.s, call.ev);
-    if ((rc = call.finish("kde_stats", rc, g_kde_stats_ms, 2))) return rc;
+    rc = kde_stats_enqueue(x, dtype, n, ncols, row_stride, pl, stats.data(), call.bufs, call.s, call.clock);
+    if ((rc = call.finish("kde_stats", rc))) return rc;
+    float ms[KDE_STATS_PHASES];
+    EVAL_TRY(call.clock.read(ms, KDE_STATS_PHASES));
     for (int c = 0; c < ncols; c++) {
         min_out[c] = stats[c];
         max_out[c] = stats[(size_t)ncols + c];
         mean_out[c] = stats[(size_t)2 * ncols + c];
         var_out[c] = stats[(size_t)3 * ncols + c];
     }
+    memcpy(g_kde_stats_ms, ms, sizeof ms);
     return 0;
 }
 
 static int kde_eval_enqueue(const void *x, int dtype, int64_t n, int ncols, int64_t stride, const double *grid, int64_t m, const double *inv_h,
-                            const double *norm, const KdePlan &pl, double *out, EvalBufs &bufs, hipStream_t s, EventList &ev)
+                            const double *norm, const KdePlan &pl, double *out, EvalBufs &bufs, hipStream_t s, PhaseClock &clock)
 {
     const size_t cm = (size_t)ncols * m;
     EVAL_ALLOC(d_x, void *, kde_span_bytes(dtype, n, ncols, stride));
@@ -297,20 +302,20 @@ static int kde_eval_enqueue(const void *x, int dtype, int64_t n, int ncols, int6
     EVAL_ALLOC(d_scale, double *, (size_t)2 * ncols * 8); // 1 / h, norm
     EVAL_ALLOC(d_part, double *, (size_t)pl.part_bytes);
     EVAL_ALLOC(d_out, double *, cm * 8);
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.open(KDE_EVAL_UP, s));
     HIP_TRY(hipMemcpyAsync(d_x, x, kde_span_bytes(dtype, n, ncols, stride), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_grid, grid, cm * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_scale, inv_h, (size_t)ncols * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_scale + ncols, norm, (size_t)ncols * 8, hipMemcpyHostToDevice, s));
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.next(KDE_EVAL_KERNEL, s));
     const dim3 ge((unsigned)pl.tiles, (unsigned)pl.chunks, (unsigned)ncols);
     if (dtype) hipLaunchKernelGGL((kde_eval_kernel<double>), ge, dim3(KDE_LANES), 0, s, (const double *)d_x, n, stride, d_grid, m, d_scale, d_part);
     else hipLaunchKernelGGL((kde_eval_kernel<float>), ge, dim3(KDE_LANES), 0, s, (const float *)d_x, n, stride, d_grid, m, d_scale, d_part);
     HIP_TRY(hipGetLastError());
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.next(KDE_EVAL_REDUCE, s));
     hipLaunchKernelGGL(kde_reduce_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)ncols), dim3(256), 0, s, d_part, pl.chunks, m, d_scale + ncols, d_out);
     HIP_TRY(hipGetLastError());
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.close(s));
     HIP_TRY(hipMemcpyAsync(out, d_out, cm * 8, hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -329,14 +334,18 @@ extern "C" int knn_kde_eval(const void *x, int32_t dtype, int64_t n, int32_t nco
     if ((rc = ensure_device(g_device))) return rc;
     HostCall call;
     if ((rc = call.lease(g_device, true))) return rc;
-    rc = kde_eval_enqueue(x, dtype, n, ncols, row_stride, grid, m, inv_h, norm, pl, out, call.bufs, call.s, call.ev);
-    return call.finish("kde_eval", rc, g_kde_eval_ms, 3);
+    rc = kde_eval_enqueue(x, dtype, n, ncols, row_stride, grid, m, inv_h, norm, pl, out, call.bufs, call.s, call.clock);
+    if ((rc = call.finish("kde_eval", rc))) return rc;
+    float ms[KDE_EVAL_PHASES];
+    EVAL_TRY(call.clock.read(ms, KDE_EVAL_PHASES));
+    memcpy(g_kde_eval_ms, ms, sizeof ms);
+    return 0;
 }
 
 extern "C" int knn_kde_last_ms(float *stats_ms, float *eval_ms)
 {
     if (!stats_ms || !eval_ms) return set_err(KNN_ERR_INVALID, "kde_last_ms: null pointer");
-    for (int i = 0; i < 2; i++) stats_ms[i] = g_kde_stats_ms[i];
-    for (int i = 0; i < 3; i++) eval_ms[i] = g_kde_eval_ms[i];
+    for (int i = 0; i < KDE_STATS_PHASES; i++) stats_ms[i] = g_kde_stats_ms[i];
+    for (int i = 0; i < KDE_EVAL_PHASES; i++) eval_ms[i] = g_kde_eval_ms[i];
     return 0;
 }

@@ -22,13 +22,15 @@
 //   hamming_scan_kernel  one thread per database row: XOR + popcount against 32 query codes held
 //                        in LDS, same candidate lists / thresholds / wave_select as the flat scan
 
+// the phases of knn_lsh_train: the slabs' uploads, their projections, the median selection
+enum { LSH_TRAIN_UP, LSH_TRAIN_PROJECT, LSH_TRAIN_SELECT, LSH_TRAIN_PHASES };
 struct knn_lsh_s {
     int d = 0, dp = 0, nbits = 0, W = 0; // W: 64-bit words per code (nbits padded up to 128 * 2^i)
     int device = 0;
     int64_t ntotal = 0, cap_rows = 0;
     float *rot = nullptr;      // [W*64][dp] rotation rows (zero rows pad the tail)
     float *thr = nullptr;      // [W*64] per-bit thresholds (zeros pad the tail: padding bits stay 1), or null: none
-    float train_ms[3] = {0, 0, 0}; // upload, projection, selection of the last knn_lsh_train (HIP events)
+    float train_ms[LSH_TRAIN_PHASES] = {0, 0, 0}; // of the last successful knn_lsh_train (HIP events)
     uint64_t *codes = nullptr; // [cap_rows][W]
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -433,12 +435,13 @@ extern "C" int64_t knn_lsh_ntotal(knn_lsh_s *h) { return h ? h->ntotal : -1; }
 extern "C" int32_t knn_lsh_code_words(knn_lsh_s *h) { return h ? h->W : -1; }
 
 // encodes n host rows into dst_codes (device, [n][W]) in slabs -- or, with proj given (the training), stores their
-// projections into proj[W*64][ldp] instead and adds the slabs' upload and kernel times (HIP events) to ms[0], ms[1].
+// projections into proj[W*64][ldp] instead.  With a clock (the training's; null: no event is recorded) every slab's upload
+// is an LSH_TRAIN_UP interval and its kernel an LSH_TRAIN_PROJECT one.
 // A slab is a whole number of 128-row tiles, so that every slab's rows start on a tile of proj.
 // (xp_out: where the LAST slab's rows, zero padded to dp, stay on the device until the handle's next call)
 static int64_t lsh_slab_rows(const knn_lsh_s *h) { return std::max<int64_t>(128, (int64_t)(256ull << 20) / ((int64_t)h->dp * 4) / 128 * 128); }
 static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, uint64_t *dst_codes, float *proj = nullptr, int64_t ldp = 0,
-                                float *ms = nullptr, const float **xp_out = nullptr)
+                                PhaseClock *clock = nullptr, const float **xp_out = nullptr)
 {
     const int64_t slab = lsh_slab_rows(h);
     if (h->ws_x.ensure((size_t)std::min(n, slab) * h->d * 4) || h->ws_xp.ensure((size_t)std::min(n, slab) * h->dp * 4))
@@ -446,10 +449,9 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
     hipStream_t s = h->stream;
     for (int64_t i0 = 0; i0 < n; i0 += slab) {
         const int64_t m = std::min(slab, n - i0);
-        EventList ev; // with ms: in front of the slab's upload, behind it, behind its kernel
-        if (ms) EVAL_TRY(ev.mark(s));
+        if (clock) EVAL_TRY(clock->open(LSH_TRAIN_UP, s));
         HIP_TRY(hipMemcpyAsync(h->ws_x.p, x_host + i0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
-        if (ms) EVAL_TRY(ev.mark(s));
+        if (clock) EVAL_TRY(clock->next(LSH_TRAIN_PROJECT, s));
         const float *xp = (const float *)h->ws_x.p;
         if (h->dp != h->d) {
             int rc = pad_rows_dev((const float *)h->ws_x.p, m, h->d, (float *)h->ws_xp.p, h->dp, s);
@@ -473,15 +475,8 @@ static int lsh_encode_host_rows(knn_lsh_s *h, const float *x_host, int64_t n, ui
             hipLaunchKernelGGL(lsh_encode_kernel, dim3(grid), dim3(256), lds, s, p);
         }
         HIP_TRY(hipGetLastError());
-        if (ms) EVAL_TRY(ev.mark(s));
+        if (clock) EVAL_TRY(clock->close(s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (ms) {
-            float up = 0, pr = 0;
-            HIP_TRY(hipEventElapsedTime(&up, ev.ev[0], ev.ev[1]));
-            HIP_TRY(hipEventElapsedTime(&pr, ev.ev[1], ev.ev[2]));
-            ms[0] += up;
-            ms[1] += pr;
-        }
     }
     return 0;
 }
@@ -524,27 +519,27 @@ extern "C" int knn_lsh_train(knn_lsh_s *h, const float *x_host, int64_t n)
                                                 " bytes, more than half of the " + std::to_string(free_b) +
                                                 " bytes free on the device: train on a sample of the rows");
     EvalBufs bufs;
-    EventList ev; // around the median kernel
+    PhaseClock clock;
     float *d_P = (float *)bufs.get(need), *d_thr = (float *)bufs.get((size_t)h->nbits * 4);
     int32_t *d_status = (int32_t *)bufs.get((size_t)h->nbits * 4);
     if (bufs.oom) return set_err(KNN_ERR_HIP, "lsh_train: out of device memory");
-    float ms[3] = {0, 0, 0};
     // the projections are taken without thresholds whatever the handle holds: lsh_project_kernel does not read them
-    int rc = lsh_encode_host_rows(h, x_host, n, nullptr, d_P, ldp, ms);
+    int rc = lsh_encode_host_rows(h, x_host, n, nullptr, d_P, ldp, &clock);
     if (rc) return rc;
     hipStream_t s = h->stream;
     LshMedianParams mp;
     mp.proj = d_P; mp.n = n; mp.ldp = ldp; mp.thr = d_thr; mp.status = d_status;
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.open(LSH_TRAIN_SELECT, s));
     hipLaunchKernelGGL(lsh_median_kernel, dim3(h->nbits), dim3(256), 0, s, mp); // (the padding columns are skipped)
     HIP_TRY(hipGetLastError());
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.close(s));
     std::vector<float> thr((size_t)h->nbits);
     std::vector<int32_t> status((size_t)h->nbits);
     HIP_TRY(hipMemcpyAsync(thr.data(), d_thr, thr.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipEventElapsedTime(&ms[2], ev.ev[0], ev.ev[1]));
+    float ms[LSH_TRAIN_PHASES];
+    EVAL_TRY(clock.read(ms, LSH_TRAIN_PHASES));
     for (int b = 0; b < h->nbits; b++)
         if (status[b])
             return set_err(KNN_ERR_INVALID, std::string("lsh_train: ") + (status[b] == 1 ? "a projection onto bit " : "the median (+inf and -inf around the middle) of bit ") +
@@ -676,7 +671,7 @@ static int launch_hamming(const HammingParams &p, int grid, size_t lds, hipStrea
 // flat given: the batch's kb ids stay on the device, refine_batch scores them against flat's rows with the batch's fp32
 // queries -- still on the device from the encode step -- and its best k are the result.  Either way only [m][k] goes down.
 static int lsh_search_batches(knn_lsh_s *h, knn_index_s *flat, const float *q_host, int64_t nq, int64_t kb, int64_t k, float *D_host,
-                              int64_t *I_host, EventList &rev)
+                              int64_t *I_host, PhaseClock &refine_clock)
 {
     hipStream_t s = h->stream;
     const int QT = 32, DT = 256;
@@ -744,7 +739,7 @@ static int lsh_search_batches(knn_lsh_s *h, knn_index_s *flat, const float *q_ho
         rc = launch_select(sp, s);
         if (rc) return rc;
         if (flat) { // exact scores of the kb hits, the best k of them into this batch's result buffers
-            rc = refine_batch(flat, xq_dev, (const int64_t *)h->ws_cI.p, m, (int)kb, (int)k, (float *)dD[slot]->p, (int64_t *)dI[slot]->p, s, rev);
+            rc = refine_batch(flat, xq_dev, (const int64_t *)h->ws_cI.p, m, (int)kb, (int)k, (float *)dD[slot]->p, (int64_t *)dI[slot]->p, s, refine_clock);
             if (rc) return rc;
         }
         return 0;
@@ -776,7 +771,7 @@ extern "C" int knn_lsh_search(knn_lsh_s *h, const float *q_host, int64_t nq, int
         fill_empty_host(D_host, I_host, nq * k, KNN_METRIC_L2); // (Hamming distances: smaller is better)
         return 0;
     }
-    EventList none;
+    PhaseClock none; // (nothing is refined: it stays empty)
     return lsh_search_batches(h, nullptr, q_host, nq, k, k, D_host, I_host, none);
 }
 
@@ -803,10 +798,10 @@ extern "C" int knn_lsh_search_refine(knn_lsh_s *h, knn_handle flat, const float 
         return 0;
     }
     HIP_TRY(hipStreamSynchronize(flat->stream)); // (the rows are read on the LSH handle's stream: whatever the flat handle's own stream still does to them first)
-    EventList rev;
-    rc = lsh_search_batches(h, flat, q_host, nq, kb, k, D_host, I_host, rev);
+    PhaseClock clock;
+    rc = lsh_search_batches(h, flat, q_host, nq, kb, k, D_host, I_host, clock);
     if (rc) return rc;
-    return refine_sum_ms(rev, flat->refine_ms);
+    return refine_commit_ms(clock, flat);
 }
 
 // IndexLSH::reset: the handle keeps its rotation, thresholds and the codes' allocation

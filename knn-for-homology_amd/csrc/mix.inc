@@ -115,7 +115,8 @@ struct knn_mix_s {
 };
 
 // measurement (tools/bench_layer_mix.py): HIP-event milliseconds of this thread's last successful call, summed over its mixes
-static thread_local float g_mix_ms[3] = {0, 0, 0}; // knn_mix_into's launches, self-search, scoring
+enum { MIX_MIX, MIX_SEARCH, MIX_SCORE, MIX_PHASES }; // knn_mix_into's launches, self-search, scoring
+static thread_local float g_mix_ms[MIX_PHASES] = {0, 0, 0};
 
 extern "C" int knn_mix_create(int32_t d, int32_t nlayers, knn_mix_handle *out)
 {
@@ -225,8 +226,9 @@ static int mix_launch(const MixPlan &pl, int nlayers, const MixArgs &a, hipStrea
 }
 
 // knn_mix_into behind its checks; the caller holds h->mu, this takes flat's.  Everything runs on flat's stream and is waited
-// for.  ev (may be null): marked in front of and behind the launches.
-static int mix_into_impl(knn_mix_s *h, const float *weights, knn_index_s *flat, bool normalize, EventList *ev)
+// for.  The launches are a MIX_MIX interval of the clock; the event behind them starts one of phase `then` (PhaseClock::NONE:
+// it only ends theirs).
+static int mix_into_impl(knn_mix_s *h, const float *weights, knn_index_s *flat, bool normalize, PhaseClock &clock, int then)
 {
     std::lock_guard<std::mutex> lk(flat->mu);
     HIP_TRY(hipSetDevice(flat->device));
@@ -253,14 +255,14 @@ static int mix_into_impl(knn_mix_s *h, const float *weights, knn_index_s *flat, 
     a.per_row = pl.per_row;
     a.d = h->d;
     a.dp = flat->dp;
-    if (ev) EVAL_TRY(ev->mark(s));
+    EVAL_TRY(clock.open(MIX_MIX, s));
     EVAL_TRY(mix_launch(pl, h->nlayers, a, s));
     if (normalize) EVAL_TRY(normalize_dev_impl(flat->xb, n, flat->d, flat->dp, s));
     // what add_dev_impl does behind its copy
     EVAL_TRY(norms_dev_impl(flat->xb, n, flat->d, flat->dp, flat->yn, s));
     EVAL_TRY(approx16_sync_rows(flat, 0, n, s));
     EVAL_TRY(scan16_sync_rows(flat, 0, n, s));
-    if (ev) EVAL_TRY(ev->mark(s));
+    EVAL_TRY(clock.next(then, s));
     flat->ntotal = n;
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
@@ -272,12 +274,11 @@ extern "C" int knn_mix_into(knn_mix_handle h, const float *weights, knn_handle f
     std::lock_guard<std::mutex> lk(h->mu);
     int rc = mix_check_args(h, "mix_into", weights, flat, false, 0, 0, 0, 0);
     if (rc) return rc;
-    EventList ev;
-    if ((rc = mix_into_impl(h, weights, flat, normalize != 0, &ev))) return rc;
-    float ms = 0.0f;
-    EVAL_TRY(sum_pairs(ev, &ms));
-    g_mix_ms[0] = ms;
-    g_mix_ms[1] = g_mix_ms[2] = 0.0f;
+    PhaseClock clock;
+    if ((rc = mix_into_impl(h, weights, flat, normalize != 0, clock, PhaseClock::NONE))) return rc;
+    float ms[MIX_PHASES]; // (no search, no scoring: both read 0)
+    EVAL_TRY(clock.read(ms, MIX_PHASES));
+    memcpy(g_mix_ms, ms, sizeof ms);
     return 0;
 }
 
@@ -305,19 +306,19 @@ extern "C" int knn_mix_sweep(knn_mix_handle h, const float *weights, int64_t G, 
         !(d_counts = scratch_device_wide<unsigned long long>(h->ws_counts, (size_t)G * nlevels, oom)))
         return KNN_ERR_HIP;
     std::vector<long long> counts((size_t)G * nlevels);
-    EventList ev; // per mix: in front of the mix, behind it, behind the search, behind the scoring
+    PhaseClock clock; // per mix: the mix, the search, the scoring, one behind the other
     const bool normalize = flat->metric == KNN_METRIC_INNER_PRODUCT;
     auto enqueue = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(d_map, mapping, (size_t)n * nlevels * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)G * nlevels * 8, s));
         for (int64_t g = 0; g < G; g++) {
-            EVAL_TRY(mix_into_impl(h, weights + g * h->nlayers, flat, normalize, &ev));
+            EVAL_TRY(mix_into_impl(h, weights + g * h->nlayers, flat, normalize, clock, MIX_SEARCH));
             EVAL_TRY(knn_flat_search_self_dev(flat, k, D_dev, I_dev));
-            EVAL_TRY(ev.mark(s));
+            EVAL_TRY(clock.next(MIX_SCORE, s));
             hipLaunchKernelGGL(mix_top1_kernel, dim3((unsigned)((n + MIX_BLOCK - 1) / MIX_BLOCK)), dim3(MIX_BLOCK), 0, s, I_dev, n, (int)k, (int)column, d_map,
                                (int)nlevels, d_counts + g * nlevels);
             HIP_TRY(hipGetLastError());
-            EVAL_TRY(ev.mark(s));
+            EVAL_TRY(clock.close(s));
             if (D_host) {
                 HIP_TRY(hipMemcpyAsync(D_host + (size_t)g * cells, D_dev, cells * 4, hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipMemcpyAsync(I_host + (size_t)g * cells, I_dev, cells * 8, hipMemcpyDeviceToHost, s));
@@ -330,15 +331,10 @@ extern "C" int knn_mix_sweep(knn_mix_handle h, const float *weights, int64_t G, 
     const hipError_t e = hipStreamSynchronize(s); // (always: copies already queued write the caller's arrays and this frame's vector)
     if (rc) return rc;
     if (e != hipSuccess) return set_err(KNN_ERR_HIP, std::string("mix_sweep: ") + hipGetErrorString(e));
-    float ms[3] = {0, 0, 0};
-    for (size_t i = 0; i + 3 < ev.ev.size(); i += 4)
-        for (int j = 0; j < 3; j++) {
-            float t = 0;
-            HIP_TRY(hipEventElapsedTime(&t, ev.ev[i + j], ev.ev[i + j + 1]));
-            ms[j] += t;
-        }
+    float ms[MIX_PHASES];
+    EVAL_TRY(clock.read(ms, MIX_PHASES));
     for (size_t i = 0; i < counts.size(); i++) counts_out[i] = (int64_t)counts[i];
-    for (int j = 0; j < 3; j++) g_mix_ms[j] = ms[j];
+    memcpy(g_mix_ms, ms, sizeof ms);
     return 0;
 }
 

@@ -141,8 +141,9 @@ __global__ __launch_bounds__(256) void overlap_kernel(OverlapParams p)
     }
 }
 
-// upload, kernel, download of this thread's last successful knn_eval_overlap
-static thread_local float g_overlap_ms[3] = {0, 0, 0};
+// the phases of this thread's last successful knn_eval_overlap
+enum { OVERLAP_UP, OVERLAP_KERNEL, OVERLAP_DOWN, OVERLAP_PHASES };
+static thread_local float g_overlap_ms[OVERLAP_PHASES] = {0, 0, 0};
 
 extern "C" int knn_eval_overlap(const int64_t *hits_a, const uint8_t *correct_a, int64_t ka, const int64_t *hits_b,
                                 const uint8_t *correct_b, int64_t kb, int64_t nq, int32_t *tp_out, int32_t *lead_out)
@@ -165,7 +166,7 @@ extern "C" int knn_eval_overlap(const int64_t *hits_a, const uint8_t *correct_a,
     HIP_TRY(hipFuncSetAttribute((const void *)overlap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HostCall call;
     EvalBufs &bufs = call.bufs;
-    EventList ev_k, ev_down; // (call.ev: the uploads')
+    PhaseClock &clock = call.clock;
     EvalCols w(bufs, slab);
     const OverlapParams p = {w.in(hits_a, (size_t)ka * 8),
                              w.in(hits_b, (size_t)kb * 8),
@@ -177,27 +178,25 @@ extern "C" int knn_eval_overlap(const int64_t *hits_a, const uint8_t *correct_a,
     EVAL_TRY(w.ready());
     for (int64_t r0 = 0; r0 < nq; r0 += slab) {
         const int64_t m = std::min(slab, nq - r0);
-        EVAL_TRY(call.ev.mark(call.s));
+        EVAL_TRY(clock.next(OVERLAP_UP, call.s));
         EVAL_TRY(w.upload(r0, m));
-        EVAL_TRY(call.ev.mark(call.s));
-        EVAL_TRY(ev_k.mark(call.s));
+        EVAL_TRY(clock.next(OVERLAP_KERNEL, call.s));
         hipLaunchKernelGGL(overlap_kernel, dim3((unsigned)m), dim3(256), lds, call.s, p);
         HIP_TRY(hipGetLastError());
-        EVAL_TRY(ev_k.mark(call.s));
-        EVAL_TRY(ev_down.mark(call.s));
+        EVAL_TRY(clock.next(OVERLAP_DOWN, call.s));
         EVAL_TRY(w.download(r0, m));
-        EVAL_TRY(ev_down.mark(call.s));
     }
-    EVAL_TRY(call.finish("overlap", 0, nullptr, 0));
-    EVAL_TRY(sum_pairs(call.ev, &g_overlap_ms[0]));
-    EVAL_TRY(sum_pairs(ev_k, &g_overlap_ms[1]));
-    EVAL_TRY(sum_pairs(ev_down, &g_overlap_ms[2]));
+    EVAL_TRY(clock.close(call.s));
+    EVAL_TRY(call.finish("overlap", 0));
+    float ms[OVERLAP_PHASES];
+    EVAL_TRY(clock.read(ms, OVERLAP_PHASES));
+    memcpy(g_overlap_ms, ms, sizeof ms);
     return 0;
 }
 
 extern "C" int knn_eval_overlap_last_ms(float *ms)
 {
     if (!ms) return set_err(KNN_ERR_INVALID, "overlap_last_ms: null pointer");
-    for (int i = 0; i < 3; i++) ms[i] = g_overlap_ms[i];
+    for (int i = 0; i < OVERLAP_PHASES; i++) ms[i] = g_overlap_ms[i];
     return 0;
 }

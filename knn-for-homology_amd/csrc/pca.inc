@@ -208,8 +208,10 @@ __global__ __launch_bounds__(256) void pca_project_kernel(const float *__restric
 
 // ---- host -------------------------------------------------------------------------------
 // measurement (tools/bench_pca.py): HIP-event milliseconds of this thread's last successful calls
-static thread_local float g_pca_moments_ms[4] = {0, 0, 0, 0}; // upload, column sums + mean, covariance kernel, reduce
-static thread_local float g_pca_project_ms = 0;                // the projection kernel, summed over the slabs
+enum { PCA_UP, PCA_MEAN, PCA_COV, PCA_REDUCE, PCA_MOMENT_PHASES }; // upload, column sums + mean, covariance kernel, reduce
+static thread_local float g_pca_moments_ms[PCA_MOMENT_PHASES] = {0, 0, 0, 0};
+enum { PCA_PROJECT }; // the one phase of knn_pca_project: its kernel, summed over the slabs
+static thread_local float g_pca_project_ms = 0;
 
 static int pca_check_shape(const char *who, int64_t n, int64_t n_min, int32_t d)
 {
@@ -219,7 +221,7 @@ static int pca_check_shape(const char *who, int64_t n, int64_t n_min, int32_t d)
 }
 
 // everything of knn_pca_moments that runs on stream s, enqueued; the caller waits for s whatever this returns
-static int pca_moments_enqueue(const float *x, int64_t n, int d, float *mean, double *cov, EvalBufs &bufs, hipStream_t s, EventList &ev)
+static int pca_moments_enqueue(const float *x, int64_t n, int d, float *mean, double *cov, EvalBufs &bufs, hipStream_t s, PhaseClock &clock)
 {
     const int64_t L = pca_group_rows(n);
     const int groups = (int)((n + L - 1) / L);
@@ -229,21 +231,21 @@ static int pca_moments_enqueue(const float *x, int64_t n, int d, float *mean, do
     EVAL_ALLOC(d_mean, float *, (size_t)d * 4);
     EVAL_ALLOC(d_part, float *, (size_t)groups * dd * 4);
     EVAL_ALLOC(d_cov, double *, dd * 8);
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.open(PCA_UP, s));
     HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)n * d * 4, hipMemcpyHostToDevice, s));
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.next(PCA_MEAN, s));
     const unsigned cblocks = (unsigned)((d + 255) / 256), tiles = (unsigned)((d + PCA_TC - 1) / PCA_TC);
     hipLaunchKernelGGL(pca_colsum_kernel, dim3(cblocks, (unsigned)groups), dim3(256), 0, s, d_x, n, d, L, d_gsum);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(pca_mean_kernel, dim3(cblocks), dim3(256), 0, s, d_gsum, groups, d, n, d_mean);
     HIP_TRY(hipGetLastError());
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.next(PCA_COV, s));
     hipLaunchKernelGGL(pca_cov_kernel, dim3(tiles, tiles, (unsigned)groups), dim3(256), 0, s, d_x, n, d, L, d_mean, d_part);
     HIP_TRY(hipGetLastError());
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.next(PCA_REDUCE, s));
     hipLaunchKernelGGL(pca_cov_reduce_kernel, dim3(cblocks, (unsigned)d), dim3(256), 0, s, d_part, groups, d, n, d_cov);
     HIP_TRY(hipGetLastError());
-    EVAL_TRY(ev.mark(s));
+    EVAL_TRY(clock.close(s));
     HIP_TRY(hipMemcpyAsync(mean, d_mean, (size_t)d * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(cov, d_cov, dd * 8, hipMemcpyDeviceToHost, s));
     return 0;
@@ -259,8 +261,12 @@ extern "C" int knn_pca_moments(const float *x, int64_t n, int32_t d, float *mean
     // the same stream (the null stream otherwise)
     HostCall call;
     if ((rc = call.lease(g_device, true))) return rc;
-    rc = pca_moments_enqueue(x, n, d, mean, cov, call.bufs, call.s, call.ev);
-    return call.finish("pca_moments", rc, g_pca_moments_ms, 4);
+    rc = pca_moments_enqueue(x, n, d, mean, cov, call.bufs, call.s, call.clock);
+    if ((rc = call.finish("pca_moments", rc))) return rc;
+    float ms[PCA_MOMENT_PHASES];
+    EVAL_TRY(call.clock.read(ms, PCA_MOMENT_PHASES));
+    memcpy(g_pca_moments_ms, ms, sizeof ms);
+    return 0;
 }
 
 extern "C" int knn_pca_project(const float *x, int64_t n, int32_t d, const float *mean, const float *components, int32_t nc, float *out)
@@ -281,17 +287,20 @@ extern "C" int knn_pca_project(const float *x, int64_t n, int32_t d, const float
     float *d_out = w.out(out, (size_t)nc * 4);
     EVAL_TRY(w.ready());
     EVAL_TRY(tab.upload(0, 1));
-    EventList ev;
+    PhaseClock clock;
     for (int64_t r0 = 0; r0 < n; r0 += slab) {
         const int64_t m = std::min(slab, n - r0);
         EVAL_TRY(w.upload(r0, m));
-        EVAL_TRY(ev.mark(nullptr));
+        EVAL_TRY(clock.open(PCA_PROJECT, nullptr));
         hipLaunchKernelGGL(pca_project_kernel, dim3((unsigned)((m + PJ_ROWS - 1) / PJ_ROWS)), dim3(256), 0, 0, d_x, m, (int)d, d_mean, d_comp, (int)nc, d_out);
         HIP_TRY(hipGetLastError());
-        EVAL_TRY(ev.mark(nullptr));
+        EVAL_TRY(clock.close(nullptr));
         EVAL_TRY(w.download(r0, m));
     }
-    return sum_pairs(ev, &g_pca_project_ms);
+    float ms;
+    EVAL_TRY(clock.read(&ms, 1));
+    g_pca_project_ms = ms;
+    return 0;
 }
 
 extern "C" int knn_pca_last_ms(float *moments_ms, float *project_ms)

@@ -143,7 +143,8 @@ __global__ __launch_bounds__(64 * POOL_MAX_WAVES) void pool_ranges_kernel(PoolAr
 
 // ---- host -------------------------------------------------------------------------------
 // measurement (tools/bench_pool.py): HIP-event milliseconds of this thread's last successful call
-static thread_local float g_pool_ms[3] = {0, 0, 0}; // uploads, kernels, download
+enum { POOL_UP, POOL_KERNELS, POOL_DOWN, POOL_PHASES };
+static thread_local float g_pool_ms[POOL_PHASES] = {0, 0, 0};
 
 static int pool_launch(const PoolPlan &pl, int dtype, bool normalize, const PoolArgs &a, hipStream_t s)
 {
@@ -215,28 +216,28 @@ extern "C" int knn_pool_ranges_dev(const void *x_dev, int32_t dtype, int64_t row
         HIP_TRY(hipMemsetAsync(d_status, 0xFF, 8, s));
         hipLaunchKernelGGL(pool_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, starts_dev, stops_dev, n, rows, d_status);
         HIP_TRY(hipGetLastError());
-        EVAL_TRY(call.ev.mark(s));
+        EVAL_TRY(call.clock.open(POOL_KERNELS, s));
         const PoolArgs a = {x_dev, rows, row_stride, (int)d, starts_dev, stops_dev, nullptr, out_dev};
         EVAL_TRY(pool_launch(pl, dtype, flags & KNN_POOL_NORMALIZE, a, s));
-        EVAL_TRY(call.ev.mark(s));
+        EVAL_TRY(call.clock.close(s));
         HIP_TRY(hipMemcpyAsync(&status, d_status, 8, hipMemcpyDeviceToHost, s));
         return 0;
     };
     // (finish() always waits: the copy already queued writes this frame's status word)
-    float kernel_ms = 0.0f; // (g_pool_ms is the last SUCCESSFUL call's)
-    if ((rc = call.finish("pool_ranges_dev", enqueue(), &kernel_ms, 1))) return rc;
+    if ((rc = call.finish("pool_ranges_dev", enqueue()))) return rc;
+    float ms[POOL_PHASES]; // (nothing is moved: the upload and the download read 0)
+    EVAL_TRY(call.clock.read(ms, POOL_PHASES));
     if (status != ~0ull)
         return set_err(KNN_ERR_INVALID, "pool_ranges_dev: range " + std::to_string(status) + " is not 0 <= start < stop <= rows with stop - start < 2^24");
-    g_pool_ms[0] = g_pool_ms[2] = 0.0f;
-    g_pool_ms[1] = kernel_ms;
+    memcpy(g_pool_ms, ms, sizeof ms);
     return 0;
 }
 
 // everything of knn_pool_ranges that is enqueued; the caller waits for both streams whatever this returns.
 // s: the kernels and the download; up: the uploads (the copy pipeline's host-to-device stream, or s itself)
 static int pool_host_enqueue(const char *x, int dtype, int d, const std::vector<int64_t> &order, const std::vector<PoolChunk> &chunks, const int64_t *starts,
-                             const int64_t *stops, int64_t n, int flags, float *out, EvalBufs &bufs, hipStream_t s, CopyPipes *cp, EventList &ev_up,
-                             EventList &ev_k, EventList &ev_down, std::vector<int64_t> &meta)
+                             const int64_t *stops, int64_t n, int flags, float *out, EvalBufs &bufs, hipStream_t s, CopyPipes *cp, PhaseClock &clock,
+                             std::vector<int64_t> &meta)
 {
     const size_t esz = dtype ? 2 : 4, row_bytes = (size_t)d * esz;
     int64_t max_rows = 0, max_count = 0;
@@ -272,10 +273,10 @@ static int pool_host_enqueue(const char *x, int dtype, int d, const std::vector<
         }
         // the slot's previous chunk has been pooled
         if (cp && ci >= 2) HIP_TRY(hipStreamWaitEvent(up, cp->ev_batch[slot], 0));
-        EVAL_TRY(ev_up.mark(up));
+        EVAL_TRY(clock.open(POOL_UP, up));
         HIP_TRY(hipMemcpyAsync(d_x[slot], x + (size_t)c.row0 * row_bytes, (size_t)(c.row1 - c.row0) * row_bytes, hipMemcpyHostToDevice, up));
         HIP_TRY(hipMemcpyAsync(d_meta[slot], h, 3 * m * 8, hipMemcpyHostToDevice, up));
-        EVAL_TRY(ev_up.mark(up));
+        EVAL_TRY(clock.close(up));
         if (cp) {
             HIP_TRY(hipEventRecord(cp->ev_query[slot], up));
             HIP_TRY(hipStreamWaitEvent(s, cp->ev_query[slot], 0));
@@ -283,14 +284,14 @@ static int pool_host_enqueue(const char *x, int dtype, int d, const std::vector<
         PoolPlan pl;
         if (!plan_pool(c.count, d, d, (uintptr_t)d_x[slot], (int)esz, flags & KNN_POOL_NORMALIZE, &pl)) return set_err(KNN_ERR_INVALID, "pool_ranges: no plan");
         const PoolArgs a = {d_x[slot], c.row1 - c.row0, (int64_t)d, d, d_meta[slot], d_meta[slot] + m, d_meta[slot] + 2 * m, d_out};
-        EVAL_TRY(ev_k.mark(s));
+        EVAL_TRY(clock.open(POOL_KERNELS, s));
         EVAL_TRY(pool_launch(pl, dtype, flags & KNN_POOL_NORMALIZE, a, s));
-        EVAL_TRY(ev_k.mark(s));
+        EVAL_TRY(clock.close(s));
         if (cp) HIP_TRY(hipEventRecord(cp->ev_batch[slot], s));
     }
-    EVAL_TRY(ev_down.mark(s));
+    EVAL_TRY(clock.open(POOL_DOWN, s));
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * d * 4, hipMemcpyDeviceToHost, s));
-    EVAL_TRY(ev_down.mark(s));
+    EVAL_TRY(clock.close(s));
     return 0;
 }
 
@@ -313,13 +314,12 @@ extern "C" int knn_pool_ranges(const void *x_host, int32_t dtype, int64_t rows, 
     HostCall call(g_device);
     if (!call.s) return set_err(KNN_ERR_HIP, "pool_ranges: no stream");
     if ((rc = call.lease(g_device, chunks.size() > 1))) return rc;
-    EventList ev_k, ev_down; // (call.ev: the uploads')
-    rc = pool_host_enqueue((const char *)x_host, dtype, d, order, chunks, starts_host, stops_host, n, flags, out_host, call.bufs, call.s, call.pipes.cp, call.ev,
-                           ev_k, ev_down, meta);
-    if ((rc = call.finish("pool_ranges", rc, nullptr, 0))) return rc;
-    EVAL_TRY(sum_pairs(call.ev, &g_pool_ms[0]));
-    EVAL_TRY(sum_pairs(ev_k, &g_pool_ms[1]));
-    EVAL_TRY(sum_pairs(ev_down, &g_pool_ms[2]));
+    rc = pool_host_enqueue((const char *)x_host, dtype, d, order, chunks, starts_host, stops_host, n, flags, out_host, call.bufs, call.s, call.pipes.cp,
+                           call.clock, meta);
+    if ((rc = call.finish("pool_ranges", rc))) return rc;
+    float ms[POOL_PHASES];
+    EVAL_TRY(call.clock.read(ms, POOL_PHASES));
+    memcpy(g_pool_ms, ms, sizeof ms);
     return 0;
 }
 

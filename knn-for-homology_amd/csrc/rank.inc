@@ -297,10 +297,12 @@ __global__ __launch_bounds__(256) void rank_gather_kernel(RankSrc<K> src, const 
 
 // ---- host -------------------------------------------------------------------------------
 // measurement (tools/bench_rank.py): how this thread's last successful knn_eval_rank ran
+// host clock: allocations, packing; HIP events (the clock's phases): upload, sort, scan of the flags, look-ups and downloads
+enum { RANK_ALLOC, RANK_PACK, RANK_UP, RANK_SORT, RANK_SCAN, RANK_LOOKUPS, RANK_PHASES };
 static thread_local struct {
     int32_t passes_run, passes_skipped;
     int64_t tiles;
-    float ms[6]; // host clock: allocations, packing; HIP events: upload, sort, scan of the flags, look-ups and downloads
+    float ms[RANK_PHASES];
 } g_rank_info = {0, 0, 0, {0, 0, 0, 0, 0, 0}};
 
 // table[0 .. m) becomes its exclusive scan (FLAGS = false, dst = src), or dst[i] = the running count of bit `bit` of src
@@ -377,10 +379,11 @@ static int rank_alloc(EvalBufs &bufs, const RankPlan &pl, RankSorted<K> &rs)
     return 0;
 }
 
-// packs, uploads and sorts; records three events: in front of the upload, behind it, behind the sort
+// packs, uploads and sorts.  On the clock the upload is an interval of up_phase (it ends whatever interval the caller has
+// open), the sort one of sort_phase, and the event behind the sort starts one of then_phase
 template <typename K>
-static int rank_sort(const void *scores, int64_t rows, int64_t k, int64_t limit, const uint8_t *correct, int desc, const RankPlan &pl, EventList &ev,
-                     RankSorted<K> &rs)
+static int rank_sort(const void *scores, int64_t rows, int64_t k, int64_t limit, const uint8_t *correct, int desc, const RankPlan &pl, PhaseClock &clock,
+                     int up_phase, int sort_phase, int then_phase, RankSorted<K> &rs)
 {
     typedef typename RankFloat<K>::F F;
     constexpr int P = (int)sizeof(K);
@@ -407,10 +410,10 @@ static int rank_sort(const void *scores, int64_t rows, int64_t k, int64_t limit,
         if (correct) up_correct = packed_correct.data();
     }
     rs.t_up = std::chrono::steady_clock::now();
-    EVAL_TRY(ev.mark(nullptr));
+    EVAL_TRY(clock.next(up_phase, nullptr));
     HIP_TRY(hipMemcpy(d_scores, up_scores, pl.scores_bytes, hipMemcpyHostToDevice));
     if (correct) HIP_TRY(hipMemcpy(d_correct, up_correct, pl.correct_bytes, hipMemcpyHostToDevice));
-    EVAL_TRY(ev.mark(nullptr));
+    EVAL_TRY(clock.next(sort_phase, nullptr));
     const RankSrc<K> src = {d_scores, d_correct, (uint32_t)pl.dev_k, (uint32_t)limit, desc};
     // ---- the sort
     HIP_TRY(hipMemset(d_hist, 0, pl.hist_bytes));
@@ -447,7 +450,7 @@ static int rank_sort(const void *scores, int64_t rows, int64_t k, int64_t limit,
     rs.keys = kin;
     rs.pay = pin;
     rs.nrun = nrun;
-    EVAL_TRY(ev.mark(nullptr));
+    EVAL_TRY(clock.next(then_phase, nullptr));
     return 0;
 }
 
@@ -463,7 +466,7 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
     // every buffer of the plan, by the plan's own sizes (plan_rank; plan_check walks them)
     const auto t_alloc = std::chrono::steady_clock::now();
     EvalBufs bufs;
-    EventList ev;
+    PhaseClock clock;
     RankSorted<K> rs;
     EVAL_TRY(rank_alloc<K>(bufs, pl, rs));
     uint32_t *d_c = nullptr;
@@ -479,7 +482,7 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
     size_t allocated = 0;
     for (const auto &b : bufs.dev) allocated += b.second;
     if (allocated != pl.resident_bytes) return set_err(KNN_ERR_INVALID, "rank: the buffers are not the plan's");
-    EVAL_TRY(rank_sort<K>(scores, rows, k, limit, correct, desc, pl, ev, rs));
+    EVAL_TRY(rank_sort<K>(scores, rows, k, limit, correct, desc, pl, clock, RANK_UP, RANK_SORT, RANK_SCAN, rs));
     const auto t_pack = rs.t_pack, t_up = rs.t_up;
     const RankSrc<K> src = rs.src;
     uint32_t *d_partial = rs.d_partial;
@@ -487,7 +490,7 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
     const int nrun = rs.nrun;
     // ---- C(r)
     if (want_c) EVAL_TRY(rank_scan<true>(d_pay, (uint64_t)n, d_partial, d_c));
-    EVAL_TRY(ev.mark(nullptr));
+    EVAL_TRY(clock.next(RANK_LOOKUPS, nullptr));
     // ---- look-ups
     const unsigned wide_grid = (unsigned)std::min<int64_t>(65536, (pl.n + 255) / 256);
     if (order_out) {
@@ -519,11 +522,13 @@ static int rank_run(const void *scores, int64_t rows, int64_t k, int64_t limit, 
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(sorted_at_out, d_at, (size_t)nr * sizeof(F), hipMemcpyDeviceToHost));
     }
-    EVAL_TRY(ev.mark(nullptr));
+    EVAL_TRY(clock.close(nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    g_rank_info.ms[0] = std::chrono::duration<float, std::milli>(t_pack - t_alloc).count();
-    g_rank_info.ms[1] = std::chrono::duration<float, std::milli>(t_up - t_pack).count();
-    for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&g_rank_info.ms[2 + i], ev.ev[i], ev.ev[i + 1]));
+    float ms[RANK_PHASES];
+    EVAL_TRY(clock.read(ms, RANK_PHASES));
+    ms[RANK_ALLOC] = std::chrono::duration<float, std::milli>(t_pack - t_alloc).count();
+    ms[RANK_PACK] = std::chrono::duration<float, std::milli>(t_up - t_pack).count();
+    memcpy(g_rank_info.ms, ms, sizeof ms);
     g_rank_info.passes_run = nrun;
     g_rank_info.passes_skipped = P - nrun;
     g_rank_info.tiles = pl.ntiles;
@@ -565,6 +570,6 @@ extern "C" int knn_last_rank_info(int32_t *passes_run, int32_t *passes_skipped, 
     *passes_run = g_rank_info.passes_run;
     *passes_skipped = g_rank_info.passes_skipped;
     *tiles = g_rank_info.tiles;
-    for (int i = 0; i < 6; i++) ms[i] = g_rank_info.ms[i];
+    for (int i = 0; i < RANK_PHASES; i++) ms[i] = g_rank_info.ms[i];
     return 0;
 }

@@ -107,18 +107,15 @@ __global__ __launch_bounds__(256, 2) void refine_rescore_kernel(RefineParams p)
 }
 
 // ---- host -------------------------------------------------------------------------------
-// The events of one call (refine_batch): three per batch -- in front of the rescore launch, between it and the selection,
-// behind it.  After the stream has drained: the batches' times summed into ms[0] (rescore), ms[1] (selection)
-static int refine_sum_ms(const EventList &ev, float *ms)
+// the phases of knn_index_s::refine_ms: the rescore launch and the selection of every batch (refine_batch)
+enum { REFINE_RESCORE, REFINE_SELECT, REFINE_PHASES };
+
+// after the stream has drained: the clock of a call's refine_batches into flat->refine_ms
+static int refine_commit_ms(const PhaseClock &clock, knn_index_s *flat)
 {
-    ms[0] = ms[1] = 0.0f;
-    for (size_t i = 0; i + 2 < ev.ev.size(); i += 3) {
-        float a = 0, b = 0;
-        HIP_TRY(hipEventElapsedTime(&a, ev.ev[i], ev.ev[i + 1]));
-        HIP_TRY(hipEventElapsedTime(&b, ev.ev[i + 1], ev.ev[i + 2]));
-        ms[0] += a;
-        ms[1] += b;
-    }
+    float ms[REFINE_PHASES];
+    EVAL_TRY(clock.read(ms, REFINE_PHASES));
+    memcpy(flat->refine_ms, ms, sizeof ms);
     return 0;
 }
 
@@ -126,7 +123,7 @@ static int refine_sum_ms(const EventList &ev, float *ms)
 // query in D_dev / I_dev [m][k], on stream s.  The caller holds flat->mu and has checked the labels' range or got them
 // from a search over the same number of rows.
 static int refine_batch(knn_index_s *flat, const float *xq_dev, const int64_t *labels_dev, int64_t m, int kb, int k, float *D_dev,
-                        int64_t *I_dev, hipStream_t s, EventList &ev)
+                        int64_t *I_dev, hipStream_t s, PhaseClock &clock)
 {
     RefineParams p;
     if (!(p.keys = scratch<uint64_t>(flat, flat->ws_rfkeys, (size_t)m * kb, s, "refine: out of device memory"))) return KNN_ERR_HIP;
@@ -135,17 +132,16 @@ static int refine_batch(knn_index_s *flat, const float *xq_dev, const int64_t *l
     const unsigned grid = (unsigned)(m * ((kb + RF_ROWS - 1) / RF_ROWS));
     void (*kern)(RefineParams) = flat->metric == KNN_METRIC_L2 ? refine_rescore_kernel<true> : refine_rescore_kernel<false>;
     HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RF_LDS));
-    int rc = ev.mark(s);
-    if (rc) return rc;
+    EVAL_TRY(clock.open(REFINE_RESCORE, s));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), RF_LDS, s, p);
     HIP_TRY(hipGetLastError());
-    if ((rc = ev.mark(s))) return rc;
+    EVAL_TRY(clock.next(REFINE_SELECT, s));
     SelectParams sp = {};
     sp.in = p.keys; sp.in_stride = kb; sp.n_fixed = kb; sp.cap = kb;
     sp.nq = m; sp.k = k; sp.metric = flat->metric;
     sp.D = D_dev; sp.I = I_dev;
-    if ((rc = launch_select(sp, s))) return rc;
-    return ev.mark(s);
+    EVAL_TRY(launch_select(sp, s));
+    return clock.close(s);
 }
 
 static int refine_check_shape(int64_t nq, int64_t kb, int64_t k, const char *who)
@@ -192,13 +188,13 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
         !(lab_dev = scratch<int64_t>(h, h->ws_rfI, (size_t)mb * kb, s, oom)) || !(D_dev = scratch<float>(h, h->ws_rfD, (size_t)mb * k, s, oom)) ||
         !(I_dev = scratch<int64_t>(h, h->ws_rfI2, (size_t)mb * k, s, oom)))
         return KNN_ERR_HIP;
-    EventList ev;
+    PhaseClock clock;
     for (int64_t b0 = 0; b0 < nq; b0 += QB) {
         const int64_t m = std::min(QB, nq - b0);
         HIP_TRY(hipMemcpyAsync(q_dev, q_host + b0 * h->d, (size_t)m * h->d * 4, hipMemcpyHostToDevice, s));
         if (h->dp != h->d && (rc = pad_rows_dev(q_dev, m, h->d, qp_dev, h->dp, s))) return rc;
         HIP_TRY(hipMemcpyAsync(lab_dev, labels_host + b0 * kb, (size_t)m * kb * 8, hipMemcpyHostToDevice, s));
-        rc = refine_batch(h, qp_dev ? qp_dev : q_dev, lab_dev, m, (int)kb, (int)k, D_dev, I_dev, s, ev);
+        rc = refine_batch(h, qp_dev ? qp_dev : q_dev, lab_dev, m, (int)kb, (int)k, D_dev, I_dev, s, clock);
         if (rc) {
             (void)hipStreamSynchronize(s); // (nothing of this batch is left running behind the error)
             return rc;
@@ -207,7 +203,7 @@ extern "C" int knn_flat_refine(knn_handle h, const float *q_host, int64_t nq, co
         HIP_TRY(hipMemcpyAsync(I_host + b0 * k, I_dev, (size_t)m * k * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    return refine_sum_ms(ev, h->refine_ms);
+    return refine_commit_ms(clock, h);
 }
 
 // measurement (tools/refine_probe.py): HIP-event milliseconds of the last successful knn_flat_refine /

@@ -161,9 +161,11 @@ __global__ __launch_bounds__(256) void window_ranges_kernel(RankSrc<K> src, cons
 
 // ---- host -------------------------------------------------------------------------------
 // measurement (tools/bench_windows.py): how this thread's last successful knn_eval_windows ran
+// host clock: allocations; HIP events (the clock's phases): upload, sort, gather and scans, chains, means, bins, downloads
+enum { WIN_ALLOC, WIN_UP, WIN_SORT, WIN_GATHER, WIN_CHAINS, WIN_MEANS, WIN_BINS, WIN_DOWN, WIN_PHASES };
 static thread_local struct {
     int64_t run, blocks_per_run, runs_per_block;
-    float ms[8]; // host clock: allocations; HIP events: upload, sort, gather and scans, chains, means, bins, downloads
+    float ms[WIN_PHASES];
 } g_windows_info = {0, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
 
 template <typename K>
@@ -177,7 +179,7 @@ static int windows_run(const void *keys, const uint8_t *values, int desc, const 
     const int64_t nb = pl.nbins, W = pl.window, nout = pl.nout;
     const auto t_alloc = std::chrono::steady_clock::now();
     EvalBufs bufs;
-    EventList ev;
+    PhaseClock clock;
     RankSorted<K> rs;
     EVAL_TRY(rank_alloc<K>(bufs, pl.rank, rs));
     auto opt = [&](size_t bytes, bool &ok) -> void * {
@@ -202,7 +204,7 @@ static int windows_run(const void *keys, const uint8_t *values, int desc, const 
     for (const auto &b : bufs.dev) allocated += b.second;
     if (allocated != pl.resident_bytes) return set_err(KNN_ERR_INVALID, "windows: the buffers are not the plan's");
     const auto t_up = std::chrono::steady_clock::now();
-    EVAL_TRY(ev.mark(nullptr)); // 0
+    EVAL_TRY(clock.open(WIN_UP, nullptr)); // the columns and the bins' vectors (the keys: rank_sort's interval of the phase)
     if (m) HIP_TRY(hipMemcpy(d_values, values, pl.values_bytes, hipMemcpyHostToDevice));
     WindowBins<K> bins = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (nb) {
@@ -220,7 +222,7 @@ static int windows_run(const void *keys, const uint8_t *values, int desc, const 
             HIP_TRY(hipMemcpy(bins.stop, stops, (size_t)nb * 8, hipMemcpyHostToDevice));
         }
     }
-    EVAL_TRY(rank_sort<K>(keys, pl.n, 1, 1, nullptr, desc, pl.rank, ev, rs)); // 1, 2, 3
+    EVAL_TRY(rank_sort<K>(keys, pl.n, 1, 1, nullptr, desc, pl.rank, clock, WIN_UP, WIN_SORT, WIN_GATHER, rs));
     // ---- masks, keys in rank order, C_c(r)
     if (d_mask || d_keyd) {
         hipLaunchKernelGGL(window_gather_kernel<K>, dim3((unsigned)pl.gather_grid), dim3(256), 0, 0, rs.src, rs.pay, n, (const uint8_t *)d_values, m, d_mask,
@@ -228,9 +230,9 @@ static int windows_run(const void *keys, const uint8_t *values, int desc, const 
         HIP_TRY(hipGetLastError());
     }
     for (int c = 0; c < m; c++) EVAL_TRY(rank_scan<true>(d_mask, (uint64_t)n, d_wpartial, d_cum + (size_t)c * n, c));
-    EVAL_TRY(ev.mark(nullptr)); // 4
-    // ---- the key's chains
+    // ---- the key's chains (a phase that does not run has no interval: it reads exactly 0)
     if (W) {
+        EVAL_TRY(clock.next(WIN_CHAINS, nullptr));
         hipLaunchKernelGGL(window_chain_kernel, dim3((unsigned)pl.chain_grid), dim3(256), pl.chain_lds, 0, (const double *)d_keyd, pl.n, W, pl.run, pl.group,
                            (int)pl.blocks_per_run, d_P, d_S);
         HIP_TRY(hipGetLastError());
@@ -238,20 +240,20 @@ static int windows_run(const void *keys, const uint8_t *values, int desc, const 
                            d_means + (size_t)m * nout);
         HIP_TRY(hipGetLastError());
     }
-    EVAL_TRY(ev.mark(nullptr)); // 5
     if (W && m) {
+        EVAL_TRY(clock.next(WIN_MEANS, nullptr));
         hipLaunchKernelGGL(window_means_kernel, dim3((unsigned)pl.means_grid, (unsigned)m), dim3(256), 0, 0, (const uint32_t *)d_cum, n, (uint32_t)W,
                            (uint32_t)nout, d_means);
         HIP_TRY(hipGetLastError());
     }
-    EVAL_TRY(ev.mark(nullptr)); // 6
     if (nb) {
+        EVAL_TRY(clock.next(WIN_BINS, nullptr));
         hipLaunchKernelGGL(window_ranges_kernel<K>, dim3((unsigned)pl.ranges_grid), dim3(256), 0, 0, rs.src, rs.keys, rs.pay, (const uint32_t *)d_cum, pl.n, m, nb,
                            bins);
         HIP_TRY(hipGetLastError());
     }
-    EVAL_TRY(ev.mark(nullptr)); // 7
     // ---- downloads
+    EVAL_TRY(clock.next(WIN_DOWN, nullptr));
     if (order_out) {
         hipLaunchKernelGGL(rank_order_kernel, dim3((unsigned)pl.gather_grid), dim3(256), 0, 0, rs.pay, n, d_wide);
         HIP_TRY(hipGetLastError());
@@ -268,13 +270,12 @@ static int windows_run(const void *keys, const uint8_t *values, int desc, const 
         HIP_TRY(hipMemcpy(key_lo_out, bins.key_lo, (size_t)nb * sizeof(F), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(key_hi_out, bins.key_hi, (size_t)nb * sizeof(F), hipMemcpyDeviceToHost));
     }
-    EVAL_TRY(ev.mark(nullptr)); // 8
+    EVAL_TRY(clock.close(nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    float t[8];
-    for (int i = 0; i < 8; i++) HIP_TRY(hipEventElapsedTime(&t[i], ev.ev[i], ev.ev[i + 1]));
-    g_windows_info.ms[0] = std::chrono::duration<float, std::milli>(t_up - t_alloc).count();
-    g_windows_info.ms[1] = t[0] + t[1]; // the columns and the bins' vectors, then the keys
-    for (int i = 2; i < 8; i++) g_windows_info.ms[i] = t[i];
+    float ms[WIN_PHASES];
+    EVAL_TRY(clock.read(ms, WIN_PHASES));
+    ms[WIN_ALLOC] = std::chrono::duration<float, std::milli>(t_up - t_alloc).count();
+    memcpy(g_windows_info.ms, ms, sizeof ms);
     g_windows_info.run = pl.run;
     g_windows_info.blocks_per_run = pl.blocks_per_run;
     g_windows_info.runs_per_block = pl.runs_per_block;
@@ -327,6 +328,6 @@ extern "C" int knn_last_windows_info(int64_t *run, int64_t *blocks_per_run, int6
     *run = g_windows_info.run;
     *blocks_per_run = g_windows_info.blocks_per_run;
     *runs_per_block = g_windows_info.runs_per_block;
-    for (int i = 0; i < 8; i++) ms[i] = g_windows_info.ms[i];
+    for (int i = 0; i < WIN_PHASES; i++) ms[i] = g_windows_info.ms[i];
     return 0;
 }
