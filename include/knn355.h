@@ -635,6 +635,55 @@ int knn_eval_windows(const void *keys, int32_t key_type, int64_t n, const uint8_
  * a window), and milliseconds ms[8]: on the host's clock the device allocations; by HIP events the uploads, the sort, the
  * gather with the scans, the chains with their combination, the columns' means, the bins, the downloads. */
 int knn_last_windows_info(int64_t *run, int64_t *blocks_per_run, int64_t *runs_per_block, float *ms /* [8] */);
+/* Tie-averaged ranks and the two correlations of cath/cath.py:949-952 (scipy.stats.pearsonr of the cosine scores and the
+ * logged E-values, scipy.stats.spearmanr of the scores and the E-values) over every hit of a result set.  All pointers are
+ * host pointers.  An array is [rows][k], float32 (KNN_RANK_F32) or float64 (KNN_RANK_F64); its elements are the N = rows *
+ * limit cells of columns 0 .. limit-1, flat position p = row * limit + column, as in knn_eval_rank; 2 <= N <= 2^31 - 1.
+ *   knn_eval_rankdata   rank2_out int64 [N]: rank2_out[p] = twice the average rank of cell p among all N, an exact integer
+ *               in [2, 2N]: in knn_eval_rank's ascending order (keys compared by their order-preserving images: -0.0 equals
+ *               +0.0, +-inf order by value) every member of a run of equal keys at the 0-based ranks s .. e gets s + e + 2.
+ *               rank2_out / 2 is scipy.stats.rankdata(a[:, :limit].ravel(), "average"), bit for bit.  *nan_count_out
+ *               receives the number of NaN cells; when it is not 0 no rank is written (scipy's nan_policy="propagate": every
+ *               statistic of such input is NaN) and the call still returns 0.
+ *   knn_eval_correlate  x and y have the same shape and either type, independently.  what is a bit set:
+ *               KNN_CORR_PEARSON: pearson_out float64 [5] = mean_x, mean_y, Sxx, Sxy, Syy.  Every value is widened to float64
+ *               first.  mean = (the sum of the N values) / N; then, with dx = x - mean_x and dy = y - mean_y, Sxx = the sum of
+ *               dx * dx, Sxy of dx * dy, Syy of dy * dy (two passes, nothing fused, as scipy does).  Every one of the five
+ *               sums is taken in ONE order that is a function of N alone (plan_correlate in csrc/plan.h): tiles of 2048
+ *               consecutive terms; lane j of 256 adds terms j, j + 256, ... of its tile in that order to +0.0; the lanes fold
+ *               by lane[j] += lane[j + off], off = 128, 64, ..., 1; the tiles' sums, in tile order, are summed the same way,
+ *               level by level, until one is left.  No floating-point atomic, nothing that depends on the grid or on the
+ *               order in which workgroups finish.  An infinity or a NaN goes through this arithmetic as IEEE 754 has it
+ *               (inf - inf = NaN): nothing is special-cased.  The statistic is Sxy / (sqrt(Sxx) * sqrt(Syy)), the caller's.
+ *               KNN_CORR_SPEARMAN: spearman_out uint64 [6] = (lo, hi) words of the three 128-bit two's-complement sums of
+ *               u * u, u * v and v * v over the doubled, centred ranks u = rank2_x - (N + 1), v = rank2_y - (N + 1): exact
+ *               integers (a term is below 2^62 in magnitude, a sum below 2^93); no floating-point number is rounded on the
+ *               device.  nan_count_out int64 [2] receives the NaN cells of x and of y; when either is not 0, spearman_out is
+ *               left untouched.  With KNN_CORR_PEARSON alone nothing is sorted and nan_count_out (may be NULL) is left
+ *               untouched: a NaN shows in the sums.
+ * KNN_ERR_INVALID, before anything is allocated or launched and with the outputs untouched: an unknown type; rows < 1; k < 1
+ * or k > INT32_MAX; limit outside [1, k]; N outside [2, 2^31 - 1]; a null input; what outside [1, 3]; a null rank2_out or
+ * nan_count_out (rankdata); KNN_CORR_PEARSON with a null pearson_out; KNN_CORR_SPEARMAN with a null spearman_out or
+ * nan_count_out.
+ * The whole problem stays on the device for the call; plan_correlate in csrc/plan.h has every buffer's bytes, the levels of
+ * the sums and the grids, and the call allocates exactly those.  The sorts of x and of y run one after the other in the
+ * same key and payload buffers.
+ * Hot path (correlate.inc): the sort of rank.inc with the flat position as payload; tie_heads_kernel (rank r heads a run
+ * when its key image differs from rank r - 1's), rank.inc's scan of the head flags (the run number of every rank),
+ * tie_starts_kernel (every head writes its run's first rank), tie_scatter_kernel (rank2[position] = start + end + 2);
+ * moment_int_kernel and moment_f64_kernel, one launch per level.  No workgroup waits on another, no atomic, plain vector
+ * stores only. */
+#define KNN_CORR_PEARSON 1
+#define KNN_CORR_SPEARMAN 2
+int knn_eval_rankdata(const void *a, int32_t key_type, int64_t rows, int64_t k, int64_t limit, int64_t *rank2_out,
+                      int32_t *nan_count_out);
+int knn_eval_correlate(const void *x, int32_t x_type, const void *y, int32_t y_type, int64_t rows, int64_t k, int64_t limit,
+                       int32_t what, double *pearson_out /* [5] */, uint64_t *spearman_out /* [6] */,
+                       int64_t *nan_count_out /* [2] */);
+/* measurement (tools/bench_correlation.py): milliseconds ms[6] of the calling thread's last successful knn_eval_rankdata or
+ * knn_eval_correlate: on the host's clock the device allocations; by HIP events the uploads (with the host's packing of the
+ * first `limit` columns), the sorts, the ranks (heads, scan, starts, scatter, NaN count), the moments, the downloads. */
+int knn_last_correlate_info(float *ms /* [6] */);
 /* cath/cath.py:404-438 bootstrap_scores, the replicates behind the "+-" of the accuracy table (:441-458): per method and
  * per resample of the evaluable queries, the raw and the superfamily-normalized top-1 accuracy.  All arrays are host
  * arrays.  is_correct uint8 [nm][n]: row m is method m's verdict for each of the n evaluable queries, a non-zero byte

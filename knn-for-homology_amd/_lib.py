@@ -143,6 +143,9 @@ def _declare(L):
         "knn_eval_windows": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
         "knn_last_windows_info": (c_int32, [i64p, i64p, i64p, f32p]),
+        "knn_eval_rankdata": (c_int32, [c_void_p, c_int32, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int32)]),
+        "knn_eval_correlate": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+        "knn_last_correlate_info": (c_int32, [f32p]),
         "knn_eval_bootstrap": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
         "knn_pca_moments": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),

@@ -32,3 +32,4 @@
 #include "pool.inc"
 #include "kde.inc"
 #include "mix.inc"
+#include "correlate.inc"

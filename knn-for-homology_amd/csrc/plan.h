@@ -853,6 +853,88 @@ static bool plan_windows(int64_t n, int key_bytes, int64_t m, int64_t window, bo
     return true;
 }
 
+// ---- tie-averaged ranks and correlation moments (correlate.inc) --------------------
+// The order of every sum of the moments, a function of N alone.  The N terms are cut into tiles of CORR_TILE consecutive
+// terms; lane j of a tile's CORR_LANES lanes adds, to a +0.0 it starts from, the terms corr_term(tile, j, 0), (tile, j, 1),
+// ... in that order (the ones below N); the lanes' sums are folded by the tree lane[j] = lane[j] + lane[j + off] for j <
+// off, off = CORR_LANES / 2, ..., 2, 1; lane 0 holds the tile's sum.  The tiles' sums, in tile order, are the terms of the
+// next level, summed the same way, until one is left: level_n[0] = N, level_n[i + 1] = ceil(level_n[i] / CORR_TILE).
+// moment_kernel and correlate_check.cpp both call corr_term: the kernel has no layout of its own.
+static const int CORR_TILE = 2048;    // terms of one workgroup
+static const int CORR_LANES = 256;    // its threads: CORR_TILE / CORR_LANES terms each
+static const int CORR_MAX_LEVELS = 3; // 2^31 - 1 -> 2^20 -> 512 -> 1
+static const int CORR_GRID = 65536;   // workgroups, at most, of the grid-stride tie kernels
+
+PLAN_HD static inline uint64_t corr_term(uint64_t tile, int lane, int i) { return tile * CORR_TILE + (uint64_t)i * CORR_LANES + lane; }
+
+struct CorrelatePlan {
+    RankPlan rank_x, rank_y; // the two orders: plan_rank(rows, k, limit, the array's bytes, no flags, running count, no wide)
+    int64_t n;               // rows * limit pairs
+    int what;                // KNN_CORR_PEARSON | KNN_CORR_SPEARMAN; 0: the doubled ranks of x alone (knn_eval_rankdata)
+    bool sorts;              // any order at all: what != KNN_CORR_PEARSON
+    int levels;              // launches of one reduction: 1 .. CORR_MAX_LEVELS
+    int64_t level_n[CORR_MAX_LEVELS + 1]; // terms of every level; level_n[levels] = 1
+    int64_t tie_grid;        // workgroups of 256 of tie_heads / tie_starts / tie_scatter
+    // every device buffer of a call: the entries allocate exactly these (0: not allocated)
+    size_t x_bytes, y_bytes;            // the device copies (rank_x.scores_bytes, rank_y.scores_bytes)
+    size_t keys_bytes, pay_bytes;       // ONE key / payload buffer, the wider array's; both sorts ping-pong between the same two of each
+    size_t table_bytes, partial_bytes;  // the digit counts; the block sums of the scan of the N head flags
+    size_t hist_bytes;                  // the digit histograms, the wider array's
+    size_t run_bytes;                   // uint32 [N]: the head flags, then (scanned in place) the 1-based run number of every rank
+    size_t start_bytes;                 // uint32 [N + 1]: the first rank of every run, and N behind the last
+    size_t rank2_bytes;                 // ONE doubled-rank buffer: int64 [N] for rankdata, uint32 [N] for Spearman (which has two)
+    int rank2_buffers;                  // 1, 2, or 0
+    size_t nan_bytes;                   // int64 [2]: NaN cells of x and of y
+    size_t moment_a_bytes, moment_b_bytes; // the partial sums of levels 1 and 2, three quantities each: float64, or 128-bit integers for Spearman
+    size_t resident_bytes;              // the sum
+};
+
+// false: not a legal problem (what plan_rank refuses, a width other than 4 or 8 bytes, N below 2, `what` outside the bit
+// set; y_bytes is 0 exactly when what is 0)
+static bool plan_correlate(int64_t rows, int64_t k, int64_t limit, int x_bytes, int y_bytes, int what, CorrelatePlan *out)
+{
+    if (what < 0 || what > (KNN_CORR_PEARSON | KNN_CORR_SPEARMAN)) return false;
+    if ((what == 0) != (y_bytes == 0)) return false;
+    CorrelatePlan pl;
+    if (!plan_rank(rows, k, limit, x_bytes, false, true, false, &pl.rank_x)) return false;
+    if (y_bytes && !plan_rank(rows, k, limit, y_bytes, false, true, false, &pl.rank_y)) return false;
+    if (!y_bytes) pl.rank_y = pl.rank_x;
+    if (pl.rank_x.n < 2) return false;
+    pl.n = pl.rank_x.n;
+    pl.what = what;
+    pl.sorts = what != KNN_CORR_PEARSON;
+    pl.levels = 0;
+    pl.level_n[0] = pl.n;
+    for (int i = 1; i <= CORR_MAX_LEVELS; i++) pl.level_n[i] = 1;
+    while (pl.level_n[pl.levels] > 1) {
+        if (pl.levels == CORR_MAX_LEVELS) return false; // (never: N <= 2^31 - 1)
+        pl.level_n[pl.levels + 1] = (pl.level_n[pl.levels] + CORR_TILE - 1) / CORR_TILE;
+        pl.levels++;
+    }
+    pl.tie_grid = std::min<int64_t>(CORR_GRID, (pl.n + 255) / 256);
+    const RankPlan &wide = pl.rank_y.key_bytes > pl.rank_x.key_bytes ? pl.rank_y : pl.rank_x;
+    const size_t n = (size_t)pl.n;
+    pl.x_bytes = pl.rank_x.scores_bytes;
+    pl.y_bytes = y_bytes ? pl.rank_y.scores_bytes : 0;
+    pl.keys_bytes = pl.sorts ? wide.keys_bytes : 0;
+    pl.pay_bytes = pl.sorts ? wide.pay_bytes : 0;
+    pl.table_bytes = pl.sorts ? wide.table_bytes : 0;
+    pl.partial_bytes = pl.sorts ? wide.partial_bytes : 0;
+    pl.hist_bytes = pl.sorts ? wide.hist_bytes : 0;
+    pl.run_bytes = pl.sorts ? n * 4 : 0;
+    pl.start_bytes = pl.sorts ? (n + 1) * 4 : 0;
+    pl.rank2_bytes = pl.sorts ? n * (what ? 4 : 8) : 0;
+    pl.rank2_buffers = pl.sorts ? (what ? 2 : 1) : 0;
+    pl.nan_bytes = pl.sorts ? 16 : 0;
+    const size_t entry = 3 * (size_t)((what & KNN_CORR_SPEARMAN) ? 16 : 8);
+    pl.moment_a_bytes = what ? (size_t)pl.level_n[1] * entry : 0;
+    pl.moment_b_bytes = what ? (size_t)pl.level_n[2] * entry : 0;
+    pl.resident_bytes = pl.x_bytes + pl.y_bytes + 2 * pl.keys_bytes + 2 * pl.pay_bytes + pl.table_bytes + pl.partial_bytes + pl.hist_bytes + pl.run_bytes +
+                        pl.start_bytes + (size_t)pl.rank2_buffers * pl.rank2_bytes + pl.nan_bytes + pl.moment_a_bytes + pl.moment_b_bytes;
+    *out = pl;
+    return true;
+}
+
 // ---- mean pooling over row ranges (pool.inc) ---------------------------------------
 static const int POOL_COLS = 256;      // columns of one wave: 64 lanes x 4
 static const int POOL_GROUP = 8;       // rows whose loads are issued in front of the first add of the group

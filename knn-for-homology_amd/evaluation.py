@@ -24,7 +24,9 @@ Each function keeps the semantics of the reference's per-row Python loop it repl
   combine_hits               pfam/proteins.py:216-240 ("combined": MMseqs2 hits with E < 0.1, filled up with k-NN hits)
   merge_hits                 pfam/proteins.py:340-372 ("both aligned": two lists sorted together, repeated ids dropped)
   compare_hits               pfam/pfam.py:349-370, 602-625 (two lists as sets of ids: "TP Set overlap" and auc1s_optimal)
+  pearsonr, spearmanr, correlations, rankdata  cath/cath.py:949-952 (the correlations of cosine scores and E-values)
 """
+import math
 from collections import Counter, namedtuple
 from itertools import groupby
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Set, Tuple
@@ -1016,6 +1018,180 @@ def score_quantiles(scores: ndarray, q: ndarray, limit: int = None) -> ndarray:
     ranks = np.concatenate([previous, following, [-1]]) % n
     _, _, _, _, at = _rank(scores, None, limit, ranks=ranks)
     return _quantile_lerp(at[:q.size], at[q.size:2 * q.size], gamma, at[-1])
+
+
+# ---- tie-averaged ranks and correlations: knn_eval_rankdata, knn_eval_correlate (include/knn355.h) --------------------
+KNN_CORR_PEARSON, KNN_CORR_SPEARMAN = 1, 2  # include/knn355.h
+
+
+class CorrelationResult(NamedTuple):
+    statistic: float
+    pvalue: float
+
+
+def _correlate_arrays(x, y, limit, who):
+    """-> (x, y, limit): float32 / float64 [rows, k] each, independently, of one shape, two pairs at least"""
+    x, _, lim = _rank_arrays(x, None, limit, True, who)
+    if y is not None:
+        y, _, _ = _rank_arrays(y, None, limit, True, who)
+        if x.shape != y.shape:
+            raise ValueError(f"{who}: x {x.shape} and y {y.shape} must have the same shape")
+    if x.shape[0] * lim < 2:
+        raise ValueError(f"{who}: two values at least are needed")
+    return x, y, lim
+
+
+def _wide_sum(lo, hi) -> int:
+    """the Python integer of a 128-bit two's-complement sum returned as two uint64 words"""
+    v = int(lo) | (int(hi) << 64)
+    return v - (1 << 128) if v >> 127 else v
+
+
+def _ratio(sab: float, saa: float, sbb: float) -> float:
+    """sab / (sqrt(saa) * sqrt(sbb)) clipped to [-1, 1]; NaN for a zero denominator (constant input) and for NaN sums"""
+    den = math.sqrt(saa) * math.sqrt(sbb) if saa >= 0 and sbb >= 0 else math.nan
+    if den == 0 or den != den or sab != sab:
+        return math.nan
+    r = sab / den
+    return r if r != r else max(-1.0, min(1.0, r))
+
+
+def correlation_pvalue(kind: str, r: float, n: int) -> float:
+    """The two-sided p-value scipy.stats reports beside a statistic r over n pairs.  kind "pearson": the exact
+    distribution of r under independence, 2 * betainc(n / 2 - 1, n / 2 - 1, (1 - |r|) / 2) (1.0 for n = 2); kind
+    "spearman": Student's t with n - 2 degrees of freedom at r * sqrt((n - 2) / ((r + 1) (1 - r))).  Pure host
+    arithmetic through scipy.special, imported here: NaN when scipy is not installed, and for a NaN statistic."""
+    if kind not in ("pearson", "spearman"):
+        raise ValueError(f"correlation_pvalue: kind must be 'pearson' or 'spearman', not {kind!r}")
+    if r != r:
+        return math.nan
+    try:
+        from scipy import special
+    except ImportError:
+        return math.nan
+    if kind == "pearson":
+        if n == 2:
+            return 1.0
+        return float(2 * special.betainc(n / 2 - 1, n / 2 - 1, 0.5 * (1 - abs(r))))
+    dof = n - 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = r * np.sqrt(np.clip(np.float64(dof) / np.float64((r + 1.0) * (1.0 - r)), 0, None))
+    return float(2 * special.stdtr(dof, -abs(t)))
+
+
+def pearson_statistic(moments: ndarray) -> float:
+    """r from knn_eval_correlate's five numbers (mean_x, mean_y, Sxx, Sxy, Syy): Sxy / (sqrt(Sxx) * sqrt(Syy))"""
+    return _ratio(float(moments[3]), float(moments[2]), float(moments[4]))
+
+
+def spearman_statistic(suu: int, suv: int, svv: int) -> float:
+    """rho from the exact integer sums over the doubled, centred ranks: float(Suv) / (sqrt(float(Suu)) * sqrt(float(Svv))).
+    Where the integers themselves say |rho| = 1 (Suv^2 = Suu Svv, neither 0: a perfectly monotone relation) the result is
+    exactly +-1, which the product of two rounded square roots may miss by an ulp."""
+    if suu and svv and suv * suv == suu * svv:
+        return 1.0 if suv > 0 else -1.0
+    return _ratio(float(suv), float(suu), float(svv))
+
+
+def _correlate(x, y, limit, what):
+    """knn_eval_correlate on checked arrays -> (the five Pearson numbers or None, (Suu, Suv, Svv) or None -- not asked
+    for, or a NaN in either array --, N)"""
+    rows, k = x.shape
+    pear = np.full(5, np.nan) if what & KNN_CORR_PEARSON else None
+    words = np.zeros(6, np.uint64) if what & KNN_CORR_SPEARMAN else None
+    nan = np.zeros(2, np.int64)
+
+    def ptr(a):
+        return a.ctypes.data if a is not None else None
+
+    _lib.check(_lib.lib().knn_eval_correlate(x.ctypes.data, 1 if x.dtype == np.float64 else 0, y.ctypes.data, 1 if y.dtype == np.float64 else 0,
+                                             rows, k, limit, what, ptr(pear), ptr(words), nan.ctypes.data))
+    sums = None
+    if words is not None and not nan.any():
+        sums = tuple(_wide_sum(words[2 * q], words[2 * q + 1]) for q in range(3))
+    return pear, sums, rows * limit
+
+
+def _pearson_result(pear, n):
+    r = pearson_statistic(pear)
+    return CorrelationResult(r, correlation_pvalue("pearson", r, n))
+
+
+def _spearman_result(sums, n):
+    r = spearman_statistic(*sums) if sums is not None else math.nan
+    return CorrelationResult(r, correlation_pvalue("spearman", r, n))
+
+
+def last_correlate_ms():
+    """How this thread's last rankdata / pearsonr / spearmanr / correlations ran on the device, in milliseconds: the device
+    allocations (host clock), then uploads, the sorts, the ranks (tie runs and scatter), the moments and the downloads (HIP
+    events)."""
+    from ctypes import c_float
+    ms = (c_float * 6)()
+    _lib.check(_lib.lib().knn_last_correlate_info(ms))
+    return dict(zip(("alloc_ms", "upload_ms", "sort_ms", "ranks_ms", "moments_ms", "download_ms"), ms))
+
+
+def rankdata(a: ndarray, limit: int = None) -> ndarray:
+    """scipy.stats.rankdata(a[:, :limit].ravel(), "average"), bit for bit -> float64 [N]: the 1-based rank of every
+    value, ties sharing the mean of their ranks (the ranks behind spearmanr, cath/cath.py:952).
+
+    a is float32 or float64, 2-D [rows, k] (limit=None: all k columns) or 1-D.  The device sorts every value at once
+    (knn_eval_rankdata), finds the runs of equal values -- -0.0 equals +0.0, infinities order by value -- and returns
+    twice the average rank as an exact integer; the halving here is exact.  With a NaN anywhere every rank is NaN, as
+    under scipy's default nan_policy="propagate".
+    Not here: the other tie methods, nan_policy="omit" or "raise", axis."""
+    from ctypes import byref, c_int32
+    a, _, limit = _correlate_arrays(a, None, limit, "rankdata")
+    rows, k = a.shape
+    rank2 = np.empty(rows * limit, np.int64)
+    nan = c_int32(0)
+    _lib.check(_lib.lib().knn_eval_rankdata(a.ctypes.data, 1 if a.dtype == np.float64 else 0, rows, k, limit, rank2.ctypes.data, byref(nan)))
+    if nan.value:
+        return np.full(rows * limit, np.nan)
+    return rank2 / 2
+
+
+def pearsonr(x: ndarray, y: ndarray, limit: int = None) -> CorrelationResult:
+    """scipy.stats.pearsonr(x[:, :limit].ravel(), y[:, :limit].ravel()) of cath/cath.py:949-951 (the cosine scores against
+    the logged E-values) -> CorrelationResult(statistic, pvalue).
+
+    x and y are float32 or float64, independently, of one shape: 2-D [rows, k] (limit=None: all k columns) or 1-D, two
+    pairs at least (ValueError otherwise, as scipy raises).  The device widens to float64, takes the two means and then
+    the centred sums Sxx, Sxy, Syy, each in one fixed order that depends on N alone (knn_eval_correlate: the same input
+    gives the same bits on every run and every device); statistic = Sxy / (sqrt(Sxx) * sqrt(Syy)), clipped to [-1, 1].
+    scipy divides by the norms first and sums in its BLAS's order, so its last bits differ.  The statistic is NaN for a
+    constant input and when a NaN or an infinity is present.  The pvalue is correlation_pvalue's: NaN without scipy.
+    Not here: `alternative` other than two-sided, `method`, `axis`, confidence intervals."""
+    x, y, limit = _correlate_arrays(x, y, limit, "pearsonr")
+    pear, _, n = _correlate(x, y, limit, KNN_CORR_PEARSON)
+    return _pearson_result(pear, n)
+
+
+def spearmanr(x: ndarray, y: ndarray, limit: int = None) -> CorrelationResult:
+    """scipy.stats.spearmanr(x[:, :limit].ravel(), y[:, :limit].ravel()) of cath/cath.py:952 (the cosine scores against
+    the E-values) -> CorrelationResult(statistic, pvalue).
+
+    Arrays as for pearsonr.  The device ranks both arrays (rankdata's ranks) and returns the exact integer sums Suu, Suv,
+    Svv over the doubled, centred ranks u = 2 rank_x - (N + 1), v = 2 rank_y - (N + 1); statistic = float(Suv) /
+    (sqrt(float(Suu)) * sqrt(float(Svv))) from those Python integers, clipped to [-1, 1]: no floating-point sum at all.
+    The statistic is NaN for a constant input and when a NaN is present (nan_policy="propagate"); infinities rank like any
+    value.  The pvalue is correlation_pvalue's: NaN without scipy.
+    Not here: `alternative` other than two-sided, nan_policy="omit" or "raise", `axis`, the matrix-valued form (x with
+    several columns as variables)."""
+    x, y, limit = _correlate_arrays(x, y, limit, "spearmanr")
+    _, sums, n = _correlate(x, y, limit, KNN_CORR_SPEARMAN)
+    return _spearman_result(sums, n)
+
+
+def correlations(x: ndarray, y: ndarray, limit: int = None) -> Tuple[CorrelationResult, CorrelationResult]:
+    """(pearsonr(x, y, limit), spearmanr(x, y, limit)) from one call: each array is uploaded once and sorted once.  Ranks
+    do not change under a monotone map, so for cath/cath.py:949-952 one call on (scores_best, logged) gives both of its
+    statements: logged is numpy.log of the E-values with the zeros' -inf moved to -1e9, below every other logarithm
+    (unless an E-value is +inf: the reference's isinf moves that logarithm to -1e9 as well, which is not monotone)."""
+    x, y, limit = _correlate_arrays(x, y, limit, "correlations")
+    pear, sums, n = _correlate(x, y, limit, KNN_CORR_PEARSON | KNN_CORR_SPEARMAN)
+    return _pearson_result(pear, n), _spearman_result(sums, n)
 
 
 KNN_FUSE_PREFIX_FILL, KNN_FUSE_SORTED_UNION = 0, 1  # include/knn355.h
